@@ -14,9 +14,11 @@ and exits with the children's status.  Under `python -m torch.distributed.run ..
 already set and each process is a rank.  `n_gpus` in the JSON is the world size the process group actually has.
 
 Extra keys on the same JSON line: "roofline" (dominant kernel, HBM-bound by SURVEY 8(d) accounting, timed with HIP
-events on the launch stream), "cpu_baseline" (the C oracle on the host cores, bounded sample), "mpc" (batched
+events on the launch stream); with --full also "cpu_baseline" (the C oracle on the host cores, bounded sample), "mpc" (batched
 calc_MPC_action throughput, N=30, xcg 0.35 -- BASELINE config 4), "config5_closed_loop" (BASELINE config 5 per GPU:
-8192 aircraft, T=100 closed-loop steps, then the timed all-gather of the [T,18,8192] shards).
+8192 aircraft, T=100 closed-loop steps, then the timed all-gather of the [T,18,8192] shards) and the other legs of run().
+A plain run (no --full) sets up, warms up, times --steps launches and prints the line; --dump-outputs DIR writes the last
+timed launch's results first (dump_outputs).
 """
 import argparse
 import json
@@ -40,6 +42,11 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4096, help="aircraft per GPU")
     ap.add_argument("--euler-steps", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (LQR closed loop, large batch, MPC, trim, horizon sweep, config 5, "
+                         "CPU baselines, the timed all-gather of a grouped run); the --no-* options below act on these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's shard) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-mpc", action="store_true")
     ap.add_argument("--no-large", action="store_true", help="skip the large-batch roofline leg")
@@ -261,6 +268,17 @@ def run(args):
     out["roofline"]["traffic"] = tr
     out["roofline"]["traffic_source"] = src
     out["roofline"]["issue"] = recorded_issue("k_rollout_q", kern_ms * 1e-3, batch=B, euler_steps=T)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env, traj)
+    if not args.full:
+        del traj
+        if rank == 0:
+            print(json.dumps(out))
+            sys.stdout.flush()
+        if grouped:
+            barrier()
+            dist.destroy_process_group()
+        return
     if grouped:
         # the one data-path collective -- all-gather of the trajectory shards -- timed on its own
         barrier()
@@ -340,6 +358,29 @@ def run(args):
     if grouped:
         barrier()
         dist.destroy_process_group()
+
+
+DUMP_TRAJ_BYTES = 48 << 20            # --dump-outputs: budget of the trajectory sample (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, env, traj):
+    """What a caller of f16_rollout receives from the last timed step: the final states x [B,18] and status words [B] in full,
+    and a fixed sample of the trajectory [T,18,B] (aircraft drawn once with seed 0, every time step while the sample fits
+    DUMP_TRAJ_BYTES, else every k-th step), with the indices it was taken at.  float64 throughout."""
+    import numpy as np
+    import torch
+    T, _, B = traj.shape
+    n = max(1, min(B, 256, DUMP_TRAJ_BYTES // (T * 18 * 8)))
+    air = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    stride = -(-T * 18 * 8 * n // DUMP_TRAJ_BYTES)
+    steps = np.arange(stride - 1, T, stride)                   # (the last step is always in the sample)
+    sample = traj.index_select(2, torch.as_tensor(air, device=traj.device)).index_select(0, torch.as_tensor(steps, device=traj.device))
+    os.makedirs(path, exist_ok=True)
+    arrays = {"x_final": env.x_values.cpu().numpy(), "status": env.status.cpu().numpy().astype(np.float64),
+              "traj_sample": sample.cpu().numpy(), "traj_sample_aircraft": air.astype(np.float64),
+              "traj_sample_steps": steps.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 SIMDS, ISSUE_PER_SIMD = 1024, 0.6e9       # 256 CUs x 4 SIMDs; one VALU wave-instruction per 4 cycles at 2.4 GHz (MI355X_MICROARCH.md)

@@ -1,7 +1,7 @@
 """The RCCL path on the one GPU the builder's box has: a REAL `nccl` process group of world size 1 (F16_DIST_FORCE_GROUP=1; by
 default one rank forms no group at all), in a fresh child process, so that the first RCCL execution of dist.py is not the
 driver's 8-GPU run: the all-gather of trajectory shards in both layouts and as point-to-point batch, the scalar reductions on
-device tensors, the bounded timeout, and `bench.py --gpus 1 --force-group` printing its `allgather` block and the RCCL version."""
+device tensors, the bounded timeout, and `bench.py --gpus 1 --force-group --full` printing its `allgather` block and the RCCL version."""
 import json
 import os
 import subprocess
@@ -72,7 +72,7 @@ def test_world_size_1_nccl_group_runs_every_collective_of_dist_py():
 
 def test_bench_gpus_1_with_a_forced_group_prints_the_allgather_block():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-group",
-                        "--no-cpu", "--no-mpc", "--no-large", "--no-config5"], env=_env(), capture_output=True, text=True,
+                        "--full", "--no-cpu", "--no-mpc", "--no-large", "--no-config5"], env=_env(), capture_output=True, text=True,
                        timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

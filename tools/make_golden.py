@@ -598,8 +598,38 @@ def g14_dynamic_lqr(steps=150):
     print("g14_dynamic_lqr.npz", os.path.getsize(os.path.join(OUT, "g14_dynamic_lqr.npz")))
 
 
+def g2r_ref_rebuilt(n=400):
+    """G2r: the reference's C compiled from its sources by oracle/Makefile (oracle/_ref/nlplant_xcg{25,35}.so, `make -C oracle ref`)
+    on the first `n` hifi inputs of G2, both xcg builds -- pins the restatement against the source path, not only the prebuilt .so
+    G2 came from.  Taken in a process where `_CLr` reads ~0, so every output column is comparable."""
+    os.chdir(REF)
+    so = {k: os.path.join(REPO, "oracle", "_ref", f"nlplant_xcg{k}.so") for k in (25, 35)}
+    for p in so.values():
+        if not os.path.exists(p):
+            raise SystemExit(f"{p} missing: run `make -C oracle ref` first")
+    libs = {k: ctypes.CDLL(p) for k, p in so.items()}
+    for k in libs:
+        if not clr_reads_zero(libs[k]):
+            raise SystemExit("this process's _CLr does not read ~0 (uninitialised heap): run the script again")
+    xu = np.load(os.path.join(OUT, "g2_nlplant.npz"))["xu_hifi"][:n]
+    g = {"n": np.array(n)}
+    for k, L in libs.items():
+        out = np.zeros((n, 18))
+        for i, x in enumerate(xu):
+            x = np.ascontiguousarray(x)
+            L.Nlplant(dptr(x), dptr(out[i]), ctypes.c_int(1))
+        g[f"xdot_hifi_xcg{k}"] = out
+    for k in libs:
+        if not clr_reads_zero(libs[k]):
+            raise SystemExit("_CLr stopped reading ~0 during the run: run the script again")
+    np.savez_compressed(os.path.join(OUT, "g2r_ref_rebuilt.npz"), **g)
+    print("g2r_ref_rebuilt.npz", os.path.getsize(os.path.join(OUT, "g2r_ref_rebuilt.npz")))
+
+
 if __name__ == "__main__":
-    if "--g14" in sys.argv:
+    if "--g2r" in sys.argv:
+        g2r_ref_rebuilt()
+    elif "--g14" in sys.argv:
         g14_dynamic_lqr()
     elif "--g13" in sys.argv:
         g13_round5()
