@@ -3,6 +3,7 @@
 //   k_linearise   env.py:294-342 (forward differences of _calc_xdot_na, eps 1e-5)          f16_linearise_batch
 //   k_c2d         scipy.signal.cont2discrete zoh = expm([[A,B],[0,0]] dt) (env.py:50,351)  f16_c2d_batch
 //   k_lqr         utils.py:219-245 dlqr (DARE + gain), Q = Cd'Cd, R = I (env.py:353-356)   f16_lqr_batch
+//   k_rollout_lqr_relin  test_env.py:625-687: the four above + step, per step, T steps       f16_rollout_lqr_relin
 //   k_mpc         utils.py:21-167 setup_OSQP + the OSQP solve of env.py:420-424            f16_mpc_batch
 //
 // Mapping.  k_linearise: one lane per (aircraft, perturbed column), tables in LDS as in the dynamics kernels.
@@ -419,6 +420,135 @@ __global__ __launch_bounds__(64, 3) void k_lqr(LqrArgs a) {
     for (int e = lane_id(); e < 27; e += F16_WAVE) a.K[e * a.ld + b] = -K[e];   // K = -dlqr(...) (env.py:356)
     if (a.Pare) store_soa(a.Pare, X, 81, a.ld, b);
     if (a.status && it >= 60 && lane_id() == 0) a.status[b] |= F16_ST_QP_MAXITER;
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------ per-step re-linearised LQR loop
+// test_env.py:625-687 `test_LQR_dynamic_nl` (and env.py's own law re-derived every step) as ONE launch: per step linearise at the
+// current (x, u) -> ZOH -> dlqr -> u[1:4] = -K (x9 - x_ref) + u0 -> step.  One wavefront per aircraft for all nsteps, the aircraft
+// independent (no hand-off between waves).  Lanes 0..11 evaluate the perturbed columns and lane 12 the base point through the
+// out-of-line xdot_na_exact, the chain runs on the same LDS-resident parts k_c2d / k_lqr use (c2d_wave, dare_sda_wave,
+// lqr_gain_wave), lane 0 takes the Euler step through euler_step_exact (the F16_FLAG_ONE_LANE step).  The state, the command and
+// the gain live in LDS between steps.
+struct RelinArgs {
+  const double *tab, *lofi, *xref, *u0;
+  double *x, *u, *traj, *utraj, *Ktraj;
+  int32_t *status;
+  long B, ld;
+  int nsteps, every;
+  unsigned track;
+  double eps, dt, xcg;
+  int fi;
+  unsigned flags;
+  MpcProb pb;              // Q, R (custom_q / custom_r); the bounds are not read
+};
+constexpr int C2D_SCRATCH = 81 + 2 + 3 * (9 * 12 + 2);                 // c2d_wave<9, 3>: X | T | Tn | EF (Bump-rounded)
+constexpr int RELIN_SCRATCH = C2D_SCRATCH > DARE_SCRATCH + 90 ? C2D_SCRATCH : DARE_SCRATCH + 90;
+
+// Two waves per SIMD: the out-of-line plant evaluation alone takes 248 registers, so one wave per SIMD is what the kernel gets without
+// a bound (256 VGPRs + 136 AGPRs); with the bound the DARE spills about a hundred registers to scratch.  A/B builds:
+// -DF16_RELIN_MIN_WAVES=1 (DESIGN.md "Per-step re-linearised LQR loop" has the measured comparison).
+#ifndef F16_RELIN_MIN_WAVES
+#define F16_RELIN_MIN_WAVES 2
+#endif
+__global__ __launch_bounds__(64, F16_RELIN_MIN_WAVES) void k_rollout_lqr_relin(RelinArgs a) {
+  __shared__ double smem[18 + 4 + 10 + 4 + 13 * 9 + 1 + 82 + 28 + 82 + 28 + 82 + 82 + 28 + 10 + RELIN_SCRATCH];
+  __shared__ int stl;
+  Bump al{smem};
+  double *xs = al.take(18), *us = al.take(4), *xr = al.take(9), *u0 = al.take(3);
+  double *F = al.take(13 * 9), *A = al.take(81), *Bm = al.take(27), *Ad = al.take(81), *Bd = al.take(27), *Q = al.take(81);
+  double *X = al.take(81), *K = al.take(27), *cd = al.take(9), *scr = al.take(RELIN_SCRATCH);
+  const int l = lane_id();
+  // column -> full-state index (k_linearise): mpc_x_idx = [3,4,7,8,9,10,11,17,16], inputs -> [13,14,15]; lane 12: the base point
+  const int idx = l == 0 ? 3 : l == 1 ? 4 : l == 2 ? 7 : l == 3 ? 8 : l == 4 ? 9 : l == 5 ? 10 : l == 6 ? 11
+                : l == 7 ? 17 : l == 8 ? 16 : l < 12 ? 13 + (l - 9) : -1;
+  for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+    if (l < 18) xs[l] = a.x[l * a.ld + b];
+    if (l < 4) us[l] = a.u[l * a.ld + b];
+    if (l < 9) xr[l] = ((a.track >> l) & 1u) ? a.xref[l * a.ld + b] : 0.0;
+    if (l < 3) u0[l] = a.u0 ? a.u0[l * a.ld + b] : 0.0;
+    if (l < 27) K[l] = 0.0;
+    if (l == 0) stl = 0;
+    __syncthreads();
+    int st = a.status ? a.status[b] : 0;
+    double *tr = a.traj ? a.traj + b : nullptr, *tu = a.utraj ? a.utraj + b : nullptr, *tk = a.Ktraj ? a.Ktraj + b : nullptr;
+    int until = a.every;
+    for (int t = 0; t < a.nsteps; ++t) {
+      if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(xs)) st |= ST_ENVELOPE;      // env.py:117-124
+      if (!(st & ST_ENVELOPE)) {
+        // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps)
+        if (l < 13) {
+          double sv[18], f[9];
+#pragma unroll
+          for (int k = 0; k < 18; ++k) sv[k] = xs[k];
+          sv[13] = us[1]; sv[14] = us[2]; sv[15] = us[3];      // env.py:175-177
+          double base = 0.0, pert = 0.0;
+#pragma unroll
+          for (int k = 0; k < 18; ++k)
+            if (k == idx) { base = sv[k]; pert = sv[k] + a.eps; sv[k] = pert; }
+          int sl = 0;      // (the grid bits of the perturbed points are not the aircraft's: _calc_LQR_gain does not keep them)
+          xdot_na_exact(a.tab, a.lofi, sv, f, a.xcg, a.fi, a.flags, &sl);
+#pragma unroll
+          for (int r = 0; r < 9; ++r) F[l * 9 + r] = f[r];
+          if (l < 9) cd[l] = (pert - base) / a.eps;
+        }
+        __syncthreads();
+        for (int e = l; e < 108; e += F16_WAVE) {
+          if (e < 81) { const int r = e / 9, c = e - r * 9; A[e] = (F[c * 9 + r] - F[12 * 9 + r]) / a.eps; }
+          else { const int e2 = e - 81, r = e2 / 3, c = e2 - r * 3; Bm[e2] = (F[(9 + c) * 9 + r] - F[12 * 9 + r]) / a.eps; }
+        }
+        for (int e = l; e < 81; e += F16_WAVE) {
+          const int i = e / 9, j = e - i * 9;
+          Q[e] = a.pb.custom_q ? a.pb.Q[e] : (i == j ? cd[i] * cd[i] : 0.0);              // Q = C'C (env.py:353), C diagonal
+        }
+        __syncthreads();
+        c2d_wave<9, 3>(A, Bm, a.dt, Ad, Bd, scr);                                         // f16_c2d_batch
+        const int it = dare_sda_wave(Ad, Bd, Q, X, scr, a.pb.custom_r ? a.pb.Rinv : nullptr);      // f16_lqr_batch_w
+        lqr_gain_wave(Ad, Bd, X, K, scr, a.pb.custom_r ? a.pb.R : nullptr);
+        if (it >= 60) st |= F16_ST_QP_MAXITER;
+        // u[1:4] = -K (x9 - x_ref) + u0, x_ref = x9 outside the tracked entries (f16_rollout_lqr_linear's rule); thrust held
+        if (l < 3) {
+          double s = 0.0;
+#pragma unroll
+          for (int j = 0; j < 9; ++j) {
+            const int k = j == 0 ? 3 : j == 1 ? 4 : j == 2 ? 7 : j == 3 ? 8 : j == 4 ? 9 : j == 5 ? 10 : j == 6 ? 11 : j == 7 ? 17 : 16;
+            const double x9 = xs[k];
+            s += K[l * 9 + j] * (x9 - (((a.track >> j) & 1u) ? xr[j] : x9));
+          }
+          us[1 + l] = -s + u0[l];
+        }
+        __syncthreads();
+        if (l == 0) {
+          double x[18], u[4];
+#pragma unroll
+          for (int k = 0; k < 18; ++k) x[k] = xs[k];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) u[k] = us[k];
+          int ss = 0;
+          euler_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &ss);
+#pragma unroll
+          for (int k = 0; k < 18; ++k) xs[k] = x[k];
+          stl = ss;
+        }
+        __syncthreads();
+        st |= stl;
+      }
+      if (--until == 0) {
+        until = a.every;
+        if (tr) { if (l < 18) __builtin_nontemporal_store(xs[l], tr + l * a.ld); tr += 18 * a.ld; }
+        if (tu) { if (l < 3) __builtin_nontemporal_store(us[1 + l], tu + l * a.ld); tu += 3 * a.ld; }
+        if (tk) { if (l < 27) __builtin_nontemporal_store(-K[l], tk + l * a.ld); tk += 27 * a.ld; }      // K = -dlqr (env.py:356)
+      }
+    }
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) finite = finite && isfinite(xs[k]);
+    if (!finite) st |= ST_NONFINITE;
+    if (st & ST_ENVELOPE) st |= envelope_state_bits(xs);
+    if (l < 18) a.x[l * a.ld + b] = xs[l];
+    if (l < 4) a.u[l * a.ld + b] = us[l];
+    if (a.status && l == 0) a.status[b] = st;
     __syncthreads();
   }
 }
@@ -947,11 +1077,8 @@ extern "C" int f16_c2d_full_batch(f16_ctx *ctx, const double *Ac, const double *
 // rows the reference bounds (alpha, beta, p, q, r, lf2: parameters.py:59-95) and leave phi, theta, lf1 out of the iteration, so
 // THAT pattern is fixed: a finite bound on one of the three, or no bound at all on one of the six, is refused (the QP-build
 // entry f16_mpc_qp_debug_w takes any pattern).
-int f16::mpc_fill_prob(MpcProb *p, const f16_mpc_weights *w) {
-  mpc_default_prob(p);
-  if (!w) return F16_OK;
-  auto inf = [](double v) { return !(fabs(v) < 1e20); };
-  auto clip = [](double v) { return v > 1e30 ? 1e30 : (v < -1e30 ? -1e30 : v); };
+// Q and R alone (utils.py:219 `dlqr(A, B, Q, R)`): validated and copied into p, which holds env.py's constants on entry.
+static int fill_prob_qr(MpcProb *p, const f16_mpc_weights *w) {
   if (!w->q_from_cd) {
     for (int i = 0; i < 9; ++i)
       for (int j = 0; j < 9; ++j) {
@@ -981,6 +1108,15 @@ int f16::mpc_fill_prob(MpcProb *p, const f16_mpc_weights *w) {
       p->custom_r = 1;
     }
   }
+  return F16_OK;
+}
+
+int f16::mpc_fill_prob(MpcProb *p, const f16_mpc_weights *w) {
+  mpc_default_prob(p);
+  if (!w) return F16_OK;
+  auto inf = [](double v) { return !(fabs(v) < 1e20); };
+  auto clip = [](double v) { return v > 1e30 ? 1e30 : (v < -1e30 ? -1e30 : v); };
+  if (int rc = fill_prob_qr(p, w)) return rc;
   static const int srow[6] = {2, 3, 4, 5, 6, 8}, free_rows[3] = {0, 1, 7};
   for (int k = 0; k < 3; ++k)
     if (!inf(w->x_lb[free_rows[k]]) || !inf(w->x_ub[free_rows[k]]))
@@ -1022,6 +1158,28 @@ extern "C" int f16_lqr_batch_w(f16_ctx *ctx, const double *Ad, const double *Bd,
 extern "C" int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, const double *Cd, double *K, double *Pare,
                              int32_t *status, long B, long ld, void *stream) {
   return f16_lqr_batch_w(ctx, Ad, Bd, Cd, nullptr, K, Pare, status, B, ld, stream);
+}
+
+extern "C" int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
+                                     const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
+                                     long B, long ld, int nsteps, int traj_every, unsigned track_mask, double eps, double dt,
+                                     double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (!ctx || !x || !u || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_rollout_lqr_relin");
+  if (nsteps < 1 || traj_every < 1 || nsteps % traj_every != 0)
+    return set_error(F16_EINVAL, "f16_rollout_lqr_relin: nsteps must be >= 1 and a multiple of traj_every >= 1");
+  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_lqr_relin: eps must be > 0");
+  if ((track_mask & 0x1FFu) && !x_ref) return set_error(F16_EINVAL, "f16_rollout_lqr_relin: x_ref is NULL but track_mask selects entries");
+  RelinArgs a{};
+  mpc_default_prob(&a.pb);
+  if (h_w)
+    if (int rc = fill_prob_qr(&a.pb, h_w)) return rc;
+  if (B == 0) return F16_OK;
+  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.xref = x_ref; a.u0 = u0;
+  a.x = x; a.u = u; a.traj = traj; a.utraj = u_traj; a.Ktraj = K_traj; a.status = status;
+  a.B = B; a.ld = ld; a.nsteps = nsteps; a.every = traj_every; a.track = track_mask & 0x1FFu;
+  a.eps = eps; a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  hipLaunchKernelGGL(k_rollout_lqr_relin, dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
+  return hip_check(hipGetLastError(), "f16_rollout_lqr_relin launch");
 }
 
 extern "C" void f16_qp_default_settings(f16_qp_settings *s) {

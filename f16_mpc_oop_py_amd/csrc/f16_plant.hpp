@@ -934,4 +934,20 @@ static __device__ __noinline__ void euler_step_exact(const double *tab, const do
   *stio |= st;
 }
 
+// env.py:152-193 _calc_xdot_na at ONE point (sv[18]: the full state with the three MPC inputs already in sv[13..15]) -> xdot9[9],
+// compiled out of line for the same reason as euler_step_exact: the per-step re-linearised LQR loop (f16_control.hip:
+// k_rollout_lqr_relin) evaluates every column of its forward differences through this one instruction sequence.  tab: the fp64
+// table image through a generic pointer (global memory); *stio |= the grid bits.
+static __device__ __noinline__ void xdot_na_exact(const double *tab, const double *lofi, const double *sv, double *xdot9, double xcg,
+                                                  int fi, unsigned flags, int *stio) {
+  double s[18], f[9];
+#pragma unroll
+  for (int k = 0; k < 18; ++k) s[k] = sv[k];
+  int st = 0;
+  calc_xdot_na(tab, lofi, s, f, xcg, fi, flags, st);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) xdot9[k] = f[k];
+  *stio |= st;
+}
+
 }  // namespace f16

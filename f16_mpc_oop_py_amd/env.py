@@ -336,7 +336,8 @@ class F16Batch:
                 dem[k] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
         return dem
 
-    def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False):
+    def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
+                    R=None):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -345,7 +346,22 @@ class F16Batch:
         action, as in the reference.  traj_every=k returns the states after every k-th step, [nsteps//k, 18, B].
         linear=True (test_env_mk2.py:46-62, what main.py:35 runs): the same law on the frozen reduced model,
         `x = ssr.Ad @ x + ssr.Bd @ u` from x = x._get_mpc_x(); x.values / u.values are not touched (the reference's loop works on
-        locals).  Returns (x_storage [nsteps//k, 9, B], u_storage [nsteps//k, 3, B]) with k = traj_every or 1."""
+        locals).  Returns (x_storage [nsteps//k, 9, B], u_storage [nsteps//k, 3, B]) with k = traj_every or 1.
+        relinearise=True: the same law with K re-derived at EVERY step, `_calc_LQR_gain(Q, R)` at the current (x, u) (Q, R: the
+        weights of utils.py:219 dlqr, default env.py's Cd'Cd and I), in one launch (rollout_LQR_relin with track = (4, 5, 6));
+        K must be None.  Returns the states as with linear=False."""
+        if relinearise:
+            if K is not None or linear:
+                raise ValueError("relinearise=True derives K at every step on the nonlinear model (K and linear are not taken)")
+            xref = torch.zeros((9, self.B), dtype=torch.float64, device=self.device)
+            xref[4:7] = self._demands(p_dem, q_dem, r_dem)                    # env.py:365-367
+            u03 = self._u_init[1:4] if u0 is None else self._soa(u0, 4)[1:4]
+            if u0 is not None:
+                self._u[0] = self._soa(u0, 4)[0]
+            k = int(traj_every or nsteps)
+            traj = self._rollout_relin(nsteps, xref, 0x70, u03.contiguous(), _lib.make_weights(Q=Q, R=R), 1e-5, k,
+                                       bool(traj_every), False, False)[0]
+            return traj
         if K is None:
             K = self._calc_LQR_gain()
         Ks = torch.as_tensor(K, device=self.device, dtype=torch.float64).reshape(self.B, 27).t().contiguous()
@@ -371,6 +387,35 @@ class F16Batch:
                                              _vp(self.status), self.B, self.B, int(nsteps), int(traj_every or 1), self.dt,
                                              self.xcg, self.fi_flag, self.flags, self._stream))
         return traj
+
+    def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None):
+        """The per-step re-linearised LQR loop (test_env.py:625-687 `test_LQR_dynamic_nl`) in ONE launch (C-ABI
+        f16_rollout_lqr_relin): per step linearise at the current (x, u[1:4]) with eps -> ZOH -> Kd = dlqr(Ad, Bd, Q, R) ->
+        u[1:4] = -Kd (x9 - x_ref) + u0 -> step(u.values), the thrust command held.  x_ref [B,9] or [9] defaults to the current x9;
+        track (indices into x9) selects the entries of x_ref that are held fixed, the others follow the current x9 (None: all nine);
+        u0 [B,3] or None (= 0); Q [9,9] / R [3,3] default to env.py's Cd'Cd and I.  x.values, u.values (the last command) and
+        status are updated in place.  Samples every k-th step, k = traj_every or gains_every or 1 (the two must agree when both
+        are given).  Returns (traj [n//k, 18, B], u_traj [n//k, 3, B], K_traj [n//k, B, 3, 9] = -dlqr or None without gains_every)."""
+        if traj_every and gains_every and int(traj_every) != int(gains_every):
+            raise ValueError("the states, commands and gains are sampled at one interval: traj_every must equal gains_every")
+        k = int(traj_every or gains_every or 1)
+        xr = self._x[P.mpc_x_idx].clone() if x_ref is None else self._soa(x_ref, 9)
+        mask = 0x1FF if track is None else sum(1 << int(j) for j in track)
+        u03 = None if u0 is None else self._soa(u0, 3)
+        return self._rollout_relin(nsteps, xr, mask, u03, _lib.make_weights(Q=Q, R=R), eps, k, True, True, gains_every is not None)
+
+    def _rollout_relin(self, nsteps, xref, mask, u03, w, eps, k, want_x, want_u, want_k):
+        """f16_rollout_lqr_relin on the resident state: xref [9,B], u03 [3,B] or None (state-major, contiguous)."""
+        nsteps, k = int(nsteps), int(k)
+        if k < 1 or nsteps % k:
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of the sampling interval ({k})")
+        mk = lambda want, rows: torch.empty((nsteps // k, rows, self.B), dtype=torch.float64, device=self.device) if want else None
+        traj, u_traj, K_traj = mk(want_x, 18), mk(want_u, 3), mk(want_k, 27)
+        self._check(self.lib.f16_rollout_lqr_relin(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
+                                                   ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj),
+                                                   _vp(self.status), self.B, self.B, nsteps, k, int(mask), float(eps), self.dt,
+                                                   self.xcg, self.fi_flag, self.flags, self._stream))
+        return traj, u_traj, None if K_traj is None else K_traj.permute(0, 2, 1).reshape(nsteps // k, self.B, 3, 9)
 
     def rollout_linear(self, x9, Ad, Bd, K, x_ref, u0, nsteps, track=None, traj_every=None, state_major=False):
         """`u = -K (x_ref - x) + u0; x = Ad x + Bd u` for nsteps on per-aircraft 9-state / 3-input linear models (C-ABI

@@ -246,6 +246,7 @@ def load():
         L.f16_mpc_default_weights.argtypes = [wp]
         L.f16_mpc_default_weights.restype = None
         L.f16_lqr_batch_w.argtypes = [vp, vp, vp, vp, wp, vp, vp, vp, l, l, vp]
+        L.f16_rollout_lqr_relin.argtypes = [vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, i, u, d, d, d, i, u, vp]
         L.f16_mpc_batch_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
         L.f16_mpc_plan_create_w.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, wp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
         L.f16_mpc_plan_solve_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]

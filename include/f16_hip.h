@@ -221,6 +221,34 @@ typedef struct f16_mpc_weights {
 void f16_mpc_default_weights(f16_mpc_weights *w);      /* env.py's constants */
 int f16_lqr_batch_w(f16_ctx *ctx, const double *Ad, const double *Bd, const double *Cd, const f16_mpc_weights *h_w, double *K,
                     double *Pare, int32_t *status, long B, long ld, void *stream);        /* utils.py:219: Q, R of h_w */
+/* The PER-STEP RE-LINEARISED LQR loop (test_env.py:625-687 `test_LQR_dynamic_nl`) as ONE launch: per step, for every aircraft that
+ * is not frozen,
+ *     A, B, C = linearise_na(x, u[1:4], eps)    (f16_linearise_batch: C = diag((x + eps - x) / eps))
+ *     Ad, Bd  = zoh(A, B, dt)                    (f16_c2d_batch)
+ *     Kd      = dlqr(Ad, Bd, Q, R)               (f16_lqr_batch_w; h_w supplies Q and R only -- NULL or q_from_cd = 1: Q = Cd'Cd,
+ *                                                 and R = I unless h_w gives another; no other field of h_w is read)
+ *     u[1+i]  = -Kd (x9 - x_ref_eff) + u0[i],   x_ref_eff[j] = x_ref[j] where bit j of track_mask is set, else the current x9[j]
+ *     step(u)                                    (env.py:105-130 through the F16_FLAG_ONE_LANE step; thrust u[0] held)
+ * with the envelope rule and status bits of f16_rollout(F16_FLAG_ONE_LANE): F16_ST_ENVELOPE freezes (F16_FLAG_NO_ENVELOPE skips the
+ * test), F16_ST_NONFINITE and F16_ST_ENV_STATE are set at the end; a DARE that has not converged within its 60 doublings sets
+ * F16_ST_QP_MAXITER (as f16_lqr_batch does) and the step goes on with that gain.  The grid bits of the linearisation's perturbed
+ * points are not kept (_calc_LQR_gain does not keep them either); those of the steps are.
+ * The two reference loops:  test_LQR_dynamic_nl: x_ref = the initial x9, track_mask = 0x1FF, Q = I, R = 1e4 I, u0 = NULL;
+ *   env.py's law re-derived every step (_calc_LQR_gain() then _calc_LQR_action(p, q, r, K, x9, u.initial_condition[1:])):
+ *   track_mask = 0x70, x_ref[4..6] = the demands, default weights, u0 = u.initial_condition[1:].
+ * x[18][ld] and u[4][ld] (u.values) in place: u ends up holding the last command.  x_ref[9][ld] (may be NULL when track_mask
+ * selects nothing; untracked entries are not read), u0[3][ld] or NULL (= 0).  status[ld] (may be NULL) is read and written: an
+ * aircraft frozen on entry stays frozen.  traj [nsteps/traj_every][18][ld], u_traj [..][3][ld], K_traj [..][27][ld] (each may be
+ * NULL) receive, every traj_every-th step, the state after the step, the command of the step and the gain used, K = -dlqr (the sign
+ * of f16_lqr_batch and _calc_LQR_gain, 3 x 9 row-major); a frozen step stores the held command and the last gain (zeros if none
+ * was computed in this launch).  F16_EINVAL: NULL x / u, ld < B, nsteps < 1, traj_every < 1, nsteps % traj_every != 0, eps <= 0,
+ * a track_mask without x_ref, or Q / R not as f16_lqr_batch_w takes them.
+ * One wavefront per aircraft for all nsteps (the matrices in LDS); results do not depend on B or on how nsteps is split over
+ * calls. */
+int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
+                          const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj,
+                          int32_t *status, long B, long ld, int nsteps, int traj_every, unsigned track_mask,
+                          double eps, double dt, double xcg, int fi_flag, unsigned flags, void *stream);
 
 typedef struct f16_qp_settings {
   double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf;
