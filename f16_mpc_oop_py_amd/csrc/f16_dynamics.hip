@@ -466,9 +466,12 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
 // fills all 256 CUs (the 4-wave kernel above occupies 64) and every role below runs sub-lane-parallel wherever the
 // arithmetic is uniform (f16_plant_quad.hpp): a step costs a CU far fewer wave-instructions.  Lane l = 4 a + s.
 //   wave 0  --        Cx, Cz, Cm totals on sub-lanes 0,1,2 (3-D / 2-D / 1-D longitudinal tables)
+//                                                                           | sin/cos of the next step's psi
 //   wave 1  x[9..11]  Cy, Cn, Cl totals on sub-lanes 0,1,2                                   | moment equations, Euler
-//   wave 2  x[0..8]   sin/cos of phi, theta, psi, alpha on sub-lanes 0..3, beta; kinematic + navigation equations
+//   wave 2  x[0..8]   sin/cos of phi, theta, beta, alpha on sub-lanes 0..3; kinematic + navigation equations
 //                                                                                            | force equations, Euler
+// Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached).  GROUPS = 2 keeps
+// the full lookup on every step and psi on wave 2 (sub-lane 2, beta in a second round): the cache's registers spill there.
 //   wave 3  x[12..17] atmosphere; the four actuators on sub-lanes 0..3; flap model (Euler)
 // Owned states are replicated over the sub-lanes of their wave; two barriers per step as in k_rollout_4w.
 // GROUPS = 2 (4096 < B <= 8192): two independent 16-aircraft groups per workgroup share the LDS table image, one role
@@ -476,9 +479,11 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
 template <int GROUPS, bool LQR = false>
 __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
   constexpr int NA = 16 * GROUPS;
+  constexpr bool G1 = GROUPS == 1;     // cell re-use and psi on wave 0: one group only (at GROUPS = 2 the registers spill)
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   __shared__ double xs[18][NA], xt[11][NA];                // published state; Cx Cz Cm | Cy Cn Cl static | qbar ps | Cy Cn Cl damping
   __shared__ int xenv[3][NA], xst[2][NA];
+  __shared__ double xpsi[3][NA];                           // psi after the step (wave 2 -> wave 0), its sin / cos (wave 0 -> wave 2)
   {
     const double2 *src = reinterpret_cast<const double2 *>(a.tab);
     double2 *dst = reinterpret_cast<double2 *>(tab);
@@ -505,6 +510,12 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
     int st = a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr;            // next sample (written by wave 2 from the published state)
     int until_store = a.traj_every;
+    QuadCell qc = quad_cell_none();                        // waves 0 / 1: cells of the last full lookup (none at launch start)
+    if (G1 && wave == 0 && s == 0) {                       // sin / cos of the first step's psi (the loop's first barrier publishes it)
+      double sp, cp;
+      F16_SINCOS(x[5], &sp, &cp);
+      xpsi[1][ac] = sp; xpsi[2][ac] = cp;
+    }
 #ifdef F16_EXP_STAMPQ
     unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
 #define QSTAMP(acc) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
@@ -564,12 +575,12 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
       if (wave == 0) {
         int sa_ = 0;
         double latd;
-        const double tot = quad_long((const double *)tab, xa, s, a.xcg, a.flags, latd, sa_);
+        const double tot = quad_long<G1>((const double *)tab, xa, s, a.xcg, a.flags, qc, latd, sa_);
         if (s < 3) { xt[s][ac] = tot; xt[8 + s][ac] = latd; }
         xst[0][ac] = sa_;
       } else if (wave == 1) {
         int sa_ = 0;
-        const double tot = quad_lat((const double *)tab, xa, s, sa_);
+        const double tot = quad_lat<G1>((const double *)tab, xa, s, a.flags, qc, sa_);
         if (s < 3) xt[3 + s][ac] = tot;
         xst[1][ac] = sa_;
         {   // the rate-product terms of the moment equations (C/nlplant.c:413-436, Heng = 0) do not need the totals: first half
@@ -581,14 +592,17 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
           mo2 = ((Jx * (Jx - Jy) + Jxz * Jxz) * P * Q - Jxz * (Jx - Jy + Jz) * Q * R) * rden;
         }
       } else if (wave == 2) {
-        // sin / cos of phi, theta, psi, alpha: one angle per sub-lane, then shared across the quad
-        const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? xa[5] : xa[7]));
-        double sn, cs, sb;
+        // sin / cos of phi, theta, beta, alpha: one angle per sub-lane, then shared across the quad; psi's from wave 0
+        // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
+        const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
+        double sn, cs, sb, s_psi, c_psi;
         F16_SINCOS(ang, &sn, &cs);
-        F16_SINCOS(xa[8], &sb, &cb);
+        // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
+        //  changes x[1] in the last place)
+        if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
         s_phi = quad_bcast<0>(sn); c_phi = quad_bcast<0>(cs);
         s_t = quad_bcast<1>(sn); c_t = quad_bcast<1>(cs);
-        const double s_psi = quad_bcast<2>(sn), c_psi = quad_bcast<2>(cs);
+        if constexpr (G1) { s_psi = xpsi[1][ac]; c_psi = xpsi[2][ac]; } else { s_psi = quad_bcast<2>(sn); c_psi = quad_bcast<2>(cs); }
         const double sal = quad_bcast<3>(sn), cal = quad_bcast<3>(cs);
         vtc = xa[6];
         if (vtc <= 0.01) vtc = 0.01;
@@ -625,6 +639,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) x[k] += xd[k] * a.dt;   // env.py:126 (navigation / kinematic states)
           }
+          if (G1 && s == 0) xpsi[0][ac] = x[5];                  // wave 0 evaluates its sin / cos in the second half
         }
       } else {
         double vt = xa[6];
@@ -688,6 +703,10 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
           x[10] += (mo1 + F16_DIVC(M_tot, Jy)) * a.dt;
           x[11] += (mo2 + (Jx * N_tot + Jxz * L_tot) * rden) * a.dt;
         }
+      } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
+        double sp, cp;
+        F16_SINCOS(xpsi[0][ac], &sp, &cp);
+        xpsi[1][ac] = sp; xpsi[2][ac] = cp;
       }
     }
 #ifdef F16_EXP_STAMPQ

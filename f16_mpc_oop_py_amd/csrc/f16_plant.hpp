@@ -25,7 +25,7 @@
 namespace f16 {
 
 constexpr int ST_ALPHA1 = 1, ST_ALPHA2 = 2, ST_BETA = 4, ST_EL = 8, ST_ENVELOPE = 16, ST_NONFINITE = 32;
-constexpr unsigned FLAG_FIX_CLR = 1u, FLAG_NO_ENVELOPE = 2u;
+constexpr unsigned FLAG_FIX_CLR = 1u, FLAG_NO_ENVELOPE = 2u, FLAG_NO_CELL_CACHE = 16u;
 
 #define F16_DEV __device__ __forceinline__
 

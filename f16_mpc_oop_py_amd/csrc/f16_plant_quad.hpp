@@ -51,6 +51,32 @@ F16_DEV QuadBr quad_br_cells(const BrRaw &r, int nX, double vX) {
   q.offa = quad_bcast_i<0>(o) != 0; q.offb = quad_bcast_i<1>(o) != 0; q.offd = quad_bcast_i<2>(o) != 0;
   return q;
 }
+
+// Cell re-use across steps.  At dt = 1 ms an axis value almost never leaves its cell, so each lane keeps the cell of its
+// own axis ([x0, x1)) and the quad's three cell indices from the last full lookup.  If every lane of the wave is still
+// inside its cell (x0 <= v < x1 -- NaN, off-grid values and a value on the last node all fail it) the wave skips the
+// breakpoint reads, the fix-up and the broadcasts; br_axis then sees the same v, x0, x1 and lambda has the same bits.  The
+// cell is unique for an on-grid v < x1, so the full path could not have picked another one.  x0 = NaN: no cell yet.
+struct QuadCell { int ja, jb, jd; double x0, x1; };
+F16_DEV QuadCell quad_cell_none() { QuadCell c; c.ja = c.jb = c.jd = 0; c.x0 = c.x1 = __builtin_nan(""); return c; }
+template <bool USE_D2, bool CACHE, typename TP>
+F16_DEV QuadBr quad_br_cached(TP T, double alpha, double beta, double el, int s, unsigned flags, QuadCell &cc) {
+  const double v = s == 0 ? alpha : (s == 1 ? beta : el);
+  const bool in = cc.x0 <= v && v < cc.x1;
+  QuadBr q;
+  if (CACHE && !(flags & FLAG_NO_CELL_CACHE) && __builtin_amdgcn_ballot_w64(!in) == 0) {   // wave-uniform branch
+    q.c.j = 0; q.c.v = v; q.c.x0 = cc.x0; q.c.x1 = cc.x1;                          // (br_axis's j is not used by the quads)
+    q.ja = cc.ja; q.jb = cc.jb; q.jd = cc.jd;
+    q.offa = q.offb = q.offd = false;
+  } else {
+    int nX; double vX;
+    const BrRaw rx = quad_br_load<USE_D2>(T, alpha, beta, el, s, nX, vX);
+    F16_PHASE();
+    q = quad_br_cells(rx, nX, vX);
+    if (CACHE) { cc.ja = q.ja; cc.jb = q.jb; cc.jd = q.jd; cc.x0 = q.c.x0; cc.x1 = q.c.x1; }
+  }
+  return q;
+}
 F16_DEV void quad_br_axes(const QuadBr &q, Axis &a, Axis &b, Axis &d) {
   const Axis own = br_axis(q.c);                                  // one division per lane
   a.j = q.ja; a.l = quad_bcast<0>(own.l); a.m = quad_bcast<0>(own.m);
@@ -91,21 +117,18 @@ __device__ unsigned long long g_qstamp[8];
 #else
 #define Q2STAMP(i)
 #endif
-template <typename TP>
-F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned flags, double &latd, int &status) {
+template <bool CACHE, typename TP>
+F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned flags, QuadCell &cc, double &latd, int &status) {
 #ifdef F16_EXP_STAMPQ2
   unsigned long long tq_ = __builtin_amdgcn_s_memtime();
 #endif
   const QuadIn in = quad_inputs(xu);
   Q2STAMP(0)
   const int k = s < 2 ? s : 2;
-  // (1) breakpoints: one axis per sub-lane
-  int nX; double vX;
-  const BrRaw rx = quad_br_load<false>(T, in.alpha, in.beta, in.el, s, nX, vX);
-  const double a45 = T[OFF_BP_A1 + N_A2 - 1];
-  F16_PHASE();
+  // (1) breakpoints and cells: one axis per sub-lane (re-used from the last step while every lane stays in its cell)
+  const QuadBr qb = quad_br_cached<false, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc);
   Q2STAMP(1)
-  const QuadBr qb = quad_br_cells(rx, nX, vX);
+  const double a45 = T[OFF_BP_A1 + N_A2 - 1];
   if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
   if (qb.offb) status |= ST_BETA;
   if (qb.offd) status |= ST_EL;
@@ -154,16 +177,13 @@ F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned fla
 // Static part (3-D / 2-D tables) of Cy_tot / Cn_tot / Cl_tot on sub-lanes 0 / 1 / 2 (C/nlplant.c:353-377, hifi_C,
 // hifi_C_lef, hifi_rudder, hifi_ailerons); the damping part comes from quad_long, the cg coupling of Cn (:367) is
 // applied by the consumer once both parts of Cy_tot are known.
-template <typename TP>
-F16_DEV double quad_lat(TP T, const double *xu, int s, int &status) {
+template <bool CACHE, typename TP>
+F16_DEV double quad_lat(TP T, const double *xu, int s, unsigned flags, QuadCell &cc, int &status) {
   const QuadIn in = quad_inputs(xu);
   const int k = s < 2 ? s : 2;
-  // (1) breakpoints: one axis per sub-lane
-  int nX; double vX;
-  const BrRaw rx = quad_br_load<true>(T, in.alpha, in.beta, in.el, s, nX, vX);
+  // (1) breakpoints and cells: one axis per sub-lane (re-used from the last step while every lane stays in its cell)
+  const QuadBr qb = quad_br_cached<true, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc);
   const double a45 = T[OFF_BP_A1 + N_A2 - 1];
-  F16_PHASE();
-  const QuadBr qb = quad_br_cells(rx, nX, vX);
   if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
   if (qb.offb) status |= ST_BETA;
   if (qb.offd) status |= ST_EL;

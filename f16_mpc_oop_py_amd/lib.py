@@ -33,6 +33,7 @@ F16_FLAG_FIX_CLR = 1
 F16_FLAG_NO_ENVELOPE = 2
 F16_FLAG_ONE_LANE = 4          # rollouts: the one-lane-per-aircraft kernel whatever the batch size (results independent of B)
 F16_FLAG_HOLD_COMMAND = 8      # closed MPC loops: a step without a command (infeasible QP, state not finite) keeps the previous one
+F16_FLAG_NO_CELL_CACHE = 16    # diagnostic: quad rollout re-brackets every step (no cell re-use); results bit-identical either way
 
 
 class F16HipError(RuntimeError):

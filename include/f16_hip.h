@@ -62,6 +62,9 @@ typedef struct f16_ctx f16_ctx;
 #define F16_FLAG_HOLD_COMMAND 8u /* closed MPC loops (f16_rollout_mpc; dist.closed_loop_mpc_rollout(hold_command=True)): a step whose QP
                                     is infeasible (or whose state is not finite) keeps the PREVIOUS surface commands instead of the NaN
                                     the reference would write into u.values (env.py:420-424 -> test_env.py:490-493)                  */
+#define F16_FLAG_NO_CELL_CACHE 16u /* diagnostic: the quad rollout kernel (B <= 8192, hifi) re-brackets every table axis on every
+                                    step instead of re-using the previous step's cell while the value stays inside it.  Results
+                                    are bit-identical either way; the flag exists so that tests can compare the two paths.   */
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* Builds the fp64 table image (int/1e5, IEEE division) and uploads it to `device`. */
