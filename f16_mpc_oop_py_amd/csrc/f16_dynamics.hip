@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/f16_hip.h"
 #include "f16_ctx.h"
 #include "f16_plant.hpp"
@@ -43,6 +45,63 @@ struct DynArgs {
   const double *K;      // [27][ld] the reference's K = -dlqr (3 x 9 row-major), or null
   const double *dem;    // [3][ld] p, q, r demands
   double *u_out;        // [4][ld] the action of the last step (self.u.values after the loop), may be null
+};
+// The SCHED instantiations (f16_rollout_sched / f16_rollout_lqr_sched) take the input schedule behind the same fields -- a type of
+// their own, so that the constant-input kernels keep their argument block byte for byte.  seq: u_seq [nrows][4][ld], or under the
+// LQR law dem_seq [nrows][3][ld]; step t takes row t / hold.  u (dem) points at row 0, which every kernel reads like a constant input.
+struct SchedArgs : DynArgs {
+  const double *seq;
+  int hold, nrows;
+};
+template <bool SCHED>
+using RolloutArgs = std::conditional_t<SCHED, SchedArgs, DynArgs>;
+
+// The schedule of one lane in a SCHED instantiation, N values per row (ld apart, the lane's first at row + lane_off).  A new row
+// must never be loaded where it is used: a load that misses to HBM is ~900 cycles, a third of a quad-kernel step.
+//   AHEAD = true   the next row waits in registers nx: loaded when the current row is installed, `hold` >= 1 whole steps before its
+//                  first use, so the only wait for it stands in the install branch a step or more after the load was issued
+//                  (one wave per SIMD: the registers are there)
+//   AHEAD = false  no registers of its own: take() loads straight into the caller's.  The split kernels call it right after the
+//                  LAST use of the old row -- wave 3 reads its inputs in the first half of a step and idles in the second, so the
+//                  load is one step (less a few instructions) ahead of its use; the 512-lane kernels, whose registers already
+//                  spill, call it at the end of a step, where the second wave of the SIMD issues while this one waits.
+// settle(): every load of the prologue (state, inputs, gains, status) has landed before the step loop is entered.  Without it the
+// compiler, which cannot tell the iterations apart, waits for ALL outstanding loads -- the row just requested among them -- at the
+// first use of any prologue-loaded register in an iteration, i.e. at the top of the next step: the load would be waited for
+// where the step starts instead of where the row is used.
+// The bookkeeping (due) is the same on every lane of the workgroup and stays in scalar registers; only take() is per lane, and in
+// the split kernels only wave 3 calls it.  A row is addressed FROM THE LANE'S STATE COLUMN col = a.out + b, whose address lives
+// through the rollout anyway, by the (uniform) distance rel between the two arrays: no second per-lane address is kept for it.
+template <int N, bool AHEAD = true>
+struct RowAhead {
+  double nx[AHEAD ? N : 1];
+  long rel;                      // the next row to install: seq + row * nvals * ld - out, in doubles
+  int left, rows;                // steps until it takes over; rows still to install
+  F16_DEV void load(double *d, const double *col, long at, long ld) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) d[k] = col[at + k * ld];
+  }
+  // nvals: values per row of the schedule (4 commands, or 3 demands); first: the lane's first value within a row (a multiple of ld)
+  F16_DEV void init(const SchedArgs &a, int nvals, const double *col, long first = 0, bool owner = true) {
+    nx[0] = 0;
+    rel = (a.seq - a.out) + nvals * a.ld; left = a.hold; rows = a.nrows - 1;
+    if (AHEAD && owner && rows > 0) load(nx, col, rel + first, a.ld);
+  }
+  F16_DEV static void settle() { __builtin_amdgcn_s_waitcnt(0); }
+  F16_DEV bool due(const SchedArgs &a, int nvals) {            // once per step, after its inputs were used: a new row from the next step on?
+    if (--left != 0 || rows == 0) return false;
+    left = a.hold; --rows; rel += nvals * a.ld;
+    return true;
+  }
+  F16_DEV void take(const SchedArgs &a, int nvals, double *d, const double *col, long first = 0) {   // after due(): the new row into d[0..N)
+    if (AHEAD) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) d[k] = nx[k];
+      if (rows > 0) load(nx, col, rel + first, a.ld);
+    } else {
+      load(d, col, rel - nvals * a.ld + first, a.ld);
+    }
+  }
 };
 
 // env.py:360-371 `_calc_LQR_action`: u = -K (x_ref - x) + u0 with x_ref = x except x_ref[4:7] = (p, q, r)_dem -- x_ref - x is
@@ -107,8 +166,8 @@ constexpr bool INC_TRIG = true;
 #else
 constexpr bool INC_TRIG = false;
 #endif
-template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false>
-__device__ __forceinline__ void rollout_lanes(const DynArgs &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
+template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false>
+__device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
                                               double (*tgs)[BLOCK] = nullptr) {
   for (long b = (long)blockIdx.x * BLOCK + threadIdx.x; b < a.B; b += (long)gridDim.x * BLOCK) {
     double x[18];
@@ -129,6 +188,14 @@ __device__ __forceinline__ void rollout_lanes(const DynArgs &a, TP T, double (*u
     double *tr = a.traj ? a.traj + b : nullptr;
     int until_store = a.traj_every;
     bool stale = true;                                   // (INCT) the first step evaluates the five pairs exactly
+    // SCHED: the row in use sits where the constant input does (us / kq[9..11]); the next one in registers (<= 256 lanes)
+    constexpr int NR = LQR ? 3 : 4;
+    // 64-lane workgroups (B <= 16,384) count the 32 steps between exact sin / cos evaluations from the start of the ROW, as the
+    // chain of launches does for any hold; the larger ones from the start of the launch (the chain's steps when hold % 32 == 0)
+    constexpr bool ROW_TRIG = SCHED && INCT && BLOCK == 64;
+    int t0 = 0;
+    RowAhead<NR, BLOCK <= 256> ra;
+    if constexpr (SCHED) { ra.init(a, NR, a.out + b); ra.settle(); }
     for (int t = 0; t < a.nsteps; ++t) {
       // env.py:117-124: the reference exit()s; here the aircraft is frozen and flagged
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;
@@ -144,7 +211,7 @@ __device__ __forceinline__ void rollout_lanes(const DynArgs &a, TP T, double (*u
         }
         if (INCT) {
           const TrigSlots ts{&tgs[0][threadIdx.x], BLOCK};
-          if (stale || (t & 31) == 0) { Trig5 g; trig_exact(x, g); trig_store(ts, g); }
+          if (stale || ((ROW_TRIG ? t - t0 : t) & 31) == 0) { Trig5 g; trig_exact(x, g); trig_store(ts, g); }
           calc_xdot<FI, TP, true>(T, a.lofi, x, u, xd, a.xcg, a.fi, a.flags, st, &ts);
           const double xo5[5] = {x[7], x[8], x[4], x[3], x[5]};
 #pragma unroll
@@ -161,6 +228,14 @@ __device__ __forceinline__ void rollout_lanes(const DynArgs &a, TP T, double (*u
 #pragma unroll
         for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
         tr += 18 * a.ld;
+      }
+      if constexpr (SCHED) if (ra.due(a, NR)) {
+        double r[NR];
+        ra.take(a, NR, r, a.out + b);
+#pragma unroll
+        for (int k = 0; k < NR; ++k) (LQR ? kq[9 + k] : us[k])[threadIdx.x] = r[k];
+        if (LQR) { ul[0] = us[1][threadIdx.x]; ul[1] = us[2][threadIdx.x]; ul[2] = us[3][threadIdx.x]; }   // (as a new launch: u0 until it steps)
+        if (ROW_TRIG) { t0 = t + 1; stale = true; }
       }
     }
     bool finite = true;
@@ -184,8 +259,8 @@ __device__ __forceinline__ void rollout_lanes(const DynArgs &a, TP T, double (*u
 // from global memory: no LDS staging) -- ONE instruction sequence for every batch size, the one the closed MPC loop (f16_rollout_mpc)
 // steps with.  Same rules as rollout_lanes (envelope freeze, status bits, trajectory samples, u_out); a reproducibility path, not a
 // fast one.
-template <bool LQR>
-__global__ __launch_bounds__(64) void k_rollout_exact(DynArgs a) {
+template <bool LQR, bool SCHED = false>
+__global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
   for (long b = (long)blockIdx.x * 64 + threadIdx.x; b < a.B; b += (long)gridDim.x * 64) {
     double x[18], u[4];
 #pragma unroll
@@ -204,6 +279,9 @@ __global__ __launch_bounds__(64) void k_rollout_exact(DynArgs a) {
     int st = a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr;
     int until_store = a.traj_every;
+    constexpr int NR = LQR ? 3 : 4;
+    RowAhead<NR> ra;
+    if constexpr (SCHED) { ra.init(a, NR, a.out + b); ra.settle(); }
     for (int t = 0; t < a.nsteps; ++t) {
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;      // env.py:117-124
       if (!(st & ST_ENVELOPE)) {
@@ -219,6 +297,10 @@ __global__ __launch_bounds__(64) void k_rollout_exact(DynArgs a) {
 #pragma unroll
         for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
         tr += 18 * a.ld;
+      }
+      if constexpr (SCHED) if (ra.due(a, NR)) {
+        ra.take(a, NR, LQR ? kq + 9 : u, a.out + b);
+        if (LQR) { u[1] = u0[0]; u[2] = u0[1]; u[3] = u0[2]; }      // (as a new launch: u0 until it steps)
       }
     }
     bool finite = true;
@@ -236,8 +318,8 @@ __global__ __launch_bounds__(64) void k_rollout_exact(DynArgs a) {
   }
 }
 
-template <int BLOCK, int FI, bool LQR = false>
-__global__ __launch_bounds__(BLOCK) void k_rollout(DynArgs a) {
+template <int BLOCK, int FI, bool LQR = false, bool SCHED = false>
+__global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED> a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   // the four inputs of a lane are constant over the rollout and used once per step: kept in lane-indexed (conflict-free) LDS
   // slots rather than in eight registers that the 512-lane instantiation (256 registers per lane) spilled and reloaded per step
@@ -246,15 +328,15 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(DynArgs a) {
   constexpr bool INCT = INC_TRIG && BLOCK <= 256 && !(LQR && BLOCK == 256);      // (the ten slots must fit beside the fp64 table image and, closed loop, the gain slots)
   __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
   if (a.fi == 1) stage_tables(tab, a.tab);
-  rollout_lanes<BLOCK, FI, const double *, LQR, INCT>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
+  rollout_lanes<BLOCK, FI, const double *, LQR, INCT, SCHED>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
                                                       reinterpret_cast<double (*)[BLOCK]>(tgs));
 }
 
 // The same rollout on the scaled-integer table image (hifi, default numerics; large batches: the LDS pipe -- 1.5 KB of
 // table vertices per aircraft-step as doubles, more than half of its cycles bank-conflict replays of the per-lane gathers --
 // is one of the two ceilings of k_rollout there).
-template <int BLOCK, bool LQR = false>
-__global__ __launch_bounds__(BLOCK) void k_rollout_i(DynArgs a) {
+template <int BLOCK, bool LQR = false, bool SCHED = false>
+__global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED> a) {
   __shared__ __attribute__((aligned(16))) int tab[i32::IMAGE_INTS];
   __shared__ double us[4][BLOCK];
   __shared__ double kq[LQR ? 12 : 1][LQR ? BLOCK : 1];
@@ -266,7 +348,7 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_i(DynArgs a) {
     for (int i = threadIdx.x; i < i32::IMAGE_INTS / 4; i += BLOCK) dst[i] = src[i];
     __syncthreads();
   }
-  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq), reinterpret_cast<double (*)[BLOCK]>(tgs));
+  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq), reinterpret_cast<double (*)[BLOCK]>(tgs));
 }
 
 // Four-wavefront rollout (latency regime, hifi): one workgroup = 64 aircraft on the four SIMDs of a CU; the state is
@@ -284,8 +366,8 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_i(DynArgs a) {
 #else
 #define STAMP(acc)
 #endif
-template <bool LQR>
-__global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
+template <bool LQR, bool SCHED = false>
+__global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   __shared__ double xs[17][64], xt[14][64];  // xs: x[0..16] published at step start ; xt: 4 x 3 partial totals, qbar, ps
   __shared__ int xenv[3][64], xst[4][64];
@@ -317,6 +399,9 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
     int st = a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr;           // next sample to be written by THIS wave
     int until_store = a.traj_every;
+    constexpr int NR = LQR ? 3 : 4;
+    RowAhead<NR, false> ra;                                // SCHED: wave 3 owns the inputs and re-loads them right after their last use
+    if constexpr (SCHED) { ra.init(a, NR, a.out + b, 0, wave == 3); ra.settle(); }
 #ifdef F16_EXP_STAMP4W
     unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -359,6 +444,8 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
       Pre p;
       double xd[18], o[3];
       int sa = 0;
+      bool newrow = false;
+      if constexpr (SCHED) newrow = ra.due(a, NR);
       if (wave == 0) {
         plant_pre<false>(xa, p, xd);
         aero_part<3>((const double *)tab, xa, a.flags, o, sa);       // longitudinal damping derivatives (1-D tables)
@@ -396,6 +483,10 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
             for (int k = 12; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
           }
           tr += 18 * a.ld;
+        }
+        if constexpr (SCHED) if (newrow) {
+          ra.take(a, NR, LQR ? kq + 9 : u, a.out + b);
+          if (LQR) { ul[0] = u[1]; ul[1] = u[2]; ul[2] = u[3]; }      // (as a new launch: u0 until it steps)
         }
       }
       // partial totals: wave 1 -> 0..2 (long. static), wave 0 -> 3..5 (long. damping), wave 2 -> 6..8, wave 3 -> 9..11
@@ -476,8 +567,8 @@ __global__ __launch_bounds__(256) void k_rollout_4w(DynArgs a) {
 // Owned states are replicated over the sub-lanes of their wave; two barriers per step as in k_rollout_4w.
 // GROUPS = 2 (4096 < B <= 8192): two independent 16-aircraft groups per workgroup share the LDS table image, one role
 // wave of each on every SIMD -- the two dependency chains interleave.
-template <int GROUPS, bool LQR = false>
-__global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
+template <int GROUPS, bool LQR = false, bool SCHED = false>
+__global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a) {
   constexpr int NA = 16 * GROUPS;
   constexpr bool G1 = GROUPS == 1;     // cell re-use and psi on wave 0: one group only (at GROUPS = 2 the registers spill)
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
@@ -498,7 +589,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
     double x[18];
 #pragma unroll
     for (int k = 0; k < 18; ++k) x[k] = a.out[k * a.ld + b];
-    const double ucmd = a.u[s * a.ld + b];                 // wave 3: sub-lane s drives actuator s
+    double ucmd = a.u[s * a.ld + b];                       // wave 3: sub-lane s drives actuator s
     // LQR (wave 3, sub-lanes 1..3): row s - 1 of K, columns 4..6, and the demands; the action of the last step
     double kr0 = 0, kr1 = 0, kr2 = 0, dm0 = 0, dm1 = 0, dm2 = 0, ulast = ucmd;
     if (LQR && wave == 3) {
@@ -511,6 +602,17 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
     double *tr = a.traj ? a.traj + b : nullptr;            // next sample (written by wave 2 from the published state)
     int until_store = a.traj_every;
     QuadCell qc = quad_cell_none();                        // waves 0 / 1: cells of the last full lookup (none at launch start)
+    // SCHED: wave 3 owns the inputs and re-loads them right after their last use in a step -- sub-lane s its own command of the
+    // new row; under the LQR law sub-lane j = 0..2 demand j (dmq), handed round the quad at the point of use: one 8-byte load
+    // per lane and row either way, and four registers fewer than three demands on every sub-lane (GROUPS = 2 has none to spare)
+    RowAhead<1, false> ra;
+    double dmq = 0;
+    const int rs = LQR && s == 3 ? 2 : s;                  // the value of a row this sub-lane reads
+    if constexpr (SCHED) {
+      dmq = s == 0 ? dm0 : (s == 1 ? dm1 : dm2);
+      ra.init(a, LQR ? 3 : 4, a.out + b, rs * a.ld, wave == 3);
+      ra.settle();
+    }
     if (G1 && wave == 0 && s == 0) {                       // sin / cos of the first step's psi (the loop's first barrier publishes it)
       double sp, cp;
       F16_SINCOS(x[5], &sp, &cp);
@@ -572,6 +674,8 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
       double xd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       double U = 0, V = 0, W = 0, s_t = 0, c_t = 0, s_phi = 0, c_phi = 0, cb = 0, vtc = 0, r1 = 0, r2 = 0, r3 = 0;
       double fu0 = 0, fv0 = 0, fw0 = 0, mo0 = 0, mo1 = 0, mo2 = 0;
+      bool newrow = false;
+      if constexpr (SCHED) newrow = ra.due(a, LQR ? 3 : 4);
       if (wave == 0) {
         int sa_ = 0;
         double latd;
@@ -652,6 +756,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
           const double lim = s == 1 ? 25.0 : (s == 2 ? 21.5 : 30.0), rate = s == 1 ? 60.0 : (s == 2 ? 80.0 : 120.0);
           double uc = ucmd;
           if (LQR) {
+            if constexpr (SCHED) { dm0 = quad_bcast<0>(dmq); dm1 = quad_bcast<1>(dmq); dm2 = quad_bcast<2>(dmq); }   // (live is the same over a quad)
             const double ua = lqr_action(kr0, kr1, kr2, dm0 - xa[9], dm1 - xa[10], dm2 - xa[11], ucmd);
             uc = s > 0 ? ua : ucmd;
             ulast = uc;
@@ -663,6 +768,16 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(DynArgs a) {
           xact += (s == 0 ? dth : dsf) * a.dt;             // env.py:126 on the actuator / flap states
           x[16] += lf2_dot * a.dt;
           x[17] += lf1_dot * a.dt;
+        }
+        if constexpr (SCHED) if (newrow) {
+          // (the sub-lane from the lane number, inside this branch: neither a register kept through the step for it nor -- GROUPS = 2
+          //  spills -- a scratch reload in front of the load; volatile so that it is not hoisted out again)
+          int rv;
+          asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(rv));
+          rv &= 3;
+          if (LQR && rv == 3) rv = 2;
+          ra.take(a, LQR ? 3 : 4, LQR ? &dmq : &ucmd, a.out + b, rv * a.ld);
+          if (LQR) ulast = ucmd;                          // (as a new launch: u0 until it steps)
         }
       }
       QSTAMP(tB)
@@ -927,8 +1042,16 @@ extern "C" int f16_nlplant_batch(f16_ctx *ctx, const double *xu, double *xdot, i
 
 // LQR = true: the closed loop of f16_rollout_lqr (same launch rules; the one-lane kernels keep K[i][4..6] and the demands in
 // lane-indexed LDS slots, which a 512-lane workgroup has room for only beside the integer table image)
-template <bool LQR>
-static int rollout_dispatch(f16_ctx *ctx, DynArgs &a, void *stream) {
+// SCHED = true: the same rules for f16_rollout_sched / f16_rollout_lqr_sched -- every kernel has a scheduled twin, so a schedule
+// never moves a batch to another kernel family.
+template <int BLOCK, bool LQR, bool SCHED>
+static void launch_lanes(int grid, hipStream_t st, const RolloutArgs<SCHED> &a) {
+  if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED>), dim3(grid), dim3(BLOCK), 0, st, a);
+  else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED>), dim3(grid), dim3(BLOCK), 0, st, a);
+}
+
+template <bool LQR, bool SCHED = false>
+static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED> &a, void *stream) {
   const long B = a.B;
   const int fi_flag = a.fi;
   static const long max4w = [] { const char *e = getenv("F16_ROLLOUT_4W_MAXB"); return e ? atol(e) : 64L * 256; }();
@@ -936,23 +1059,23 @@ static int rollout_dispatch(f16_ctx *ctx, DynArgs &a, void *stream) {
   if (a.flags & F16_FLAG_ONE_LANE) {
     // results independent of the batch size: ONE kernel for every B, its step an out-of-line function (k_rollout_exact)
     const long blocks = (B + 63) / 64;
-    hipLaunchKernelGGL(k_rollout_exact<LQR>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "f16_rollout launch");
   }
   if (fi_flag == 1 && B <= maxq) {
     // at most 16 aircraft per CU: four lanes per aircraft, one 16-aircraft workgroup per CU
-    hipLaunchKernelGGL((k_rollout_q<1, LQR>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_rollout_q<1, LQR, SCHED>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "f16_rollout launch");
   }
   if (fi_flag == 1 && B <= 2 * maxq) {
     // at most 32 per CU: two 16-aircraft groups per workgroup
-    hipLaunchKernelGGL((k_rollout_q<2, LQR>), dim3((unsigned)((B + 31) / 32)), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_rollout_q<2, LQR, SCHED>), dim3((unsigned)((B + 31) / 32)), dim3(512), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "f16_rollout launch");
   }
   // (three groups per workgroup leave 168 registers per lane: the roles spill, 3.96 ms against the 4-wave kernel's 2.13)
   if (fi_flag == 1 && B <= max4w) {
     // latency regime: four wavefronts per 64 aircraft, one workgroup per CU
-    hipLaunchKernelGGL(k_rollout_4w<LQR>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_rollout_4w<LQR, SCHED>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "f16_rollout launch");
   }
   Geometry g = geometry(B, fi_flag);
@@ -961,41 +1084,52 @@ static int rollout_dispatch(f16_ctx *ctx, DynArgs &a, void *stream) {
   static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
   if (fi_flag == 1 && use_i32 && g.block == 512) {
     a.tab32 = ctx->d_tab32;
-    hipLaunchKernelGGL((k_rollout_i<512, LQR>), dim3(g.grid), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED>), dim3(g.grid), dim3(512), 0, (hipStream_t)stream, a);
     return hip_check(hipGetLastError(), "f16_rollout launch");
   }
 #endif
-  if (LQR) {
-    if (g.block == 512) g.block = 256;       // (fp64 image + 16 slots of 512 lanes would not fit the 160 KB of a CU)
-    const hipStream_t st = (hipStream_t)stream;
-    if (g.block == 64) {
-      if (fi_flag == 0) hipLaunchKernelGGL((k_rollout<64, 0, LQR>), dim3(g.grid), dim3(64), 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<64, -1, LQR>), dim3(g.grid), dim3(64), 0, st, a);
-    } else if (g.block == 128) {
-      if (fi_flag == 0) hipLaunchKernelGGL((k_rollout<128, 0, LQR>), dim3(g.grid), dim3(128), 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<128, -1, LQR>), dim3(g.grid), dim3(128), 0, st, a);
-    } else {
-      if (fi_flag == 0) hipLaunchKernelGGL((k_rollout<256, 0, LQR>), dim3(g.grid), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<256, -1, LQR>), dim3(g.grid), dim3(256), 0, st, a);
-    }
-    return hip_check(hipGetLastError(), "f16_rollout launch");
-  }
-  LAUNCH_BY_BLOCK_FI(k_rollout, g, (hipStream_t)stream, a);
+  if (LQR && g.block == 512) g.block = 256;  // (fp64 image + 16 slots of 512 lanes would not fit the 160 KB of a CU)
+  const hipStream_t st = (hipStream_t)stream;
+  if (g.block == 64) launch_lanes<64, LQR, SCHED>(g.grid, st, a);
+  else if (g.block == 128) launch_lanes<128, LQR, SCHED>(g.grid, st, a);
+  else if (LQR || g.block == 256) launch_lanes<256, LQR, SCHED>(g.grid, st, a);
+  else launch_lanes<512, false, SCHED>(g.grid, st, a);
   return hip_check(hipGetLastError(), "f16_rollout launch");
+}
+
+// the argument rules f16_rollout and its scheduled / closed-loop siblings share
+static int check_rollout(f16_ctx *ctx, const double *x, const double *u, const double *traj, long B, long ld, int nsteps, int traj_every) {
+  if (int rc = check_common(ctx, x, u, B, ld)) return rc;
+  if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
+    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj is given");
+  return F16_OK;
 }
 
 extern "C" int f16_rollout(f16_ctx *ctx, double *x, const double *u, double *traj, int32_t *status, long B, long ld,
                            int nsteps, int traj_every, double dt, double xcg, int fi_flag, unsigned flags,
                            void *stream) {
-  if (int rc = check_common(ctx, x, u, B, ld)) return rc;
-  if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
-    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj is given");
+  if (int rc = check_rollout(ctx, x, u, traj, B, ld, nsteps, traj_every)) return rc;
   if (B == 0 || nsteps == 0) return F16_OK;
   DynArgs a{};
   a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u; a.out = x; a.traj = traj; a.status = status;
   a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
   a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   return rollout_dispatch<false>(ctx, a, stream);
+}
+
+extern "C" int f16_rollout_sched(f16_ctx *ctx, double *x, const double *u_seq, double *traj, int32_t *status, long B, long ld,
+                                 int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, unsigned flags,
+                                 void *stream) {
+  if (!u_seq) return set_error(F16_EINVAL, "u_seq is NULL");
+  if (int rc = check_rollout(ctx, x, u_seq, traj, B, ld, nsteps, traj_every)) return rc;
+  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
+  if (B == 0 || nsteps == 0) return F16_OK;
+  SchedArgs a{};
+  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u_seq; a.out = x; a.traj = traj; a.status = status;
+  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
+  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  a.seq = u_seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
+  return rollout_dispatch<false, true>(ctx, a, stream);
 }
 
 extern "C" int f16_rollout_lqr(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem, double *traj,
@@ -1012,6 +1146,22 @@ extern "C" int f16_rollout_lqr(f16_ctx *ctx, double *x, const double *u0, const 
   a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   a.K = K; a.dem = dem; a.u_out = u_out;
   return rollout_dispatch<true>(ctx, a, stream);
+}
+
+extern "C" int f16_rollout_lqr_sched(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq,
+                                     double *traj, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
+                                     int traj_every, double dt, double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (int rc = check_rollout(ctx, x, u0, traj, B, ld, nsteps, traj_every)) return rc;
+  if (!K || !dem_seq) return set_error(F16_EINVAL, "K / dem_seq is NULL");
+  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
+  if (B == 0 || nsteps == 0) return F16_OK;
+  SchedArgs a{};
+  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u0; a.out = x; a.traj = traj; a.status = status;
+  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
+  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  a.K = K; a.dem = dem_seq; a.u_out = u_out;
+  a.seq = dem_seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
+  return rollout_dispatch<true, true>(ctx, a, stream);
 }
 
 extern "C" int f16_rollout_lqr_linear(f16_ctx *ctx, double *x9, const double *Ad, const double *Bd, const double *K, const double *x_ref,

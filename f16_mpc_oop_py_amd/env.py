@@ -201,6 +201,42 @@ class F16Batch:
                                          self.flags, self._stream))
         return traj
 
+    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None):
+        """The reference's call pattern `u.values = action; step(u.values)` with an action that changes during the run
+        (env.py:105-130; the doublets of Nguyen_m/runF16Sim.m) in ONE launch (C-ABI f16_rollout_sched): step t takes
+        actions[t // hold], a zero-order hold.  actions: [S, B, 4] (numpy or torch), or a state-major [S, 4, B] fp64 tensor
+        already on the device, which is taken as it is, without a copy (for B == 4 a 3-D device tensor is read as [S, B, 4];
+        pass a host array or a non-contiguous view to say otherwise).  nsteps defaults to S * hold and needs
+        S >= ceil(nsteps / hold) rows.  Returns what `rollout` returns; u.values ends up holding the last row used, as the
+        reference's caller leaves it."""
+        hold = int(hold)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
+        if t.dim() != 3:
+            raise ValueError(f"actions must be [S, B, 4] or a state-major [S, 4, B] device tensor, not {tuple(t.shape)}")
+        if tuple(t.shape[1:]) == (self.B, 4):
+            seq = t.to(device=self.device, dtype=torch.float64).permute(0, 2, 1).contiguous()
+        elif tuple(t.shape[1:]) == (4, self.B) and t.device == self.device and t.dtype == torch.float64 and t.is_contiguous():
+            seq = t
+        else:
+            raise ValueError(f"actions must be [S, {self.B}, 4] or a contiguous fp64 [S, 4, {self.B}] tensor on {self.device}, "
+                             f"not {tuple(t.shape)} ({t.dtype}, {t.device})")
+        S = seq.shape[0]
+        nsteps = S * hold if nsteps is None else int(nsteps)
+        if nsteps < 1 or (nsteps + hold - 1) // hold > S:
+            raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), actions has {S}")
+        traj = None
+        if traj_every:
+            if nsteps % int(traj_every):
+                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
+            traj = torch.empty((nsteps // int(traj_every), 18, self.B), dtype=torch.float64, device=self.device)
+        self._check(self.lib.f16_rollout_sched(self.ctx.handle, _vp(self._x), _vp(seq), _vp(traj), _vp(self.status), self.B,
+                                               self.B, nsteps, hold, int(traj_every or 1), self.dt, self.xcg, self.fi_flag,
+                                               self.flags, self._stream))
+        self._u.copy_(seq[(nsteps - 1) // hold])
+        return traj
+
     # ------------------------------------------------------------------ env.py:152-193
     def _get_mpc_x(self):
         return self._x[P.mpc_x_idx].t()
@@ -336,8 +372,29 @@ class F16Batch:
                 dem[k] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
         return dem
 
+    def _demand_schedule(self, p_dem, q_dem, r_dem):
+        """Demands of which at least one is a time history [S] or [S, B] (scalars broadcast) -> state-major [S, 3, B] on the device;
+        None when none of them is (scalar / [B] demands: the constant-input path)."""
+        vs = [v if isinstance(v, (int, float)) else torch.as_tensor(v, dtype=torch.float64, device=self.device) for v in (p_dem, q_dem, r_dem)]
+        # ([B] is a constant demand per aircraft, as it always was; a time history for B aircraft is [S, B])
+        hist = [v for v in vs if torch.is_tensor(v) and (v.dim() == 2 or (v.dim() == 1 and v.shape[0] != self.B))]
+        if not hist:
+            return None
+        S = hist[0].shape[0]
+        seq = torch.empty((S, 3, self.B), dtype=torch.float64, device=self.device)
+        for k, v in enumerate(vs):
+            if not torch.is_tensor(v) or v.dim() == 0:
+                seq[:, k].fill_(float(v))
+            elif v.dim() == 2 or v.shape[0] != self.B:
+                if v.shape[0] != S or (v.dim() == 2 and v.shape[1] != self.B):
+                    raise ValueError(f"demand histories must agree: [{S}] or [{S}, {self.B}], not {tuple(v.shape)}")
+                seq[:, k] = v if v.dim() == 2 else v.unsqueeze(1)
+            else:
+                seq[:, k] = v.unsqueeze(0)
+        return seq
+
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
-                    R=None):
+                    R=None, hold=None):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -349,7 +406,22 @@ class F16Batch:
         locals).  Returns (x_storage [nsteps//k, 9, B], u_storage [nsteps//k, 3, B]) with k = traj_every or 1.
         relinearise=True: the same law with K re-derived at EVERY step, `_calc_LQR_gain(Q, R)` at the current (x, u) (Q, R: the
         weights of utils.py:219 dlqr, default env.py's Cd'Cd and I), in one launch (rollout_LQR_relin with track = (4, 5, 6));
-        K must be None.  Returns the states as with linear=False."""
+        K must be None.  Returns the states as with linear=False.
+        Demand histories: when any of p_dem, q_dem, r_dem is [S] or [S, B] (the pilot loop of flight_sim.py:141-182, whose demands
+        change from frame to frame under one gain) the loop runs as one launch of f16_rollout_lqr_sched: step t takes row
+        t // hold (hold defaults to 1; scalars are broadcast; S >= ceil(nsteps / hold)).  Not combined with linear=True or
+        relinearise=True (ValueError).  Scalar / [B] demands call f16_rollout_lqr exactly as before; hold is then not taken."""
+        dem_seq = self._demand_schedule(p_dem, q_dem, r_dem)
+        if dem_seq is not None:
+            if linear or relinearise:
+                raise ValueError("demand histories run on the nonlinear loop with a fixed gain (not with linear=True / relinearise=True)")
+            hold = 1 if hold is None else int(hold)
+            if hold < 1:
+                raise ValueError("hold must be >= 1")
+            if nsteps < 1 or (nsteps + hold - 1) // hold > dem_seq.shape[0]:
+                raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), the demands have {dem_seq.shape[0]}")
+        elif hold is not None:
+            raise ValueError("hold goes with demand histories ([S] or [S, B]); scalar / [B] demands are constant")
         if relinearise:
             if K is not None or linear:
                 raise ValueError("relinearise=True derives K at every step on the nonlinear model (K and linear are not taken)")
@@ -365,7 +437,7 @@ class F16Batch:
         if K is None:
             K = self._calc_LQR_gain()
         Ks = torch.as_tensor(K, device=self.device, dtype=torch.float64).reshape(self.B, 27).t().contiguous()
-        dem = self._demands(p_dem, q_dem, r_dem)
+        dem = self._demands(p_dem, q_dem, r_dem) if dem_seq is None else None
         if linear:
             if self.ssr is None:
                 self.build_ssr()
@@ -383,6 +455,11 @@ class F16Batch:
         if traj_every:
             assert nsteps % traj_every == 0
             traj = torch.empty((nsteps // traj_every, 18, self.B), dtype=torch.float64, device=self.device)
+        if dem_seq is not None:
+            self._check(self.lib.f16_rollout_lqr_sched(self.ctx.handle, _vp(self._x), _vp(u0s), _vp(Ks), _vp(dem_seq), _vp(traj),
+                                                       _vp(self._u), _vp(self.status), self.B, self.B, int(nsteps), hold,
+                                                       int(traj_every or 1), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
+            return traj
         self._check(self.lib.f16_rollout_lqr(self.ctx.handle, _vp(self._x), _vp(u0s), _vp(Ks), _vp(dem), _vp(traj), _vp(self._u),
                                              _vp(self.status), self.B, self.B, int(nsteps), int(traj_every or 1), self.dt,
                                              self.xcg, self.fi_flag, self.flags, self._stream))

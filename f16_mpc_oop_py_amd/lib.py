@@ -224,6 +224,9 @@ def load():
     L.f16_nlplant_batch.argtypes = [vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_rollout.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, d, d, i, u, vp]
     L.f16_rollout_lqr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, d, d, i, u, vp]
+    if hasattr(L, "f16_rollout_sched"):      # (absent from an older library loaded through F16HIP_SO for an A/B run: calling it then raises)
+        L.f16_rollout_sched.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
+        L.f16_rollout_lqr_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
     L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]

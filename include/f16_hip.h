@@ -131,6 +131,32 @@ int f16_rollout(f16_ctx *ctx, double *x, const double *u, double *traj, int32_t 
 int f16_rollout_lqr(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem, double *traj,
                     double *u_out, int32_t *status, long B, long ld, int nsteps, int traj_every, double dt, double xcg,
                     int fi_flag, unsigned flags, void *stream);
+/* f16_rollout / f16_rollout_lqr under an INPUT SCHEDULE, as ONE launch: the reference's caller hands step() a new action at every
+ * step (env.py:105-130; the doublets of Nguyen_m/runF16Sim.m; the pilot demands of flight_sim.py:141-182), which with a constant
+ * input per launch costs one launch and one row copy per input change.
+ *   f16_rollout_sched      u_seq[S][4][ld]   the four commands;
+ *   f16_rollout_lqr_sched  dem_seq[S][3][ld] the (p, q, r) demands -- the thrust command stays u0[0], K and u0 are constant;
+ * S = ceil(nsteps / hold) rows in the state-major layout of every other argument.  Step t of the launch uses row t / hold: a
+ * zero-order hold whose last segment may be shorter.  hold >= 1; hold = 1 is a new input at every step, hold >= nsteps reads row 0
+ * only.  Everything else as in f16_rollout / f16_rollout_lqr: x in place, traj and traj_every (independent of hold), envelope freeze
+ * (a frozen aircraft ignores the rest of its schedule), sticky status bits, F16_FLAG_*, u_out; NaN / infinite commands go through
+ * the actuator models as a constant one does.  F16_EINVAL where f16_rollout returns it, and for hold < 1 or a NULL u_seq / dem_seq.
+ * Contract: the result -- final state, status, every stored sample, u_out -- equals the chain of f16_rollout (f16_rollout_lqr)
+ * calls, one per segment with that segment's row, BIT FOR BIT wherever f16_rollout's split-launch guarantee holds: any hold for
+ * B <= 16,384 (the lofi kernel of that range, which does carry its sin / cos pairs, restarts them with every row as the chain's
+ * launches do); any hold under F16_FLAG_ONE_LANE; hold % 32 == 0 beyond that (the carried pairs are re-evaluated at steps 0, 32,
+ * ... of the launch, which are then the same steps as in the chain).  Other holds on the large-batch kernels agree with the chain
+ * to the 1e-12 relative over 100 steps stated above for split launches.  S identical rows give f16_rollout's own bits for any hold
+ * (in that lofi kernel: for hold % 32 == 0, else the chain's).  A schedule cut into two calls at a segment boundary equals
+ * one call under the same conditions.  The launch rules are f16_rollout's: every kernel has a scheduled twin, so a schedule never
+ * moves a batch to another kernel.  The next row is loaded a step or more before its first use; with hold = 1 that is
+ * 32 B (24 B) of reads per aircraft-step beside the 144 B a stored step writes.  Nothing is allocated: the calls can be captured
+ * into a graph. */
+int f16_rollout_sched(f16_ctx *ctx, double *x, const double *u_seq, double *traj, int32_t *status, long B, long ld, int nsteps,
+                      int hold, int traj_every, double dt, double xcg, int fi_flag, unsigned flags, void *stream);
+int f16_rollout_lqr_sched(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, double *traj,
+                          double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
+                          double xcg, int fi_flag, unsigned flags, void *stream);
 /* The reference's LINEAR-model closed loops as ONE launch (9-state reduced model, 3 inputs; one lane per aircraft, its matrices in
  * registers):   per step   u = -K (x_ref - x) + u0,   x = Ad x + Bd u
  *   test_env_mk2.py:46-62 `LQR(linear=True)` (what main.py:35 runs): the frozen model ssr.Ad / ssr.Bd under env.py:360-371

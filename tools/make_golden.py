@@ -626,8 +626,80 @@ def g2r_ref_rebuilt(n=400):
     print("g2r_ref_rebuilt.npz", os.path.getsize(os.path.join(OUT, "g2r_ref_rebuilt.npz")))
 
 
+def g17_input_schedules():
+    """G17: the reference's `step` loop (env.py:105-130) and its LQR loop (test_env_mk2.py:70-85) under inputs that CHANGE during
+    the run, both xcg builds.  Step loop from the trim point + the eight perturbed starts of G4 with their commands u0:
+      doublet   1000 steps, a new command every 100: u0 + s_k d with s = (0, +1, +1, -1, -1, 0, ...) (the shape of
+                Nguyen_m/runF16Sim.m), d per aircraft from default_rng(17): thrust U[-500, 500] lb, each surface U[-1, 1] deg
+      sinusoid  300 steps, a new command every step: u0 + d sin(2 pi t / 100)
+    LQR loop from G12's six starts and gains, 300 steps, the demands switched every 50 steps: rows from default_rng(18)
+    U[-0.15, 0.15], first row zero.  Every 25th state (and the last action of the LQR loop).  Inputs, schedules, recorded states."""
+    parameters, env, utils = import_reference()
+    libs = {25: ctypes.CDLL(os.path.join(REF, "C", "nlplant_xcg25.so")),
+            35: ctypes.CDLL(os.path.join(REF, "C", "nlplant_xcg35.so"))}
+    f16 = make_f16_objects(parameters, env, libs)
+    for k in libs:
+        if not clr_reads_zero(libs[k]):
+            raise SystemExit("this process's _CLr does not read ~0 (uninitialised heap): run the script again")
+    g4 = np.load(os.path.join(OUT, "g4_rollout.npz"))
+    g567 = np.load(os.path.join(OUT, "g567_trim_lin_lqr.npz"))
+    g12 = np.load(os.path.join(OUT, "g12_lqr_loop.npz"))
+    d = np.random.default_rng(17).uniform([-500, -1, -1, -1], [500, 1, 1, 1], (9, 4))
+    sk = np.array([0, 1, 1, -1, -1, 0, 0, 0, 0, 0.0])
+    sin_t = np.sin(2 * np.pi * np.arange(300) / 100)
+    dem_rows = np.random.default_rng(18).uniform(-0.15, 0.15, (6, 6, 3))
+    dem_rows[:, 0] = 0.0
+    g = dict(d=d, doublet_sign=sk, dem_rows=dem_rows)
+
+    def run(f, x0, useq, hold, nsteps):
+        f.reset()
+        f.x.values = np.copy(x0)
+        tr = []
+        for t in range(nsteps):
+            f.u.values = np.copy(useq[t // hold])
+            f.step(f.u.values)
+            if (t + 1) % 25 == 0:
+                tr.append(np.copy(f.x.values))
+        return np.array(tr)
+
+    for k, f in f16.items():
+        x0s = np.concatenate((g567[f"trim_x_xcg{k}"][None], g4[f"pert_x0_xcg{k}"]))
+        u0s = np.concatenate((g4[f"trim_u_xcg{k}"][None], g4[f"pert_u_xcg{k}"]))
+        dbl = u0s[None] + sk[:, None, None] * d[None]                  # [10, 9, 4]
+        sin = u0s[None] + sin_t[:, None, None] * d[None]               # [300, 9, 4]
+        g[f"x0_xcg{k}"], g[f"u0_xcg{k}"] = x0s, u0s
+        g[f"doublet_u_xcg{k}"], g[f"sin_u_xcg{k}"] = dbl, sin
+        g[f"doublet_traj_xcg{k}"] = np.array([run(f, x0s[j], dbl[:, j], 100, 1000) for j in range(9)])   # [9, 40, 18]
+        g[f"sin_traj_xcg{k}"] = np.array([run(f, x0s[j], sin[:, j], 1, 300) for j in range(9)])         # [9, 12, 18]
+        K = g12[f"K_xcg{k}"]
+        trajs, ulast = [], []
+        for j in range(6):
+            f.reset()
+            f.x.values = np.copy(g12[f"x0_xcg{k}"][j])
+            f.u.values = np.copy(f.u.initial_condition)
+            tr = []
+            for t in range(300):
+                dem = dem_rows[j, t // 50]
+                u = f._calc_LQR_action(dem[0], dem[1], dem[2], K, f.x._get_mpc_x(), f.u.initial_condition[1:])
+                f.u.values[1:] = u
+                f.step(f.u.values)
+                if (t + 1) % 25 == 0:
+                    tr.append(np.copy(f.x.values))
+            trajs.append(np.array(tr)), ulast.append(np.copy(f.u.values))
+            f.u.values = np.copy(f.u.initial_condition)
+        g[f"lqr_traj_xcg{k}"], g[f"lqr_u_last_xcg{k}"] = np.array(trajs), np.array(ulast)
+        f.reset()
+    for k in libs:
+        if not clr_reads_zero(libs[k]):
+            raise SystemExit("_CLr stopped reading ~0 during the run: run the script again")
+    np.savez_compressed(os.path.join(OUT, "g17_input_schedules.npz"), **g)
+    print("g17_input_schedules.npz", os.path.getsize(os.path.join(OUT, "g17_input_schedules.npz")))
+
+
 if __name__ == "__main__":
-    if "--g2r" in sys.argv:
+    if "--g17" in sys.argv:
+        g17_input_schedules()
+    elif "--g2r" in sys.argv:
         g2r_ref_rebuilt()
     elif "--g14" in sys.argv:
         g14_dynamic_lqr()
