@@ -24,6 +24,7 @@
 #include "f16_plant.hpp"
 #include "f16_smallmat.hpp"
 #include "f16_mpc.hpp"
+#include "f16_mpc_model.hpp"
 #include "f16_mpc_state.hpp"
 
 namespace f16 {
@@ -125,12 +126,6 @@ __global__ __launch_bounds__(BLOCK) void k_linearise_full(LinArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------ small LDS allocator
-struct Bump {
-  double *p;
-  __device__ double *take(int n) { double *r = p; p += (n + 1) & ~1; return r; }
-};
-
 __device__ __forceinline__ void load_soa(double *dst, const double *src, int n, long ld, long b) {
   for (int e = lane_id(); e < n; e += F16_WAVE) dst[e] = src[e * ld + b];
   __syncthreads();
@@ -139,54 +134,7 @@ __device__ __forceinline__ void store_soa(double *dst, const double *src, int n,
   for (int e = lane_id(); e < n; e += F16_WAVE) dst[e * ld + b] = src[e];
 }
 
-// ------------------------------------------------------------------------------------ c2d (ZOH)
-// exp([[A,B],[0,0]] h) = [[E,F],[0,I]]: only the top 9x12 block [E F] is propagated.
-// Scaling-and-squaring Taylor: X = A h/2^s, Y = B h/2^s, T_1 = [X Y], T_{k+1} = X T_k/(k+1), 13 terms
-// (||X|| <= 0.5 => truncation < 1e-15 relative), then s squarings [E F] <- E [E F] + [0 F].
-template <int NS, int NI>
-__device__ void c2d_wave(const double *A, const double *Bm, double h, double *Ad, double *Bd, double *scr) {
-  constexpr int NW = NS + NI, NE = NS * NW;
-  Bump al{scr};
-  double *X = al.take(NS * NS), *T = al.take(NE), *Tn = al.take(NE), *EF = al.take(NE);
-  const int l = lane_id();
-  double rs = 0.0;
-  if (l < NS) {
-    for (int j = 0; j < NS; ++j) rs += fabs(A[l * NS + j]);
-    for (int j = 0; j < NI; ++j) rs += fabs(Bm[l * NI + j]);
-    rs *= fabs(h);
-  }
-  const double nrm = wave_max(rs);
-  int s = 0;
-  if (nrm > 0.5) s = min(40, (int)ceil(log2(nrm / 0.5)));
-  const double sc = ldexp(h, -s);
-  for (int e = l; e < NS * NS; e += F16_WAVE) X[e] = A[e] * sc;
-  for (int e = l; e < NE; e += F16_WAVE) {
-    const int i = e / NW, j = e - i * NW;
-    const double v = j < NS ? A[i * NS + j] * sc : Bm[i * NI + (j - NS)] * sc;
-    T[e] = v;
-    EF[e] = v + (j == i ? 1.0 : 0.0);
-  }
-  __syncthreads();
-  for (int k = 2; k <= 13; ++k) {
-    mm<false, false>(Tn, X, T, NS, NS, NW, 1.0 / k);
-    for (int e = l; e < NE; e += F16_WAVE) { T[e] = Tn[e]; EF[e] += Tn[e]; }
-    __syncthreads();
-  }
-  for (int q = 0; q < s; ++q) {
-    for (int e = l; e < NS * NS; e += F16_WAVE) X[e] = EF[(e / NS) * NW + (e % NS)];   // E
-    __syncthreads();
-    mm<false, false>(Tn, X, EF, NS, NS, NW);
-    for (int e = l; e < NE; e += F16_WAVE) {
-      const int j = e % NW;
-      EF[e] = Tn[e] + (j >= NS ? EF[e] : 0.0);
-    }
-    __syncthreads();
-  }
-  for (int e = l; e < NS * NS; e += F16_WAVE) Ad[e] = EF[(e / NS) * NW + (e % NS)];
-  for (int e = l; e < NS * NI; e += F16_WAVE) Bd[e] = EF[(e / NI) * NW + NS + (e % NI)];
-  __syncthreads();
-}
-
+// ------------------------------------------------------------------------------------ c2d (ZOH): c2d_wave, f16_mpc_model.hpp
 struct C2dArgs { const double *Ac, *Bc; double *Ad, *Bd; long B, ld; double dt; };
 
 template <int NS, int NI>
@@ -206,188 +154,7 @@ __global__ __launch_bounds__(64) void k_c2d(C2dArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------ DARE / dlqr
-// DARE  X = A'XA - A'XB (R+B'XB)^-1 B'XA + Q  by the structure-preserving doubling algorithm (SDA):
-//   A0 = A, G0 = B R^-1 B', H0 = Q;  W = (I + G H)^-1;  A+ = A W A;  G+ = G + A W G A';  H+ = H + A' H W A.
-// H_k -> X quadratically (21 doublings at the reference's trim point; scipy.linalg.solve_discrete_are's
-// answer is reproduced to ~1e-11 relative).  R = I here (env.py:354, :405-407).
-//
-// Mapping: one wavefront per aircraft, every 9x9 operand lives in REGISTERS as a zero-padded 16x16 tile in the
-// accumulator layout of v_mfma_f64_16x16x4_f64 (register q of lane l holds element (4q + l/16, l%16); rows 12..15 are
-// padding and never stored), and every product is three chained MFMAs with no data movement at all, because
-//   * the B operand of k-step s (lane l -> B[4s + l/16][l%16]) IS register s of the right factor's tile, and
-//   * the A operand of k-step s (lane l -> A[l%16][4s + l/16]) IS register s of the tile of the left factor's TRANSPOSE,
-// so the iteration carries A and A' (G, H are symmetric) and forms each intermediate in the orientation its consumer
-// needs: 9 products = 27 MFMAs per doubling.  W = (I + G H)^-1 is a register-resident Gauss-Jordan (inverse9_tile).
-typedef double d4_t __attribute__((ext_vector_type(4)));
-constexpr int DARE_SCRATCH = 9 * 18 + 16;
-
-// D = C + L R, the left factor given as the tile of L'
-__device__ __forceinline__ d4_t mm16(const d4_t &Lt, const d4_t &R, d4_t C) {
-  C = __builtin_amdgcn_mfma_f64_16x16x4f64(Lt[0], R[0], C, 0, 0, 0);
-  C = __builtin_amdgcn_mfma_f64_16x16x4f64(Lt[1], R[1], C, 0, 0, 0);
-  C = __builtin_amdgcn_mfma_f64_16x16x4f64(Lt[2], R[2], C, 0, 0, 0);
-  return C;
-}
-// tile of the row-major 9x9 LDS matrix M (or of its transpose)
-__device__ __forceinline__ d4_t tile9(const double *M, bool transpose) {
-  const int l = lane_id(), lc = l & 15, lq = l >> 4;
-  d4_t t = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int r = 4 * q + lq;
-    if (r < 9 && lc < 9) t[q] = transpose ? M[lc * 9 + r] : M[r * 9 + lc];
-  }
-  return t;
-}
-
-// W <- M^-1 for the 9x9 tile M: Gauss-Jordan with partial pivoting on [M | I] held one COLUMN per lane (lanes 0..17,
-// nine rows in registers).  A pivot step broadcasts the pivot column from its lane (v_readlane -> scalars), so the pivot
-// search and the multipliers are wave-uniform and the step needs no LDS and no barrier; rows are not swapped, the row
-// map is applied when the inverse is written back.  LDS (Wl, 81 doubles) only converts between the two layouts.
-// PIVOT = false: the same elimination in natural order (no search, no row map) -- a third of the instructions.  The
-// caller checks the result (residual of M W - I on the matrix cores) and repeats with PIVOT = true if it is not clean.
-template <bool PIVOT>
-__device__ __forceinline__ bool inverse9_tile(const d4_t &M, d4_t &W, double *Wl) {
-  const int l = lane_id(), lc = l & 15, lq = l >> 4;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int r = 4 * q + lq;
-    if (r < 9 && lc < 9) Wl[r * 9 + lc] = M[q];
-  }
-  __syncthreads();
-  const int j = l < 18 ? l : 17;                       // lanes beyond 17 shadow column 17
-  double r[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r[i] = j < 9 ? Wl[i * 9 + j] : (i == j - 9 ? 1.0 : 0.0);
-  unsigned done = 0;
-  int pinv[9];                                         // pinv[i] = the pivot step that used row i
-  bool ok = true;
-#pragma unroll
-  for (int p = 0; p < 9; ++p) {
-    double c[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) c[i] = readlane_f64(r[i], p);
-    if (PIVOT) {
-      int piv = 0;
-      double best = -1.0, cp = 1.0;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        const double v = ((done >> i) & 1u) ? -1.0 : fabs(c[i]);
-        const bool gt = v > best;
-        best = gt ? v : best; piv = gt ? i : piv; cp = gt ? c[i] : cp;
-      }
-      ok = ok && best > 0.0;
-      done |= 1u << piv;
-      double rp = r[0];
-#pragma unroll
-      for (int i = 1; i < 9; ++i) rp = piv == i ? r[i] : rp;
-      rp *= 1.0 / cp;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        r[i] = piv == i ? rp : fma(-c[i], rp, r[i]);
-        pinv[i] = piv == i ? p : (p == 0 ? 0 : pinv[i]);
-      }
-    } else {
-      ok = ok && c[p] != 0.0;
-      const double rp = r[p] * (1.0 / c[p]);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) r[i] = i == p ? rp : fma(-c[i], rp, r[i]);
-    }
-  }
-  if (!PIVOT) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) pinv[i] = i;
-  }
-  __syncthreads();                                     // all reads of Wl are long done; reuse it for the inverse
-  if (l >= 9 && l < 18) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Wl[pinv[i] * 9 + (l - 9)] = r[i];
-  }
-  __syncthreads();
-  W = d4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int rr = 4 * q + lq;
-    if (rr < 9 && lc < 9) W[q] = Wl[rr * 9 + lc];
-  }
-  __syncthreads();
-  return ok;
-}
-
-// Rinv: null = R is the identity (env.py:405-407), else the inverse of the input weight, 3 x 3 row-major (utils.py:219 `dlqr(A, B, Q, R)`)
-__device__ __forceinline__ int dare_sda_wave(const double *A0, const double *Bm, const double *Q, double *X, double *scr, const double *Rinv = nullptr) {
-  const int l = lane_id(), lc = l & 15, lq = l >> 4;
-  const d4_t zero = {0.0, 0.0, 0.0, 0.0};
-  d4_t A = tile9(A0, false), At = tile9(A0, true), H = tile9(Q, false);
-  d4_t G;
-  {
-    d4_t Bt = zero;                                  // tile of B' (3x9): element (k, i) = B[i][k]
-    if (lq < 3 && lc < 9) Bt[0] = Bm[lc * 3 + lq];
-    double br = Bt[0];                               // element (lc, lq) of B R^-1
-    if (Rinv && lq < 3 && lc < 9) br = Bm[lc * 3] * Rinv[lq] + Bm[lc * 3 + 1] * Rinv[3 + lq] + Bm[lc * 3 + 2] * Rinv[6 + lq];
-    G = __builtin_amdgcn_mfma_f64_16x16x4f64(br, Bt[0], zero, 0, 0, 0);        // G0 = B R^-1 B'  (R = I: B B')
-  }
-  d4_t eye = zero;
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-    if (4 * q + lq == lc && lc < 9) eye[q] = 1.0;
-  int it = 0;
-  for (; it < 60; ++it) {
-    const d4_t M = mm16(G, H, eye);                  // I + G H          (G symmetric: its own transpose)
-    const d4_t GAt = mm16(G, At, zero);              // G A'             (independent of W: overlaps the inverse)
-    d4_t W;
-    {
-      // natural-order elimination first; accept it if || M W - I ||_max (M' = I + H G as the left factor) is at the level
-      // cond(M) eps allows -- cond(M) reaches 3e7 late in the iteration, where partial pivoting leaves the same 1e-9 --
-      // otherwise redo with partial pivoting.  Measured on the config-4 models (3,800 inversions): median residual
-      // 1.4e-12, 99th percentile 6e-11, 0.05 % above the threshold; worst unpivoted pivot/column-max ratio 5e-5.
-      bool good = inverse9_tile<false>(M, W, scr);
-      const d4_t Mt = mm16(H, G, eye);
-      d4_t neye = zero;
-#pragma unroll
-      for (int q = 0; q < 3; ++q) neye[q] = -eye[q];
-      const d4_t E = mm16(Mt, W, neye);
-      double emax = fmax(fmax(fabs(E[0]), fabs(E[1])), fabs(E[2]));
-      emax = wave_max(emax);
-      good = good && emax <= 2e-9;
-      if (!good && !inverse9_tile<true>(M, W, scr)) { it = 60; break; }
-    }
-    const d4_t T1t = mm16(W, At, zero);              // (A W)' = W' A'   (left W' <- tile of W)
-    const d4_t HWt = mm16(W, H, zero);               // (H W)' = W' H
-    const d4_t An = mm16(T1t, A, zero);              // A W A            (left A W <- tile of (A W)')
-    const d4_t Atn = mm16(A, T1t, zero);             // (A W A)' = A' (A W)'
-    G = mm16(T1t, GAt, G);                           // G + A W G A'
-    const d4_t HWA = mm16(HWt, A, zero);             // H W A            (left H W <- tile of (H W)')
-    const d4_t dH = mm16(A, HWA, zero);              // A' H W A         (left A' <- tile of A)
-    double dmax = 0.0, hmax = 0.0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      H[q] += dH[q];
-      dmax = fmax(dmax, fabs(dH[q]));
-      hmax = fmax(hmax, fabs(H[q]));
-    }
-    dmax = wave_max(dmax);
-    hmax = wave_max(hmax);
-    A = An; At = Atn;
-    if (dmax <= 1e-16 * hmax) { ++it; break; }
-  }
-  // X = (H + H') / 2 through LDS (the caller wants it there)
-  double *Xt = scr;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int r = 4 * q + lq;
-    if (r < 9 && lc < 9) Xt[r * 9 + lc] = H[q];
-  }
-  __syncthreads();
-  for (int e = l; e < 81; e += F16_WAVE) {
-    const int i = e / 9, j = e - i * 9;
-    X[e] = 0.5 * (Xt[e] + Xt[j * 9 + i]);
-  }
-  __syncthreads();
-  return it;
-}
-
+// ------------------------------------------------------------------------------------ DARE / dlqr: dare_sda_wave, f16_mpc_model.hpp
 // K = (B'XB + R)^-1 (B'XA)  (utils.py:244; Rw: null = R is the identity); scr >= 27+27+9+18+3 (+pad)
 __device__ void lqr_gain_wave(const double *A, const double *Bm, const double *X, double *K, double *scr, const double *Rw = nullptr) {
   Bump al{scr};
@@ -443,7 +210,6 @@ struct RelinArgs {
   unsigned flags;
   MpcProb pb;              // Q, R (custom_q / custom_r); the bounds are not read
 };
-constexpr int C2D_SCRATCH = 81 + 2 + 3 * (9 * 12 + 2);                 // c2d_wave<9, 3>: X | T | Tn | EF (Bump-rounded)
 constexpr int RELIN_SCRATCH = C2D_SCRATCH > DARE_SCRATCH + 90 ? C2D_SCRATCH : DARE_SCRATCH + 90;
 
 // Two waves per SIMD: the out-of-line plant evaluation alone takes 248 registers, so one wave per SIMD is what the kernel gets without
@@ -627,8 +393,7 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
       if (l < 27) Bm[l] = b0;
       __syncthreads();
     }
-    if (a.pb.custom_q) { for (int e = l; e < 81; e += F16_WAVE) Q[e] = a.pb.Q[e]; __syncthreads(); }       // utils.py:21 `Q`
-    else mm<true, false>(Q, Qb, Qb, 9, 9, 9);         // Q = C'C (env.py:389)
+    mpc_model_q(Q, Qb, a, l);                                // Q = C'C (env.py:389) or utils.py:21 `Q`; the model part: f16_mpc_model.hpp
     }
     if (l < 9) {
       const int MX[9] = {3, 4, 7, 8, 9, 10, 11, 17, 16};
@@ -647,32 +412,9 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
     if (!update_only) {
     dare_sda_wave(A, Bm, Q, X, scr, a.pb.custom_r ? a.pb.Rinv : nullptr);
     BSTAMP(1)
-    // (the gain K = -dlqr of utils.py:96 is not needed itself: it only enters through Q_bar)
-    // Q_bar (utils.py:100) solves X = Phi' X Phi + Q + K'RK with Phi = A + B K: for the LQR gain K that equation IS the
-    // DARE, so its solution is the DARE solution X itself.  (Measured on the reference's trim models: SDA's X agrees
-    // with scipy.linalg.solve_discrete_lyapunov's Q_bar to 3e-13 relative -- closer than scipy's own DARE result.)
-    copy(Qb, X, 81);
-    if (exm) {
-      for (int e = l; e < 81; e += F16_WAVE) { exm[e] = A[e]; exm[81 + e] = Q[e]; exm[162 + e] = Qb[e]; }
-    }
+    mpc_model_keep(A, Q, Qb, X, exm, l);                // Qbar = X, and A | Q | Qbar to the workspace
     // ---------------- prediction blocks G_k = A^k B, pred_i = A^(i+1) x (utils.py:171-197 without forming CC/MM)
-    {   // lane e = (r,c) < 27 carries G_k[r][c]; G_(k+1)[r][c] = sum_p A[r][p] G_k[p][c] takes the nine operands from the
-        // lanes (p,c) by ds_bpermute: no LDS round trip + barrier per step of this N-long dependent chain
-      const int e = l < 27 ? l : 0, r = e / 3, c = e - 3 * r;
-      double ar[9], gv = Bm[e];
-#pragma unroll
-      for (int p = 0; p < 9; ++p) ar[p] = A[r * 9 + p];
-      __syncthreads();                         // (Bm aliases pred: read before anything writes there)
-      if (l < 27) G[l] = gv;
-      for (int k = 1; k < N; ++k) {
-        double sacc = 0.0;
-#pragma unroll
-        for (int p = 0; p < 9; ++p) sacc += ar[p] * __shfl(gv, p * 3 + c, 64);
-        gv = sacc;
-        if (l < 27) G[k * 27 + l] = gv;
-      }
-      __syncthreads();
-    }
+    mpc_model_G(A, Bm, G, N, l);
     BSTAMP(2)
     }
     // ---------------- pred_i = A^(i+1) x and q = -2 CC' QQ (x_ref - MM x)   (utils.py:112; f16_mpc_state.hpp: the closed-loop
@@ -680,61 +422,9 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
     mpc_state_vectors(A, Q, Qb, G, x9, xref, pred, wbuf, qv, N);
     BSTAMP(3)
     BSTAMP(4)
-    // ---------------- P = 2 (CC' QQ CC + RR), packed lower, to the workspace.  (A'A is no longer formed here: the solvers
-    // need the row-WEIGHTED Gram A'WA of the equilibrated problem, which has no Toeplitz recursion, and build it themselves.)
-    // Block (j,l), j >= l, d = j-l:  T(j,l) = TQ(j,l) + G'_{N-1-j} Qbar G_{N-1-l},
-    //   TQ(j,l) = TQ(j+1,l+1) + G'_{N-2-j} Q G_{N-2-l} (0 beyond N-2).
-    // One chain per (diagonal d, element (ra,cb)), up to MAXCH per lane; all chains walk j together, so the two weighted
-    // blocks a step needs (Q G_{N-2-j}, Qbar G_{N-1-j}) are the same for every lane and are formed once per step (jit).
-    // This loop is LDS-bandwidth-bound (42 operand reads for 24 FMAs per chain element).  Tried and dropped: one lane per
-    // block diagonal (216 FMAs for 27 + 72 reads per step, running sums in registers, no jit broadcast conflicts) --
-    // fewer LDS bytes but only N active lanes and as many address computations for the packed stores: 20 % slower.
+    // ---------------- P = 2 (CC' QQ CC + RR), packed lower, to the workspace (mpc_model_P, f16_mpc_model.hpp)
     double *Pg = a.Ppk + (size_t)b * np;
-    if (!update_only) {
-      constexpr int MAXCH = (9 * (BIG ? BIG_MAXN : MAXN) + F16_WAVE - 1) / F16_WAVE;
-      double tq[MAXCH];
-#pragma unroll
-      for (int t = 0; t < MAXCH; ++t) tq[t] = 0.0;
-      const int wh = l >= 27 ? 1 : 0, je = l - 27 * wh, jr = je / 3, jc = je - 3 * jr;      // jit roles of lanes 0..53
-      const double *Qw = wh ? Qb : Q;
-      __syncthreads();
-      for (int j = N - 1; j >= 0; --j) {
-        const int kq = wh ? N - 1 - j : N - 2 - j;
-        if (l < 54 && kq >= 0) {
-          double sj = 0.0;
-#pragma unroll
-          for (int p = 0; p < 9; ++p) sj += Qw[jr * 9 + p] * G[kq * 27 + p * 3 + jc];
-          jit[l] = sj;
-        }
-        __syncthreads();
-        const double *QGk = jit, *QbGk = jit + 27;
-#pragma unroll
-        for (int t = 0; t < MAXCH; ++t) {
-          const int ch = l + F16_WAVE * t, d = ch / 9, ee = ch - 9 * d, ra = ee / 3, cb = ee - 3 * ra;
-          __builtin_amdgcn_sched_barrier(0);      // one chain at a time: bounds the live operands (two waves per SIMD)
-          if (ch < 9 * N && j >= d) {
-            const int lcol = j - d;
-            if (j <= N - 2) {
-              double s = 0.0;
-#pragma unroll
-              for (int p = 0; p < 9; ++p) s += QGk[p * 3 + ra] * G[(N - 2 - lcol) * 27 + p * 3 + cb];
-              tq[t] += s;
-            }
-            double gc[9];
-#pragma unroll
-            for (int p = 0; p < 9; ++p) gc[p] = G[(N - 1 - lcol) * 27 + p * 3 + cb];
-            double sb = 0.0;
-#pragma unroll
-            for (int p = 0; p < 9; ++p) sb += QbGk[p * 3 + ra] * gc[p];
-            const int gi = 3 * j + ra, gj = 3 * lcol + cb;
-            // RR = blkdiag(R, ..., R) (utils.py:108-111); R = I (env.py:405-407) unless the caller gave one
-            const double rr_ = a.pb.custom_r ? (d == 0 ? a.pb.R[ra * 3 + cb] : 0.0) : ((gi == gj) ? 1.0 : 0.0);
-            if (gi >= gj) Pg[tri(gi, gj)] = 2.0 * (tq[t] + sb + rr_);
-          }
-        }
-        __syncthreads();                                                    // jit is rewritten by the next step
-      }
-    }
+    if (!update_only) mpc_model_P<(9 * (BIG ? BIG_MAXN : MAXN) + F16_WAVE - 1) / F16_WAVE>(Q, Qb, G, jit, Pg, N, a, l);
     BSTAMP(5)
     // ---------------- bounds of the kept rows (utils.py:129-152): [6N state | 3N command | 3N rate]
     RowVec<BIG> lo, hi, z, y, dy, Eo, eqf;
@@ -1483,6 +1173,8 @@ struct f16_mpc_plan {
   bool have_order;
   void *last_stream;   // the stream of the creation / the last solve: what f16_mpc_plan_destroy waits for
   void *roll_sync;     // f16_rollout_mpc: ticket counter + per-aircraft progress counters (allocated by its first call)
+  double *relin_w;     // f16_rollout_mpc_relin: Q[81] | R[9] | Rinv[9] of the plan's weights on the device (allocated by its first call)
+  bool relin_model;    // the model blocks were overwritten by f16_rollout_mpc_relin: no frozen-model call may read them any more
   MpcArgs a;
 };
 
@@ -1510,7 +1202,7 @@ extern "C" int f16_mpc_plan_create_w(f16_ctx *ctx, f16_mpc_plan **plan, const do
   f16_mpc_plan *p = new f16_mpc_plan();
   p->ctx = ctx; p->B = B; p->ld = ld; p->N = hzn; p->dt = dt;
   p->warm = nullptr; p->warm_on = false; p->have_prev = false; p->sched = nullptr; p->have_order = false; p->last_stream = stream;
-  p->roll_sync = nullptr;
+  p->roll_sync = nullptr; p->relin_w = nullptr; p->relin_model = false;
   if (s) p->s = *s; else f16_qp_default_settings(&p->s);
   if (p->s.check_every < 1 || p->s.rho_every < 1 || !(p->s.rho >= 0) || !(p->s.sigma > 0) || p->s.max_iter < 1 || p->s.scaling < 0 ||
       p->s.scaling > 100 || (p->s.scaling > 0 && !(p->s.rho > 0)) || (p->s.adaptive_rho && p->s.rho_every % p->s.check_every != 0)) {
@@ -1554,6 +1246,7 @@ extern "C" int f16_mpc_plan_solve(f16_mpc_plan *p, const double *x, const double
 extern "C" int f16_mpc_plan_solve_w(f16_mpc_plan *p, const double *x, const double *dem, const double *x_ref, double *u_cmd,
                                     double *u_seq, double *info, int32_t *status, void *stream) {
   if (!p || !x || (!dem && !x_ref) || !u_cmd) return set_error(F16_EINVAL, "bad argument to f16_mpc_plan_solve");
+  if (p->relin_model) return set_error(F16_EINVAL, "f16_mpc_plan_solve: f16_rollout_mpc_relin overwrote this plan's model; create a new plan for the frozen model");
   MpcArgs a = p->a;
   a.x = x; a.dem = dem; a.xref = x_ref; a.ucmd = u_cmd; a.useq = u_seq; a.info = info; a.status = status;
   p->last_stream = stream;
@@ -1582,6 +1275,7 @@ extern "C" int f16_rollout_mpc(f16_mpc_plan *p, double *x, double *u, const doub
                                int32_t *iters_traj, int32_t *status, int nsteps, int traj_every, double xcg, int fi_flag,
                                unsigned flags, void *stream) {
   if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc");
+  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc: f16_rollout_mpc_relin overwrote this plan's model; create a new plan for the frozen model");
   if (p->N > WAVE_MAXN || p->s.scaling <= 0)
     return set_error(F16_EINVAL, "f16_rollout_mpc needs a plan with hzn <= 30 and equilibrated solves (scaling > 0); "
                                  "other plans run the host loop (f16_mpc_plan_solve + f16_rollout per step)");
@@ -1597,6 +1291,42 @@ extern "C" int f16_rollout_mpc(f16_mpc_plan *p, double *x, double *u, const doub
   c.sync = p->roll_sync; c.T = nsteps; c.every = traj ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
   c.warm = p->warm_on ? p->warm : nullptr;
   c.warm_load = p->warm_on && p->have_prev;
+  const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
+  if (!rc) p->have_prev = p->warm_on;
+  return rc;
+}
+
+// The closed loop with the model re-derived at every step (k_rollout_mpc<true>, f16_mpc_wave.hip): f16_rollout_mpc's launch with the
+// linearisation step, the model record and the weights the in-kernel QP build reads from memory.
+extern "C" int f16_rollout_mpc_relin(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                                     int32_t *iters_traj, double *model_traj, int32_t *status, int nsteps, int traj_every, double eps,
+                                     double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin");
+  if (p->N > WAVE_MAXN || p->s.scaling <= 0)
+    return set_error(F16_EINVAL, "f16_rollout_mpc_relin needs a plan with hzn <= 30 and equilibrated solves (scaling > 0); "
+                                 "other plans run the host loop (linearise + f16_mpc_batch + f16_rollout per step)");
+  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin: the linearisation step eps must be > 0");
+  if (nsteps < 0 || ((traj || model_traj) && (traj_every < 1 || nsteps % traj_every != 0)))
+    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj or model_traj is given");
+  if (nsteps == 0) return F16_OK;
+  if (!p->roll_sync) {
+    if (int rc = hip_check(hipMalloc(&p->roll_sync, 8 + (size_t)p->B * sizeof(int32_t)), "hipMalloc f16_rollout_mpc counters")) return rc;
+  }
+  if (!p->relin_w) {
+    if (int rc = hip_check(hipMalloc(&p->relin_w, 99 * sizeof(double)), "hipMalloc f16_rollout_mpc_relin weights")) return rc;
+    double h[99];
+    for (int i = 0; i < 81; ++i) h[i] = p->a.pb.Q[i];
+    for (int i = 0; i < 9; ++i) { h[81 + i] = p->a.pb.R[i]; h[90 + i] = p->a.pb.Rinv[i]; }
+    if (int rc = hip_check(hipMemcpy(p->relin_w, h, sizeof(h), hipMemcpyHostToDevice), "f16_rollout_mpc_relin weights")) return rc;
+  }
+  p->last_stream = stream;
+  p->relin_model = true;
+  RolloutMpcCall c{};
+  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
+  c.sync = p->roll_sync; c.T = nsteps; c.every = (traj || model_traj) ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  c.warm = p->warm_on ? p->warm : nullptr;
+  c.warm_load = p->warm_on && p->have_prev;
+  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.wq = p->relin_w;
   const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
   if (!rc) p->have_prev = p->warm_on;
   return rc;
@@ -1621,6 +1351,7 @@ extern "C" void f16_mpc_plan_destroy(f16_mpc_plan *p) {
   if (p->sched) (void)hipFree(p->sched);
   if (p->warm) (void)hipFree(p->warm);
   if (p->roll_sync) (void)hipFree(p->roll_sync);
+  if (p->relin_w) (void)hipFree(p->relin_w);
   delete p;
 }
 

@@ -134,6 +134,10 @@ struct RolloutMpcCall {
   double xcg;
   int fi;
   unsigned flags;
+  int relin;                  // f16_rollout_mpc_relin: re-derive the model at every step, at (x, u[1:4]) with the step `eps`
+  double eps;
+  double *model_traj;         // relin: [T / every][189][ld] Ad | Bd | Cd of every stored step, or null
+  const double *wq;           // relin: the plan's weights on the device, Q[81] | R[9] | Rinv[9]
 };
 int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall &c, void *stream);
 

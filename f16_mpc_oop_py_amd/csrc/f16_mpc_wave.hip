@@ -22,6 +22,8 @@
 //   k_mpc_wave      one calc_MPC_action per aircraft (f16_mpc_batch / f16_mpc_plan_solve), aircraft from a work queue
 //   k_rollout_mpc   the reference's closed MPC loop test_env.py:480-495 as ONE launch (f16_rollout_mpc, round 5): (step, aircraft)
 //                   pairs from a ticket counter, per pair the state-dependent QP vectors, the solve, the command, one Euler step
+//   k_rollout_mpc<true>   the same loop with the model re-derived at every step (f16_rollout_mpc_relin): per pair, in front of the
+//                   above, linearise at the current point -> ZOH -> the model part of the QP (pair_model)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -29,6 +31,7 @@
 #include <type_traits>
 
 #include "f16_mpc.hpp"
+#include "f16_mpc_model.hpp"
 #include "f16_mpc_state.hpp"
 #include "f16_plant.hpp"
 #include "f16_smallmat.hpp"
@@ -1743,6 +1746,108 @@ __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
   __syncthreads();
 }
 
+// ---- The re-linearising loop (f16_rollout_mpc_relin; SURVEY 8(f)-2: `_calc_MPC_action(..., relinearise=True)` at every step).  One more
+// out-of-line stage in front of pair_prepare: the model of THIS step, derived at the point f16_linearise_batch / build_ssr() take
+// (x.values with u.values[1:4] in place of the actuator states, env.py:175-177), and everything of the QP that depends on the model
+// only, written into the aircraft's own blocks of the plan's workspace (A | Q | Qbar, G, packed P) -- where pair_prepare and
+// solve_aircraft pick it up exactly as they pick up a frozen plan's.  The pieces are the ones k_rollout_lqr_relin and k_mpc<true> run
+// (f16_plant.hpp: xdot_na_exact; f16_mpc_model.hpp: c2d_wave, dare_sda_wave, mpc_model_*), so f16_mpc_batch_w on the stored model
+// builds the same QP bit for bit.  Scratch: the solver's LDS block, idle between two solves:
+constexpr int RM_F = 0, RM_A = RM_F + 13 * 9 + 1, RM_B = RM_A + 82, RM_C = RM_B + 28, RM_AD = RM_C + 82, RM_BD = RM_AD + 82, RM_Q = RM_BD + 28,
+              RM_QB = RM_Q + 82, RM_X = RM_QB + 82, RM_JIT = RM_X + 82, RM_CD = RM_JIT + 54, RM_SCR = RM_CD + 10,
+              RM_SCR_SIZE = ((C2D_SCRATCH > DARE_SCRATCH ? C2D_SCRATCH : DARE_SCRATCH) + 1) & ~1, RM_G = RM_SCR + RM_SCR_SIZE,
+              RM_END = RM_G + 27 * WN;                 // 1,954 doubles of 5,120
+static_assert(RM_END <= LDS_DOUBLES && (RM_A & 1) == 0 && (RM_B & 1) == 0 && (RM_C & 1) == 0 && (RM_AD & 1) == 0 && (RM_BD & 1) == 0 &&
+              (RM_Q & 1) == 0 && (RM_QB & 1) == 0 && (RM_X & 1) == 0 && (RM_JIT & 1) == 0 && (RM_CD & 1) == 0 && (RM_SCR & 1) == 0 &&
+              (RM_G & 1) == 0, "model-stage scratch of the re-linearising rollout kernel");
+constexpr int MODEL_ROWS = 189;                        // a model_traj record: Ad (81) | Bd (27) | Cd (81), row-major
+struct ModelIO {
+  double *Pg;                    // this aircraft's packed P in the plan's workspace
+  double *model;                 // column b of this step's model_traj record, or null (step not stored / no model_traj)
+  struct { const double *Q, *R, *Rinv; int custom_q, custom_r; } pb;      // the plan's weights (device copies of MpcProb's Q, R, Rinv)
+  double eps;
+};
+
+// The finiteness test comes first and covers EVERYTHING the plant evaluation reads (all eighteen states and u[1:4]; pair_prepare
+// tests what the QP reads): the table lookup has no answer for a NaN input.  Returns the code pair_prepare would (which then runs only
+// for PAIR_SOLVE and finds the same); a pair without a solve stores NaN in its model record.
+__device__ __noinline__ int pair_model(PairIO *io, const ModelIO *mo) {
+  const int l = threadIdx.x;
+  const long ld = io->ld, b = io->b;
+  const int N = __builtin_amdgcn_readfirstlane(io->N), n = 3 * N;
+  const double *xg = io->x, *ug = io->u, *dg = io->dem;
+  double x[18], u3[3];
+#pragma unroll
+  for (int i = 0; i < 18; ++i) x[i] = xg[i * ld + b];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) u3[c] = ug[(1 + c) * ld + b];
+  int stw = io->status ? io->status[b] : 0;
+  if (!(stw & ST_ENVELOPE) && !(io->flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) stw |= ST_ENVELOPE | envelope_state_bits(x);
+  int code = PAIR_SOLVE;
+  if (uniform_flag((stw & ST_ENVELOPE) != 0)) code = PAIR_FROZEN;
+  else {
+    bool fin = true;
+#pragma unroll
+    for (int i = 0; i < 18; ++i) fin = fin && isfinite(x[i]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) fin = fin && isfinite(u3[c]) && isfinite(dg[c * ld + b]);
+    if (!uniform_flag(fin)) { code = PAIR_NONFINITE; stw |= ST_NONFINITE; }
+  }
+  double *const mt = mo->model;
+  if (code != PAIR_SOLVE) {
+    if (mt) { for (int e = l; e < MODEL_ROWS; e += 64) mt[e * ld] = NAN; }
+    io->stw = stw;
+    return code;
+  }
+  double *F = s_w + RM_F, *A = s_w + RM_A, *Bm = s_w + RM_B, *Cm = s_w + RM_C, *Ad = s_w + RM_AD, *Bd = s_w + RM_BD, *Q = s_w + RM_Q,
+         *Qb = s_w + RM_QB, *X = s_w + RM_X, *jit = s_w + RM_JIT, *cd = s_w + RM_CD, *scr = s_w + RM_SCR, *G = s_w + RM_G;
+  const double eps = mo->eps;
+  wave_lds_sync();
+  // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps).  Lane l < 12: column
+  // l (mpc_x_idx = [3,4,7,8,9,10,11,17,16], inputs -> [13,14,15]); lane 12: the base point.  As k_rollout_lqr_relin.
+  if (l < 13) {
+    const int idx = l == 0 ? 3 : l == 1 ? 4 : l == 2 ? 7 : l == 3 ? 8 : l == 4 ? 9 : l == 5 ? 10 : l == 6 ? 11
+                  : l == 7 ? 17 : l == 8 ? 16 : l < 12 ? 13 + (l - 9) : -1;
+    double sv[18], f[9];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) sv[k] = x[k];
+    sv[13] = u3[0]; sv[14] = u3[1]; sv[15] = u3[2];      // env.py:175-177
+    double base = 0.0, pert = 0.0;
+#pragma unroll
+    for (int k = 0; k < 18; ++k)
+      if (k == idx) { base = sv[k]; pert = sv[k] + eps; sv[k] = pert; }
+    int sl = 0;      // (the grid bits of the perturbed points are not the aircraft's: build_ssr does not keep them)
+    xdot_na_exact(io->tab, io->lofi, sv, f, io->xcg, io->fi, io->flags, &sl);
+#pragma unroll
+    for (int r = 0; r < 9; ++r) F[l * 9 + r] = f[r];
+    if (l < 9) cd[l] = (pert - base) / eps;
+  }
+  __syncthreads();
+  for (int e = l; e < 108; e += 64) {
+    if (e < 81) { const int r = e / 9, c = e - r * 9; A[e] = (F[c * 9 + r] - F[12 * 9 + r]) / eps; }
+    else { const int e2 = e - 81, r = e2 / 3, c = e2 - r * 3; Bm[e2] = (F[(9 + c) * 9 + r] - F[12 * 9 + r]) / eps; }
+  }
+  for (int e = l; e < 81; e += 64) { const int i = e / 9, j = e - i * 9; Cm[e] = i == j ? cd[i] : 0.0; }
+  __syncthreads();
+  c2d_wave<9, 3>(A, Bm, io->dt, Ad, Bd, scr);                                           // f16_c2d_batch
+  if (mt) {
+    for (int e = l; e < MODEL_ROWS; e += 64) mt[e * ld] = e < 81 ? Ad[e] : (e < 108 ? Bd[e - 81] : Cm[e - 108]);
+  }
+  // the model part of the QP, as k_mpc<true> builds it (f16_mpc_model.hpp).  A DARE that has not converged after 60 doublings is
+  // not flagged: f16_mpc_batch_w goes on with the last iterate too.
+  double *const exw = io->exw;
+  mpc_model_q(Q, Cm, *mo, l);
+  dare_sda_wave(Ad, Bd, Q, X, scr, mo->pb.custom_r ? mo->pb.Rinv : nullptr);
+  mpc_model_keep(Ad, Q, Qb, X, exw + mpc_ext_model(N), l);
+  mpc_model_G(Ad, Bd, G, N, l);
+  for (int e = l; e < 27 * N; e += 64) exw[n + e] = G[e];
+  mpc_model_P<(9 * WN + 63) / 64>(Q, Qb, G, jit, mo->Pg, N, *mo, l);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  io->stw = stw;
+  return code;
+}
+
 // Bring-up aid (-DF16_DBG_MARK; tools/gpu_fused_marks.py): phase markers as system-scope stores into the first words of cmd_traj, readable
 // by a copy on ANOTHER stream while the kernel runs -- how a kernel that never returns is located.  Compiled out of the product.
 #ifdef F16_DBG_PAIRSTAMP   // measurement build: cycles per phase of a pair, summed over every pair of the launch -> eight words BEHIND the command record
@@ -1755,7 +1860,18 @@ __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
 #else
 #define DBGM(i, v)
 #endif
-__global__ __launch_bounds__(64, 1) void k_rollout_mpc(RollMpcArgs ra) {
+// (RELIN: the re-linearising loop f16_rollout_mpc_relin, an instantiation of its own; k_rollout_mpc<false> is the frozen loop)
+struct RollRelinArgs {
+  RollMpcArgs r;
+  double *model_traj;            // [T / every][189][ld] or null
+  const double *wq;              // Q[81] | R[9] | Rinv[9] of the plan's weights (device)
+  double eps;
+};
+__device__ __forceinline__ const RollMpcArgs &rollout_args(const RollMpcArgs &k) { return k; }
+__device__ __forceinline__ const RollMpcArgs &rollout_args(const RollRelinArgs &k) { return k.r; }
+template <bool RELIN>
+__global__ __launch_bounds__(64, 1) void k_rollout_mpc(typename std::conditional<RELIN, RollRelinArgs, RollMpcArgs>::type kargs) {
+  const RollMpcArgs &ra = rollout_args(kargs);
   const MpcArgs &a = ra.m;
   const int N = a.N;
   const Role R = role(N);
@@ -1797,7 +1913,17 @@ __global__ __launch_bounds__(64, 1) void k_rollout_mpc(RollMpcArgs ra) {
     io.ld = a.ld; io.b = b; io.t = t; io.N = N; io.every = ra.every; io.fi = ra.fi; io.flags = ra.flags; io.xcg = ra.xcg; io.dt = a.dt;
     io.cmd[0] = NAN; io.cmd[1] = NAN; io.cmd[2] = NAN; io.iters = 0; io.stw = 0; io.stall = stall;
     DBGM(1, 2000 + t)
-    const int code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
+    int code;
+    if constexpr (RELIN) {
+      ModelIO mo;
+      mo.Pg = a.Ppk + (size_t)b * (size_t)(3 * N * (3 * N + 1) / 2);
+      mo.model = (kargs.model_traj && (t + 1) % ra.every == 0) ? kargs.model_traj + (size_t)((t + 1) / ra.every - 1) * MODEL_ROWS * a.ld + b : nullptr;
+      mo.pb.Q = kargs.wq; mo.pb.R = kargs.wq + 81; mo.pb.Rinv = kargs.wq + 90; mo.pb.custom_q = a.pb.custom_q; mo.pb.custom_r = a.pb.custom_r; mo.eps = kargs.eps;
+      code = __builtin_amdgcn_readfirstlane(pair_model(&io, &mo));
+      if (code == PAIR_SOLVE) code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
+    } else {
+      code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
+    }
     DBGM(2, 3000 + code)
     PSTAMP(3)
     if (code == PAIR_SOLVE) {
@@ -1835,7 +1961,6 @@ __global__ __launch_bounds__(64, 1) void k_rollout_mpc(RollMpcArgs ra) {
   }
   DBGM(6, 7000)
 }
-
 }  // namespace wave
 
 bool mpc_wave_enabled(const MpcArgs &a) {
@@ -1876,7 +2001,7 @@ int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
   return hip_check(hipGetLastError(), "f16_mpc_batch wavefront solve launch");
 }
 
-// f16_rollout_mpc: the closed loop as one launch (k_rollout_mpc).  `sync` = the plan's [8 bytes ticket counter | B x int32 progress].
+// f16_rollout_mpc / f16_rollout_mpc_relin: the closed loop as one launch (k_rollout_mpc<false> / k_rollout_mpc<true>).  `sync` = the plan's [8 bytes ticket counter | B x int32 progress].
 int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall &c, void *stream) {
   if (a.N < 1 || a.N > WAVE_MAXN || !a.gramws || !a.pblk || !a.ext || !a.Ppk) return set_error(F16_EINVAL, "closed-loop MPC rollout needs a plan with 1 <= hzn <= 30");
   if ((unsigned long long)a.B * (unsigned long long)c.T >= 0xffffffffULL) return set_error(F16_EINVAL, "nsteps x B must stay below 2^32 per call");
@@ -1906,7 +2031,13 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   // only wait
   const long slots = cus > 0 ? 4L * cus : 1024;
   const unsigned grid = (unsigned)(a.B < slots ? a.B : slots);
-  hipLaunchKernelGGL(wave::k_rollout_mpc, dim3(grid), dim3(64), 0, (hipStream_t)stream, r);
+  if (c.relin) {      // f16_rollout_mpc_relin: the model of every step is derived inside the pair (pair_model)
+    wave::RollRelinArgs rr{};
+    rr.r = r; rr.model_traj = c.model_traj; rr.wq = c.wq; rr.eps = c.eps;
+    hipLaunchKernelGGL(wave::k_rollout_mpc<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rr);
+    return hip_check(hipGetLastError(), "f16_rollout_mpc_relin launch");
+  }
+  hipLaunchKernelGGL(wave::k_rollout_mpc<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, r);
   return hip_check(hipGetLastError(), "f16_rollout_mpc launch");
 }
 

@@ -145,7 +145,7 @@ def or_status(status):
 
 
 def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, traj_every=1, gather=True, use_plan=True, stats=None,
-                            fused=None, hold_command=False, one_lane=False):
+                            fused=None, hold_command=False, one_lane=False, relinearise=False):
     """BASELINE config 5 / test_env.py:480-495 pattern on this rank's shard, then one all-gather:
     per step  cmd = calc_MPC_action(p,q,r,hzn); u.values[1:] = cmd; step(u.values).
     fused=True: the whole loop of the shard as ONE launch (F16Batch.rollout_MPC / C-ABI f16_rollout_mpc: (step, aircraft) pairs from
@@ -164,6 +164,9 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
     the steps of the LONGEST solve of the step (device-side reductions, read once at the end; the host loop cannot end a step before
     its longest solve) and "flagged_per_step" = per step the number of aircraft whose solve raised F16_ST_QP_INFEASIBLE / QP_MAXITER /
     NONFINITE (host loop only).
+    relinearise: the reduced model is re-derived at every step instead of frozen -- fused: F16Batch.rollout_MPC(...,
+    relinearise=True) (C-ABI f16_rollout_mpc_relin, one launch); host loop: `_calc_MPC_action(relinearise=True)` per step (no plan: the
+    model changes with every call, so use_plan only selects the default path here).
     Returns the collated trajectory [steps//traj_every, 18, B_total] (or the local shard if gather=False)."""
     from . import lib as _lib
     T = steps // traj_every
@@ -171,7 +174,8 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
         plan_ok = getattr(env, "_plan", None) is None or (env._plan_hzn == int(hzn) and getattr(env, "_plan_default_settings", False))
         fused = bool(use_plan) and int(hzn) <= 30 and plan_ok and not one_lane
     if fused:
-        traj, info = env.rollout_MPC(steps, p_dem, q_dem, r_dem, hzn, traj_every=traj_every, return_info=True, hold_command=hold_command)
+        traj, info = env.rollout_MPC(steps, p_dem, q_dem, r_dem, hzn, traj_every=traj_every, return_info=True, hold_command=hold_command,
+                                     **(dict(relinearise=True) if relinearise else {}))
         if stats is not None:
             its = info["iters"].to(torch.float64)
             stats["iters_mean"] = float(its.mean())
@@ -189,7 +193,8 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
         env.flags = env.flags | _lib.F16_FLAG_ONE_LANE
     try:
         for k in range(steps):
-            cmd = env._calc_MPC_action(dem, None, None, hzn, use_plan=use_plan)
+            cmd = env._calc_MPC_action(dem, None, None, hzn, relinearise=True) if relinearise else \
+                env._calc_MPC_action(dem, None, None, hzn, use_plan=use_plan)
             if it_sum is not None:
                 it_sum += env.last_iters.sum()
                 it_max += env.last_iters.max()

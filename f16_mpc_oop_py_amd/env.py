@@ -545,12 +545,24 @@ class F16Batch:
         self._plan_default_settings = int((settings or {}).get("scaling", 10)) > 0       # (what f16_rollout_mpc takes: equilibrated solves)
         if warm_start:      # OSQP's in-object default; the reference starts cold on every call (new object), so: opt-in
             self._check(self.lib.f16_mpc_plan_warm_start(h, 1))
+        self._plan_args = dict(settings=settings, warm_start=warm_start, weights=weights)
+        self._plan_foreign = False      # True once rollout_MPC(relinearise=True) has overwritten the plan's model blocks
         return self
+
+    def _frozen_plan(self, hzn):
+        """The prepared plan of horizon hzn for a frozen-model call: made if absent; prepared AGAIN from self.ssr (same settings, weights
+        and warm-start switch) if the re-linearised loop has run on it -- its model blocks then hold per-step models, and the
+        library refuses it for frozen-model calls."""
+        if getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
+            self.prepare_MPC(hzn)
+        elif getattr(self, "_plan_foreign", False):
+            self.prepare_MPC(hzn, **self._plan_args)
+        return self._plan
 
     def release_MPC_plan(self):
         if getattr(self, "_plan", None) is not None:
             self.lib.f16_mpc_plan_destroy(self._plan)
-        self._plan, self._plan_hzn = None, None
+        self._plan, self._plan_hzn, self._plan_foreign = None, None, False
 
     def __del__(self):
         try:
@@ -619,8 +631,7 @@ class F16Batch:
         if use_plan:
             if relinearise or settings or weights:
                 raise ValueError("a prepared plan fixes the model, the QP settings and the weights (prepare_MPC)")
-            if getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
-                self.prepare_MPC(hzn)
+            self._frozen_plan(hzn)
             xr = self._soa(x_ref, 9) if x_ref is not None else None
             self._check(self.lib.f16_mpc_plan_solve_w(self._plan, _vp(self._x), _vp(dem), _vp(xr), _vp(ucmd), _vp(useq), _vp(info),
                                                       _vp(st), self._stream))
@@ -646,7 +657,8 @@ class F16Batch:
 
     calc_MPC_action = _calc_MPC_action
 
-    def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False):
+    def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False,
+                    relinearise=False, eps=1e-5):
         """The reference's closed MPC loop (test_env.py:480-495; BASELINE config 5) as ONE launch (C-ABI f16_rollout_mpc): per step
         `cmd = _calc_MPC_action(p_dem, q_dem, r_dem, hzn); u.values[1:] = cmd; step(u.values)` from the frozen reduced model
         (env.py:49-60) with OSQP's default settings (every solve cold, as the reference's -- or warm from the step before when the plan was
@@ -655,9 +667,27 @@ class F16Batch:
         call) joins the batch after every solve.  Uses the prepared plan of horizon hzn (prepare_MPC; made here if absent).
         Returns the states after every traj_every-th step [nsteps//k, 18, B] (None without traj_every); with return_info also
         dict(cmd [nsteps, 3, B]: what calc_MPC_action returned per step, iters [nsteps, B]).  x.values / u.values / status are
-        updated in place; u.values ends up holding the last command.  hold_command: F16_FLAG_HOLD_COMMAND."""
-        if getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
+        updated in place; u.values ends up holding the last command.  hold_command: F16_FLAG_HOLD_COMMAND.
+        relinearise=True (C-ABI f16_rollout_mpc_relin): the reduced model is re-derived at EVERY step at the current
+        (x.values, u.values[1:4]) with the forward-difference step eps -- `_calc_MPC_action(..., relinearise=True)` per step, still one
+        launch.  The info dict then also carries model [nsteps//k, 189, B]: Ad (81) | Bd (27) | Cd (81) of the solve of every stored
+        step (NaN where an aircraft was not solved for).  The call takes the plan's weights, bounds and settings but overwrites its
+        model blocks, so the plan is marked: further relinearise=True calls go on using it, while the next frozen-model call
+        (use_plan=True, rollout_MPC without relinearise) prepares it again from self.ssr, which is untouched."""
+        nsteps = int(nsteps)
+        if relinearise:      # (argument checks first: they need no GPU)
+            if not float(eps) > 0.0:
+                raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
+            if int(hzn) < 1 or int(hzn) > 30:
+                raise ValueError(f"relinearise=True runs on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
+            if nsteps < 0 or (traj_every and (int(traj_every) < 1 or nsteps % int(traj_every))):
+                raise ValueError(f"nsteps ({nsteps}) must be >= 0 and a multiple of traj_every ({traj_every})")
+        if not relinearise:
+            self._frozen_plan(hzn)
+        elif getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
             self.prepare_MPC(hzn)
+        if relinearise and not self._plan_default_settings:
+            raise ValueError("relinearise=True needs a plan with equilibrated solves (scaling > 0)")
         dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
         traj = None
         if traj_every:
@@ -666,6 +696,16 @@ class F16Batch:
         cmd = torch.empty((nsteps, 3, self.B), dtype=torch.float64, device=self.device) if return_info else None
         its = torch.empty((nsteps, self.B), dtype=torch.int32, device=self.device) if return_info else None
         flags = self.flags | (_lib.F16_FLAG_HOLD_COMMAND if hold_command else 0)
+        if relinearise:
+            k = int(traj_every or 1)
+            model = torch.empty((nsteps // k, 189, self.B), dtype=torch.float64, device=self.device) if return_info else None
+            self._plan_foreign = nsteps > 0 or self._plan_foreign      # its model blocks are per-step models from here on, not self.ssr
+            self._check(self.lib.f16_rollout_mpc_relin(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
+                                                       _vp(model), _vp(self.status), nsteps, k, float(eps), self.xcg,
+                                                       self.fi_flag, flags, self._stream))
+            if return_info:
+                return traj, dict(cmd=cmd, iters=its, model=model)
+            return traj
         self._check(self.lib.f16_rollout_mpc(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
                                              _vp(self.status), int(nsteps), int(traj_every or 1), self.xcg, self.fi_flag, flags,
                                              self._stream))

@@ -335,6 +335,34 @@ typedef struct f16_mpc_plan f16_mpc_plan;
 int f16_rollout_mpc(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                     int32_t *iters_traj, int32_t *status, int nsteps, int traj_every, double xcg, int fi_flag, unsigned flags,
                     void *stream);
+/* The same closed loop with the model RE-DERIVED AT EVERY STEP (what `_calc_MPC_action(..., relinearise=True)` does when
+ * it is called from a loop), as ONE launch.  Per step, for every aircraft that is neither frozen nor non-finite:
+ *     A, B, C = forward differences of the reduced model at (x, u[1:4]) with the step eps   (the point and the rule of f16_linearise_batch:
+ *                                                                  u.values, not the actuator states; C = diag((x + eps - x) / eps))
+ *     Ad, Bd  = ZOH(A, B, dt)                                                               (f16_c2d_batch)
+ *     cmd     = calc_MPC_action built from (Ad, Bd, C) with the plan's weights, bounds, horizon and settings
+ *     u[1:4]  = cmd;  step(u)                                                               (the F16_FLAG_ONE_LANE step)
+ * Arguments, the in-place x / u, traj, cmd_traj, iters_traj, the sticky status, F16_FLAG_HOLD_COMMAND, F16_FLAG_NO_ENVELOPE, the ticket
+ * scheme and the rules for infeasible and frozen aircraft: as f16_rollout_mpc.  Differences:
+ *   - the finiteness test comes before the linearisation and covers everything the plant evaluation reads: an aircraft with a
+ *     non-finite entry in ANY of its eighteen states, in u[1:4] or in its demands is not linearised and not solved for (NaN command,
+ *     zero iterations, F16_ST_NONFINITE); it still takes its step, as in f16_rollout_mpc.  The table-grid bits of the thirteen
+ *     evaluation points of the linearisation are not kept (as f16_rollout_lqr_relin);
+ *   - model_traj (may be NULL) [nsteps / traj_every][189][ld]: Ad (81) | Bd (27) | Cd (81), row-major, of the solve of every stored
+ *     step (the counterpart of K_traj of f16_rollout_lqr_relin).  A pair without a solve (frozen, non-finite) stores NaN.  With the
+ *     model of step t, the state before that step and the demands, f16_mpc_batch_w returns exactly cmd_traj[t] and iters_traj[t]: the
+ *     loop builds its QP with the build kernel's own code;
+ *   - a DARE that has not converged after 60 doublings is not flagged and its last iterate is the terminal weight: what f16_mpc_batch_w
+ *     does with the same model;
+ *   - eps <= 0 (or NaN) is F16_EINVAL; traj_every applies when traj or model_traj is given.
+ * The plan supplies the workspace, weights, bounds, horizon, settings, the warm-start switch and the counters; the model it was created
+ * from is NOT used, and the call overwrites the plan's per-aircraft model blocks (A | Q | Qbar, G_k, packed P).  Afterwards they hold,
+ * per aircraft, the model of its last solved step, so the plan no longer describes one frozen model: from then on f16_mpc_plan_solve(_w)
+ * and f16_rollout_mpc refuse it (F16_EINVAL); f16_rollout_mpc_relin, f16_mpc_plan_warm_start and f16_mpc_plan_destroy still take it.
+ * Not capturable on its first call on a plan (allocates the counters and a copy of the weights). */
+int f16_rollout_mpc_relin(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                          int32_t *iters_traj, double *model_traj, int32_t *status, int nsteps, int traj_every, double eps,
+                          double xcg, int fi_flag, unsigned flags, void *stream);
 int f16_mpc_plan_create(f16_ctx *ctx, f16_mpc_plan **plan, const double *Ad, const double *Bd, const double *Cd,
                         long B, long ld, int hzn, double dt, const f16_qp_settings *s, void *stream);
 int f16_mpc_plan_solve(f16_mpc_plan *plan, const double *x, const double *dem, double *u_cmd, double *u_seq,
