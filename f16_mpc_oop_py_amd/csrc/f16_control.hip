@@ -14,6 +14,7 @@
 // diagonal recursion over the same blocks (DESIGN.md "QP build").
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+#include <stdio.h>
 #include <math.h>
 
 #include <mutex>
@@ -1271,6 +1272,29 @@ extern "C" int f16_mpc_plan_solve_w(f16_mpc_plan *p, const double *x, const doub
   return F16_OK;
 }
 
+// What the four closed-loop entry points share behind their argument checks: the counters (and, re-linearised, the device copy of
+// the weights) of the plan's first call, the warm-start switch, the launch.  nctrl control steps of `hold` plant steps of `dt` each.
+static int rollout_mpc_common(f16_mpc_plan *p, RolloutMpcCall &c, int nctrl, int hold, double dt, void *stream) {
+  if (!p->roll_sync) {
+    if (int rc = hip_check(hipMalloc(&p->roll_sync, 8 + (size_t)p->B * sizeof(int32_t)), "hipMalloc f16_rollout_mpc counters")) return rc;
+  }
+  if (c.relin && !p->relin_w) {
+    if (int rc = hip_check(hipMalloc(&p->relin_w, 99 * sizeof(double)), "hipMalloc f16_rollout_mpc_relin weights")) return rc;
+    double h[99];
+    for (int i = 0; i < 81; ++i) h[i] = p->a.pb.Q[i];
+    for (int i = 0; i < 9; ++i) { h[81 + i] = p->a.pb.R[i]; h[90 + i] = p->a.pb.Rinv[i]; }
+    if (int rc = hip_check(hipMemcpy(p->relin_w, h, sizeof(h), hipMemcpyHostToDevice), "f16_rollout_mpc_relin weights")) return rc;
+  }
+  p->last_stream = stream;
+  if (c.relin) p->relin_model = true;
+  c.sync = p->roll_sync; c.T = nctrl; c.hold = hold; c.dt = dt; c.wq = p->relin_w;
+  c.warm = p->warm_on ? p->warm : nullptr;
+  c.warm_load = p->warm_on && p->have_prev;
+  const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
+  if (!rc) p->have_prev = p->warm_on;
+  return rc;
+}
+
 extern "C" int f16_rollout_mpc(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                int32_t *iters_traj, int32_t *status, int nsteps, int traj_every, double xcg, int fi_flag,
                                unsigned flags, void *stream) {
@@ -1282,18 +1306,10 @@ extern "C" int f16_rollout_mpc(f16_mpc_plan *p, double *x, double *u, const doub
   if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
     return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj is given");
   if (nsteps == 0) return F16_OK;
-  if (!p->roll_sync) {
-    if (int rc = hip_check(hipMalloc(&p->roll_sync, 8 + (size_t)p->B * sizeof(int32_t)), "hipMalloc f16_rollout_mpc counters")) return rc;
-  }
-  p->last_stream = stream;
   RolloutMpcCall c{};
   c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.sync = p->roll_sync; c.T = nsteps; c.every = traj ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  c.warm = p->warm_on ? p->warm : nullptr;
-  c.warm_load = p->warm_on && p->have_prev;
-  const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
-  if (!rc) p->have_prev = p->warm_on;
-  return rc;
+  c.every = traj ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  return rollout_mpc_common(p, c, nsteps, 1, p->dt, stream);      // (the control period IS the plant step)
 }
 
 // The closed loop with the model re-derived at every step (k_rollout_mpc<true>, f16_mpc_wave.hip): f16_rollout_mpc's launch with the
@@ -1309,27 +1325,62 @@ extern "C" int f16_rollout_mpc_relin(f16_mpc_plan *p, double *x, double *u, cons
   if (nsteps < 0 || ((traj || model_traj) && (traj_every < 1 || nsteps % traj_every != 0)))
     return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj or model_traj is given");
   if (nsteps == 0) return F16_OK;
-  if (!p->roll_sync) {
-    if (int rc = hip_check(hipMalloc(&p->roll_sync, 8 + (size_t)p->B * sizeof(int32_t)), "hipMalloc f16_rollout_mpc counters")) return rc;
-  }
-  if (!p->relin_w) {
-    if (int rc = hip_check(hipMalloc(&p->relin_w, 99 * sizeof(double)), "hipMalloc f16_rollout_mpc_relin weights")) return rc;
-    double h[99];
-    for (int i = 0; i < 81; ++i) h[i] = p->a.pb.Q[i];
-    for (int i = 0; i < 9; ++i) { h[81 + i] = p->a.pb.R[i]; h[90 + i] = p->a.pb.Rinv[i]; }
-    if (int rc = hip_check(hipMemcpy(p->relin_w, h, sizeof(h), hipMemcpyHostToDevice), "f16_rollout_mpc_relin weights")) return rc;
-  }
-  p->last_stream = stream;
-  p->relin_model = true;
   RolloutMpcCall c{};
   c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.sync = p->roll_sync; c.T = nsteps; c.every = (traj || model_traj) ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  c.warm = p->warm_on ? p->warm : nullptr;
-  c.warm_load = p->warm_on && p->have_prev;
-  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.wq = p->relin_w;
-  const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
-  if (!rc) p->have_prev = p->warm_on;
-  return rc;
+  c.every = (traj || model_traj) ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = c.every;
+  return rollout_mpc_common(p, c, nsteps, 1, p->dt, stream);
+}
+
+// The two loops at a control period of `hold` plant steps (pair_finish, f16_mpc_wave.hip): the argument rules they share.
+static int rollout_mpc_hold_check(const char *name, const f16_mpc_plan *p, const void *traj, int nctrl, int hold, int traj_every, double dt) {
+  char msg[256];
+  if (p->N > WAVE_MAXN || p->s.scaling <= 0) {
+    snprintf(msg, sizeof msg, "%s needs a plan with hzn <= 30 and equilibrated solves (scaling > 0)", name);
+    return set_error(F16_EINVAL, msg);
+  }
+  if (nctrl < 1 || hold < 1 || (long long)nctrl * hold > 0x7fffffffLL) {
+    snprintf(msg, sizeof msg, "%s: nctrl and hold must be >= 1 and nctrl x hold < 2^31", name);
+    return set_error(F16_EINVAL, msg);
+  }
+  if (!(fabs((double)hold * dt - p->dt) <= 1e-12 * p->dt)) {
+    snprintf(msg, sizeof msg, "%s: hold x dt (%d x %.17g) is not the plan's dt (%.17g) -- the plan's model and rate rows are "
+             "discretised at the control period", name, hold, dt, p->dt);
+    return set_error(F16_EINVAL, msg);
+  }
+  if (traj && (traj_every < 1 || (long long)nctrl * hold % traj_every != 0)) {
+    snprintf(msg, sizeof msg, "%s: nctrl x hold must be a multiple of traj_every >= 1 when traj is given", name);
+    return set_error(F16_EINVAL, msg);
+  }
+  return F16_OK;
+}
+
+extern "C" int f16_rollout_mpc_hold(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                                    int32_t *iters_traj, int32_t *status, int nctrl, int hold, int traj_every, double dt,
+                                    double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_hold");
+  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc_hold: a re-linearised loop overwrote this plan's model; create a new plan for the frozen model");
+  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_hold", p, traj, nctrl, hold, traj_every, dt)) return rc;
+  RolloutMpcCall c{};
+  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
+  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+}
+
+extern "C" int f16_rollout_mpc_relin_hold(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                                          int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold,
+                                          int traj_every, int model_every, double dt, double eps, double xcg, int fi_flag,
+                                          unsigned flags, void *stream) {
+  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin_hold");
+  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_relin_hold", p, traj, nctrl, hold, traj_every, dt)) return rc;
+  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_hold: the linearisation step eps must be > 0");
+  if (model_every < 1 || (model_traj && nctrl % model_every != 0))
+    return set_error(F16_EINVAL, "f16_rollout_mpc_relin_hold: model_every must be >= 1, and divide nctrl when model_traj is given");
+  RolloutMpcCall c{};
+  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
+  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = model_every;
+  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
 }
 
 extern "C" int f16_mpc_plan_warm_start(f16_mpc_plan *p, int on) {

@@ -130,13 +130,16 @@ struct RolloutMpcCall {
   void *sync;                 // [8 bytes ticket counter | B x int32 progress], zeroed by the launch
   double *warm;               // the plan's warm-start buffer (opt-in), or null: every solve starts cold, as the reference's does
   int warm_load;              // step 0 starts from what the plan's previous call left (later steps always start from the step before)
-  int T, every;
+  int T, every;               // T control steps; a sample after every `every`-th plant step
+  int hold;                   // plant steps per control step (1: f16_rollout_mpc / f16_rollout_mpc_relin)
+  double dt;                  // the plant's Euler step (hold x dt = the plan's dt)
   double xcg;
   int fi;
   unsigned flags;
   int relin;                  // f16_rollout_mpc_relin: re-derive the model at every step, at (x, u[1:4]) with the step `eps`
   double eps;
-  double *model_traj;         // relin: [T / every][189][ld] Ad | Bd | Cd of every stored step, or null
+  double *model_traj;         // relin: [T / model_every][189][ld] Ad | Bd | Cd of every stored control step, or null
+  int model_every;
   const double *wq;           // relin: the plan's weights on the device, Q[81] | R[9] | Rinv[9]
 };
 int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall &c, void *stream);

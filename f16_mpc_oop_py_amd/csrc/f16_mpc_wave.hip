@@ -24,6 +24,8 @@
 //                   pairs from a ticket counter, per pair the state-dependent QP vectors, the solve, the command, one Euler step
 //   k_rollout_mpc<true>   the same loop with the model re-derived at every step (f16_rollout_mpc_relin): per pair, in front of the
 //                   above, linearise at the current point -> ZOH -> the model part of the QP (pair_model)
+//   Both take `hold` Euler steps of the plant's own dt per pair (f16_rollout_mpc_hold / f16_rollout_mpc_relin_hold: a control period
+//   of several plant steps; pair_finish); f16_rollout_mpc / f16_rollout_mpc_relin are the hold = 1 calls of the same two kernels.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -1608,7 +1610,9 @@ struct RollMpcArgs {
   unsigned *queue;               // ticket counter, zero at the launch
   int32_t *progress;             // [B] steps completed per aircraft, zero at the launch
   const double *tab, *lofi;      // table images (global)
-  int T, every;
+  int T, every;                  // T control steps (the tickets' steps); a sample after every `every`-th PLANT step
+  int hold;                      // plant steps per control step (f16_rollout_mpc_hold; 1: the reference's loop)
+  double dtp;                    // the plant's Euler step (hold x dtp = m.dt, the plan's period: checked by the entry point)
   double xcg;
   int fi;
   unsigned flags, stride, total; // total = T x B tickets (< 2^32: checked by the launcher)
@@ -1636,9 +1640,9 @@ struct PairIO {
   const double *tab, *lofi;
   double *exw;                   // this aircraft's extras block of the plan's workspace: q | G | pred | A Q Qbar
   long ld, b;
-  int t, N, every, fi;
+  int t, N, every, fi, hold;     // t: the control step; hold plant steps follow its solve
   unsigned flags;
-  double xcg, dt;
+  double xcg, dt, dtp;           // dt: the plan's period (model, rate rows); dtp: the plant's Euler step
   double cmd[3];                 // what calc_MPC_action returned (NaN: infeasible / not finite / no solve)
   int iters, stw, stall;
 };
@@ -1696,12 +1700,16 @@ __device__ __noinline__ int pair_prepare(PairIO *io) {
 }
 
 // End of a pair: u.values[1:] = cmd (test_env.py:490-493; F16_FLAG_HOLD_COMMAND: a step without a command keeps the previous one),
-// step(u.values) (env.py:126: euler_step_exact, the out-of-line step of the F16_FLAG_ONE_LANE rollout kernel; the table image from
-// global memory), then the stores of the pair: state, command, flags, samples.
+// then `hold` times step(u.values) (env.py:105-130 with the PLANT step io->dtp; env.py:126: euler_step_exact, the out-of-line step of
+// the F16_FLAG_ONE_LANE rollout kernel; the table image from global memory), then the stores of the pair: state, command, flags.  The
+// envelope test of plant step 0 is pair_prepare's; plant steps 1.. test here, as k_rollout_exact does inside a launch: an aircraft found
+// outside is frozen from that plant step on and the rest of its hold is not stepped.  Plant step s = t x hold + j stores its sample
+// when (s + 1) % every == 0 -- a frozen aircraft repeats its state.  hold = 1 is the reference's loop.
 __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
   const int l = threadIdx.x;
   const long ld = io->ld, b = io->b;
   const int t = __builtin_amdgcn_readfirstlane(io->t);
+  const int hold = __builtin_amdgcn_readfirstlane(io->hold), every = __builtin_amdgcn_readfirstlane(io->every);
   const unsigned flags = (unsigned)__builtin_amdgcn_readfirstlane((int)io->flags);
   double *xg = io->x, *ug = io->u;
   double x[18], u[4];
@@ -1716,7 +1724,22 @@ __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       if (!((flags & F16_FLAG_HOLD_COMMAND) && cmd[c] != cmd[c])) u[1 + c] = cmd[c];
-    euler_step_exact(io->tab, io->lofi, x, u, io->dt, io->xcg, __builtin_amdgcn_readfirstlane(io->fi), flags, &stw);
+  }
+  double *const trg = io->traj;
+  int s1 = t * hold + 1;           // (plant steps taken after this one; nctrl x hold < 2^31: checked by the entry point)
+  for (int j = 0; j < hold; ++j, ++s1) {
+    if (live) {
+      if (j > 0 && !(stw & ST_ENVELOPE) && !(flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) stw |= ST_ENVELOPE | envelope_state_bits(x);
+      if (!uniform_flag((stw & ST_ENVELOPE) != 0))
+        euler_step_exact(io->tab, io->lofi, x, u, io->dtp, io->xcg, __builtin_amdgcn_readfirstlane(io->fi), flags, &stw);
+    }
+    if (trg && s1 % every == 0 && l == 0) {
+      double *tr = trg + (size_t)(s1 / every - 1) * 18 * ld + b;
+#pragma unroll
+      for (int i = 0; i < 18; ++i) __builtin_nontemporal_store(x[i], tr + i * ld);
+    }
+  }
+  if (live) {
     bool finx = true;
 #pragma unroll
     for (int i = 0; i < 18; ++i) finx = finx && isfinite(x[i]);
@@ -1730,12 +1753,6 @@ __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
       for (int c = 0; c < 3; ++c) ug[(1 + c) * ld + b] = u[1 + c];
     }
     if (io->status) io->status[b] = stw;
-    const int every = io->every;
-    if (io->traj && (t + 1) % every == 0) {
-      double *tr = io->traj + (size_t)((t + 1) / every - 1) * 18 * ld + b;
-#pragma unroll
-      for (int i = 0; i < 18; ++i) __builtin_nontemporal_store(x[i], tr + i * ld);
-    }
     if (io->cmd_traj) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) io->cmd_traj[((size_t)t * 3 + c) * ld + b] = cmd[c];
@@ -1863,7 +1880,8 @@ __device__ __noinline__ int pair_model(PairIO *io, const ModelIO *mo) {
 // (RELIN: the re-linearising loop f16_rollout_mpc_relin, an instantiation of its own; k_rollout_mpc<false> is the frozen loop)
 struct RollRelinArgs {
   RollMpcArgs r;
-  double *model_traj;            // [T / every][189][ld] or null
+  double *model_traj;            // [T / model_every][189][ld] or null
+  int model_every;               // the model of control step t is stored when (t + 1) % model_every == 0
   const double *wq;              // Q[81] | R[9] | Rinv[9] of the plan's weights (device)
   double eps;
 };
@@ -1911,13 +1929,14 @@ __global__ __launch_bounds__(64, 1) void k_rollout_mpc(typename std::conditional
     io.x = ra.x; io.u = ra.u; io.dem = ra.dem; io.traj = ra.traj; io.cmd_traj = ra.cmd_traj; io.iters_traj = ra.iters_traj;
     io.status = ra.status; io.tab = ra.tab; io.lofi = ra.lofi; io.exw = a.ext + (size_t)b * mpc_ext_doubles(N);
     io.ld = a.ld; io.b = b; io.t = t; io.N = N; io.every = ra.every; io.fi = ra.fi; io.flags = ra.flags; io.xcg = ra.xcg; io.dt = a.dt;
+    io.hold = ra.hold; io.dtp = ra.dtp;
     io.cmd[0] = NAN; io.cmd[1] = NAN; io.cmd[2] = NAN; io.iters = 0; io.stw = 0; io.stall = stall;
     DBGM(1, 2000 + t)
     int code;
     if constexpr (RELIN) {
       ModelIO mo;
       mo.Pg = a.Ppk + (size_t)b * (size_t)(3 * N * (3 * N + 1) / 2);
-      mo.model = (kargs.model_traj && (t + 1) % ra.every == 0) ? kargs.model_traj + (size_t)((t + 1) / ra.every - 1) * MODEL_ROWS * a.ld + b : nullptr;
+      mo.model = (kargs.model_traj && (t + 1) % kargs.model_every == 0) ? kargs.model_traj + (size_t)((t + 1) / kargs.model_every - 1) * MODEL_ROWS * a.ld + b : nullptr;
       mo.pb.Q = kargs.wq; mo.pb.R = kargs.wq + 81; mo.pb.Rinv = kargs.wq + 90; mo.pb.custom_q = a.pb.custom_q; mo.pb.custom_r = a.pb.custom_r; mo.eps = kargs.eps;
       code = __builtin_amdgcn_readfirstlane(pair_model(&io, &mo));
       if (code == PAIR_SOLVE) code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
@@ -2013,7 +2032,7 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   r.queue = reinterpret_cast<unsigned *>(c.sync);
   r.progress = reinterpret_cast<int32_t *>(c.sync) + 2;
   r.tab = ctx->d_tab; r.lofi = ctx->d_lofi;
-  r.T = c.T; r.every = c.every; r.xcg = c.xcg; r.fi = c.fi; r.flags = c.flags;
+  r.T = c.T; r.every = c.every; r.hold = c.hold; r.dtp = c.dt; r.xcg = c.xcg; r.fi = c.fi; r.flags = c.flags;
   r.total = (unsigned)((unsigned long long)a.B * (unsigned long long)c.T);
   r.stride = 0;
   static const bool spread = [] { const char *e = getenv("F16_MPC_SPREAD"); return !(e && e[0] == '0'); }();
@@ -2033,7 +2052,7 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   const unsigned grid = (unsigned)(a.B < slots ? a.B : slots);
   if (c.relin) {      // f16_rollout_mpc_relin: the model of every step is derived inside the pair (pair_model)
     wave::RollRelinArgs rr{};
-    rr.r = r; rr.model_traj = c.model_traj; rr.wq = c.wq; rr.eps = c.eps;
+    rr.r = r; rr.model_traj = c.model_traj; rr.model_every = c.model_every; rr.wq = c.wq; rr.eps = c.eps;
     hipLaunchKernelGGL(wave::k_rollout_mpc<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rr);
     return hip_check(hipGetLastError(), "f16_rollout_mpc_relin launch");
   }

@@ -144,8 +144,31 @@ def or_status(status):
     return int(sum(int(b) << k for k, b in enumerate(flags.tolist())))
 
 
+def _relin_action_at_period(env, dem, hzn, period):
+    """One solve of the re-linearised host loop at a control period of `period` seconds: linearise at the current (x.values,
+    u.values[1:4]), ZOH at that period, calc_MPC_action on that model with the rate rows at the same period (OSQP's defaults).
+    env.ssr, the environment's own frozen model, is not touched."""
+    import ctypes
+    from . import lib as _lib
+    from .env import _vp
+    env._linearise_na()
+    Ac, Bc, Cc = env._lin
+    Ad, Bd = torch.empty_like(Ac), torch.empty_like(Bc)
+    env._check(env.lib.f16_c2d_batch(env.ctx.handle, _vp(Ac), _vp(Bc), _vp(Ad), _vp(Bd), env.B, env.B, period, env._stream))
+    s = _lib.QPSettings()
+    env.lib.f16_qp_default_settings(ctypes.byref(s))
+    ucmd = torch.empty((3, env.B), dtype=torch.float64, device=env.device)
+    info = torch.empty((4, env.B), dtype=torch.float64, device=env.device)
+    st = torch.zeros(env.B, dtype=torch.int32, device=env.device)
+    env._check(env.lib.f16_mpc_batch_w(env.ctx.handle, _vp(Ad), _vp(Bd), _vp(Cc), _vp(env._x), _vp(dem), None, None, _vp(ucmd), None,
+                                       _vp(info), _vp(st), env.B, env.B, int(hzn), period, ctypes.byref(s), env._stream))
+    env.last_status, env.last_iters = st, info[0]
+    env.status |= st
+    return ucmd.t()
+
+
 def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, traj_every=1, gather=True, use_plan=True, stats=None,
-                            fused=None, hold_command=False, one_lane=False, relinearise=False):
+                            fused=None, hold_command=False, one_lane=False, relinearise=False, ctrl_every=1):
     """BASELINE config 5 / test_env.py:480-495 pattern on this rank's shard, then one all-gather:
     per step  cmd = calc_MPC_action(p,q,r,hzn); u.values[1:] = cmd; step(u.values).
     fused=True: the whole loop of the shard as ONE launch (F16Batch.rollout_MPC / C-ABI f16_rollout_mpc: (step, aircraft) pairs from
@@ -167,15 +190,26 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
     relinearise: the reduced model is re-derived at every step instead of frozen -- fused: F16Batch.rollout_MPC(...,
     relinearise=True) (C-ABI f16_rollout_mpc_relin, one launch); host loop: `_calc_MPC_action(relinearise=True)` per step (no plan: the
     model changes with every call, so use_plan only selects the default path here).
+    ctrl_every = k > 1: the controller runs every k-th plant step (steps % k == 0; steps and traj_every stay in plant steps) on a model
+    and rate rows at the control period k * env.dt -- fused: rollout_MPC(..., ctrl_every=k) (C-ABI f16_rollout_mpc_hold /
+    f16_rollout_mpc_relin_hold, one launch); host loop: per control step a solve on the plan of that period (re-linearised: the
+    model discretised at that period, no plan), the command into u.values, then env.rollout(k) -- bit-identical with one_lane=True.
+    The stats then count per control step.
     Returns the collated trajectory [steps//traj_every, 18, B_total] (or the local shard if gather=False)."""
     from . import lib as _lib
+    ctrl_every = int(ctrl_every)
+    if ctrl_every < 1 or steps % ctrl_every:
+        raise ValueError(f"steps ({steps}) must be a multiple of ctrl_every ({ctrl_every}) >= 1")
+    if ctrl_every > 1 and steps % traj_every:
+        raise ValueError(f"steps ({steps}) must be a multiple of traj_every ({traj_every}) when ctrl_every > 1")
     T = steps // traj_every
     if fused is None:
         plan_ok = getattr(env, "_plan", None) is None or (env._plan_hzn == int(hzn) and getattr(env, "_plan_default_settings", False))
         fused = bool(use_plan) and int(hzn) <= 30 and plan_ok and not one_lane
     if fused:
         traj, info = env.rollout_MPC(steps, p_dem, q_dem, r_dem, hzn, traj_every=traj_every, return_info=True, hold_command=hold_command,
-                                     **(dict(relinearise=True) if relinearise else {}))
+                                     **(dict(relinearise=True) if relinearise else {}),
+                                     **(dict(ctrl_every=ctrl_every) if ctrl_every > 1 else {}))
         if stats is not None:
             its = info["iters"].to(torch.float64)
             stats["iters_mean"] = float(its.mean())
@@ -187,14 +221,19 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
         dem[k] = torch.as_tensor(v, dtype=torch.float64, device=env.device)
     it_sum = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
     it_max = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
-    flagged = torch.zeros((steps, 3), dtype=torch.int64, device=env.device) if stats is not None else None
+    nctrl = steps // ctrl_every
+    flagged = torch.zeros((nctrl, 3), dtype=torch.int64, device=env.device) if stats is not None else None
     flags0 = env.flags
     if one_lane:
         env.flags = env.flags | _lib.F16_FLAG_ONE_LANE
     try:
-        for k in range(steps):
-            cmd = env._calc_MPC_action(dem, None, None, hzn, relinearise=True) if relinearise else \
-                env._calc_MPC_action(dem, None, None, hzn, use_plan=use_plan)
+        for k in range(nctrl):
+            if ctrl_every > 1:
+                cmd = _relin_action_at_period(env, dem, hzn, ctrl_every * env.dt) if relinearise else \
+                    env._calc_MPC_action(dem, None, None, hzn, use_plan=True, ctrl_every=ctrl_every)
+            else:
+                cmd = env._calc_MPC_action(dem, None, None, hzn, relinearise=True) if relinearise else \
+                    env._calc_MPC_action(dem, None, None, hzn, use_plan=use_plan)
             if it_sum is not None:
                 it_sum += env.last_iters.sum()
                 it_max += env.last_iters.max()
@@ -204,13 +243,23 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
                 flagged[k, 2] = ((st & _lib.F16_ST["NONFINITE"]) != 0).sum()
             c = cmd.t()
             env._u[1:4] = torch.where(torch.isnan(c), env._u[1:4], c) if hold_command else c
+            if ctrl_every > 1:      # the hold: ctrl_every plant steps in one launch, the samples that fall into it
+                s0, s1 = k * ctrl_every, (k + 1) * ctrl_every
+                if ctrl_every % traj_every == 0:
+                    traj[s0 // traj_every:s1 // traj_every] = env.rollout(ctrl_every, traj_every=traj_every)
+                else:
+                    seg = env.rollout(ctrl_every, traj_every=1)
+                    for j in range(ctrl_every):
+                        if (s0 + j + 1) % traj_every == 0:
+                            traj[(s0 + j + 1) // traj_every - 1] = seg[j]
+                continue
             env.rollout(1)
             if (k + 1) % traj_every == 0:
                 traj[(k + 1) // traj_every - 1] = env._x
     finally:
         env.flags = flags0
     if stats is not None:
-        stats["iters_mean"] = float(it_sum) / max(1, steps * env.B)
-        stats["iters_max_mean"] = float(it_max) / max(1, steps)
+        stats["iters_mean"] = float(it_sum) / max(1, nctrl * env.B)
+        stats["iters_max_mean"] = float(it_max) / max(1, nctrl)
         stats["flagged_per_step"] = flagged.cpu().numpy()
     return all_gather_trajectories(traj) if gather else traj

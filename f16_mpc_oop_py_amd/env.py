@@ -340,6 +340,7 @@ class F16Batch:
         self._linearise_na(eps)
         Ad, Bd = self.discretise()
         self.ssr = (Ad, Bd, self._lin[2])
+        self._ssr_cont = self._lin[:2]          # the continuous (Ac, Bc) of this point: prepare_MPC(ctrl_every > 1) discretises them again
         return self.ssr
 
     def _calc_LQR_gain(self, Q=None, R=None):
@@ -523,15 +524,29 @@ class F16Batch:
         return trx, tru
 
     # ------------------------------------------------------------------ env.py:373-424
-    def prepare_MPC(self, hzn, settings=None, warm_start=False, weights=None):
+    def prepare_MPC(self, hzn, settings=None, warm_start=False, weights=None, ctrl_every=1):
         """Prepare the model-only part of calc_MPC_action for horizon hzn from the frozen reduced model self.ssr
         (env.py:49-60 freezes it; the reference still rebuilds the QP on every call): DARE, terminal weight, prediction
         blocks, P, A'A, start rho and the KKT factorisation stay on the device.  `_calc_MPC_action(..., use_plan=True)`
-        then only forms the state-dependent vectors and iterates; results are bit-identical to the one-shot call."""
+        then only forms the state-dependent vectors and iterates; results are bit-identical to the one-shot call.
+        ctrl_every = k > 1: a plan for a controller that runs every k plant steps (rollout_MPC(..., ctrl_every=k)).  Its model is this
+        environment's linearisation -- the continuous (Ac, Bc) of build_ssr's point -- through the zero-order hold at the control
+        period k * self.dt, which is also the dt of its rate rows; self.ssr itself is untouched."""
+        ctrl_every = int(ctrl_every)
+        if ctrl_every < 1:
+            raise ValueError(f"ctrl_every must be >= 1 (got {ctrl_every})")
         if self.ssr is None:
             self.build_ssr()
         self.release_MPC_plan()
         Ad, Bd, Cd = self.ssr
+        plan_dt = self.dt
+        if ctrl_every > 1:
+            if getattr(self, "_ssr_cont", None) is None:
+                raise ValueError("ctrl_every > 1 discretises the continuous model of build_ssr(); self.ssr was set by hand")
+            Ac, Bc = self._ssr_cont
+            plan_dt = ctrl_every * self.dt
+            Ad, Bd = torch.empty_like(Ac), torch.empty_like(Bc)
+            self._check(self.lib.f16_c2d_batch(self.ctx.handle, _vp(Ac), _vp(Bc), _vp(Ad), _vp(Bd), self.B, self.B, plan_dt, self._stream))
         s = _lib.QPSettings()
         self.lib.f16_qp_default_settings(ctypes.byref(s))
         for k, v in (settings or {}).items():
@@ -539,9 +554,9 @@ class F16Batch:
         h = ctypes.c_void_p()
         w = _lib.make_weights(**weights) if weights else None           # (utils.py:21 Q, R and the six bound vectors; fixed for the plan)
         self._check(self.lib.f16_mpc_plan_create_w(self.ctx.handle, ctypes.byref(h), _vp(Ad), _vp(Bd), _vp(Cd),
-                                                   ctypes.byref(w) if w else None, self.B, self.B, int(hzn), self.dt, ctypes.byref(s),
+                                                   ctypes.byref(w) if w else None, self.B, self.B, int(hzn), plan_dt, ctypes.byref(s),
                                                    self._stream))
-        self._plan, self._plan_hzn = h, int(hzn)
+        self._plan, self._plan_hzn, self._plan_ctrl_every = h, int(hzn), ctrl_every
         self._plan_default_settings = int((settings or {}).get("scaling", 10)) > 0       # (what f16_rollout_mpc takes: equilibrated solves)
         if warm_start:      # OSQP's in-object default; the reference starts cold on every call (new object), so: opt-in
             self._check(self.lib.f16_mpc_plan_warm_start(h, 1))
@@ -549,20 +564,20 @@ class F16Batch:
         self._plan_foreign = False      # True once rollout_MPC(relinearise=True) has overwritten the plan's model blocks
         return self
 
-    def _frozen_plan(self, hzn):
-        """The prepared plan of horizon hzn for a frozen-model call: made if absent; prepared AGAIN from self.ssr (same settings, weights
-        and warm-start switch) if the re-linearised loop has run on it -- its model blocks then hold per-step models, and the
-        library refuses it for frozen-model calls."""
-        if getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
-            self.prepare_MPC(hzn)
+    def _frozen_plan(self, hzn, ctrl_every=1):
+        """The prepared plan of (horizon hzn, control period ctrl_every plant steps) for a frozen-model call: made if absent; prepared
+        AGAIN from self.ssr (same settings, weights and warm-start switch) if the re-linearised loop has run on it -- its model blocks
+        then hold per-step models, and the library refuses it for frozen-model calls."""
+        if getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), int(ctrl_every)):
+            self.prepare_MPC(hzn, ctrl_every=ctrl_every)
         elif getattr(self, "_plan_foreign", False):
-            self.prepare_MPC(hzn, **self._plan_args)
+            self.prepare_MPC(hzn, ctrl_every=ctrl_every, **self._plan_args)
         return self._plan
 
     def release_MPC_plan(self):
         if getattr(self, "_plan", None) is not None:
             self.lib.f16_mpc_plan_destroy(self._plan)
-        self._plan, self._plan_hzn, self._plan_foreign = None, None, False
+        self._plan, self._plan_hzn, self._plan_foreign, self._plan_ctrl_every = None, None, False, 1
 
     def __del__(self):
         try:
@@ -604,12 +619,15 @@ class F16Batch:
         return P, q, A, l, u
 
     def _calc_MPC_action(self, p_dem, q_dem, r_dem, hzn, settings=None, return_info=False, relinearise=False,
-                         use_plan=False, weights=None, x_ref=None):
+                         use_plan=False, weights=None, x_ref=None, ctrl_every=1):
         """First MPC move [B,3] (dh,da,dr commands) for demands p,q,r (scalars or [B]) over horizon hzn, from the
         frozen reduced model self.ssr (env.py:385-387) and the current state.  The QP of utils.py:21-167 is solved
         on the GPU by OSQP-style ADMM (the reference calls the `osqp` package, env.py:420-422).
         weights / x_ref: as in setup_OSQP (the solvers keep the reference's pattern of bounded rows; a plan fixes its weights at
-        prepare_MPC, x_ref is per call)."""
+        prepare_MPC, x_ref is per call).  ctrl_every = k > 1 (use_plan only): the plan of control period k * self.dt
+        (prepare_MPC(ctrl_every=k)) -- the solve of the multi-rate loop rollout_MPC(..., ctrl_every=k)."""
+        if int(ctrl_every) != 1 and not use_plan:
+            raise ValueError("ctrl_every > 1 is a property of a prepared plan: use_plan=True")
         # relinearise=True: SURVEY.md 8f-2 -- the reduced model is re-derived at the CURRENT state on every call (the
         # reference freezes it at construction, env.py:49-60; its test_env.py:625-687 loops re-linearise per step)
         if self.ssr is None or relinearise:
@@ -631,7 +649,7 @@ class F16Batch:
         if use_plan:
             if relinearise or settings or weights:
                 raise ValueError("a prepared plan fixes the model, the QP settings and the weights (prepare_MPC)")
-            self._frozen_plan(hzn)
+            self._frozen_plan(hzn, ctrl_every)
             xr = self._soa(x_ref, 9) if x_ref is not None else None
             self._check(self.lib.f16_mpc_plan_solve_w(self._plan, _vp(self._x), _vp(dem), _vp(xr), _vp(ucmd), _vp(useq), _vp(info),
                                                       _vp(st), self._stream))
@@ -658,7 +676,7 @@ class F16Batch:
     calc_MPC_action = _calc_MPC_action
 
     def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False,
-                    relinearise=False, eps=1e-5):
+                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None):
         """The reference's closed MPC loop (test_env.py:480-495; BASELINE config 5) as ONE launch (C-ABI f16_rollout_mpc): per step
         `cmd = _calc_MPC_action(p_dem, q_dem, r_dem, hzn); u.values[1:] = cmd; step(u.values)` from the frozen reduced model
         (env.py:49-60) with OSQP's default settings (every solve cold, as the reference's -- or warm from the step before when the plan was
@@ -673,8 +691,20 @@ class F16Batch:
         launch.  The info dict then also carries model [nsteps//k, 189, B]: Ad (81) | Bd (27) | Cd (81) of the solve of every stored
         step (NaN where an aircraft was not solved for).  The call takes the plan's weights, bounds and settings but overwrites its
         model blocks, so the plan is marked: further relinearise=True calls go on using it, while the next frozen-model call
-        (use_plan=True, rollout_MPC without relinearise) prepares it again from self.ssr, which is untouched."""
-        nsteps = int(nsteps)
+        (use_plan=True, rollout_MPC without relinearise) prepares it again from self.ssr, which is untouched.
+        ctrl_every = k > 1 (C-ABI f16_rollout_mpc_hold / f16_rollout_mpc_relin_hold): the controller runs every k-th plant step and its
+        command is held for k steps of self.dt; the plan's model and rate rows are at the control period k * self.dt
+        (prepare_MPC(ctrl_every=k); made here if absent).  nsteps and traj_every stay in PLANT steps, nsteps % k == 0; cmd and iters
+        have one row per control step ([nsteps // k, ...]); model (relinearise) [nsteps // k // model_every, 189, B] holds the model of
+        every model_every-th control step (default 1).  The envelope is tested before every plant step."""
+        nsteps, ctrl_every = int(nsteps), int(ctrl_every)
+        if ctrl_every < 1 or nsteps % ctrl_every:      # (argument checks first: they need no GPU)
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of ctrl_every ({ctrl_every}) >= 1")
+        if ctrl_every > 1:
+            return self._rollout_MPC_hold(nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps,
+                                          ctrl_every, model_every)
+        if model_every is not None:
+            raise ValueError("model_every belongs to ctrl_every > 1 (with ctrl_every = 1 the models follow traj_every)")
         if relinearise:      # (argument checks first: they need no GPU)
             if not float(eps) > 0.0:
                 raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
@@ -684,7 +714,7 @@ class F16Batch:
                 raise ValueError(f"nsteps ({nsteps}) must be >= 0 and a multiple of traj_every ({traj_every})")
         if not relinearise:
             self._frozen_plan(hzn)
-        elif getattr(self, "_plan", None) is None or self._plan_hzn != int(hzn):
+        elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), 1):
             self.prepare_MPC(hzn)
         if relinearise and not self._plan_default_settings:
             raise ValueError("relinearise=True needs a plan with equilibrated solves (scaling > 0)")
@@ -712,6 +742,44 @@ class F16Batch:
         if return_info:
             return traj, dict(cmd=cmd, iters=its)
         return traj
+
+    def _rollout_MPC_hold(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps, hold,
+                          model_every):
+        """rollout_MPC at a control period of `hold` > 1 plant steps."""
+        nctrl = nsteps // hold
+        model_every = 1 if model_every is None else int(model_every)
+        if nctrl < 1:
+            raise ValueError(f"ctrl_every={hold} needs nsteps >= {hold} (got {nsteps})")
+        if traj_every and (int(traj_every) < 1 or nsteps % int(traj_every)):
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
+        if int(hzn) < 1 or int(hzn) > 30:
+            raise ValueError(f"ctrl_every > 1 runs on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
+        if relinearise and not float(eps) > 0.0:
+            raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
+        if model_every < 1 or (relinearise and nctrl % model_every):
+            raise ValueError(f"the control steps ({nctrl}) must be a multiple of model_every ({model_every}) >= 1")
+        if not relinearise:
+            self._frozen_plan(hzn, hold)
+        elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), hold):
+            self.prepare_MPC(hzn, ctrl_every=hold)
+        if not self._plan_default_settings:
+            raise ValueError("ctrl_every > 1 needs a plan with equilibrated solves (scaling > 0)")
+        dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
+        k = int(traj_every or 1)
+        traj = torch.empty((nsteps // k, 18, self.B), dtype=torch.float64, device=self.device) if traj_every else None
+        cmd = torch.empty((nctrl, 3, self.B), dtype=torch.float64, device=self.device) if return_info else None
+        its = torch.empty((nctrl, self.B), dtype=torch.int32, device=self.device) if return_info else None
+        flags = self.flags | (_lib.F16_FLAG_HOLD_COMMAND if hold_command else 0)
+        if relinearise:
+            model = torch.empty((nctrl // model_every, 189, self.B), dtype=torch.float64, device=self.device) if return_info else None
+            self._plan_foreign = True
+            self._check(self.lib.f16_rollout_mpc_relin_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd),
+                                                            _vp(its), _vp(model), _vp(self.status), nctrl, hold, k, model_every, self.dt,
+                                                            float(eps), self.xcg, self.fi_flag, flags, self._stream))
+            return (traj, dict(cmd=cmd, iters=its, model=model)) if return_info else traj
+        self._check(self.lib.f16_rollout_mpc_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
+                                                  _vp(self.status), nctrl, hold, k, self.dt, self.xcg, self.fi_flag, flags, self._stream))
+        return (traj, dict(cmd=cmd, iters=its)) if return_info else traj
 
     def _calc_constr_checking_hzn(self, max_hzn=150, settings=None, return_info=False):
         """env.py:426-436: the first move of calc_MPC_action(0, 0, 0, N) for every horizon N = 1..max_hzn (the reference

@@ -257,6 +257,9 @@ def load():
         L.f16_mpc_qp_debug_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, wp, l, l, i, d, vp, vp, vp, vp, vp]
         L.f16_rollout_mpc.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, d, i, u, vp]
         L.f16_rollout_mpc_relin.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, d, d, i, u, vp]
+        if hasattr(L, "f16_rollout_mpc_hold"):      # (absent from an older library loaded through F16HIP_SO for an A/B run)
+            L.f16_rollout_mpc_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, d, d, i, u, vp]
+            L.f16_rollout_mpc_relin_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, d, d, d, i, u, vp]
         L.f16_mpc_plan_warm_start.argtypes = [vp, i]
         L.f16_mpc_plan_destroy.argtypes = [vp]
         L.f16_mpc_plan_destroy.restype = None

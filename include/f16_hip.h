@@ -363,6 +363,43 @@ int f16_rollout_mpc(f16_mpc_plan *plan, double *x, double *u, const double *dem,
 int f16_rollout_mpc_relin(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                           int32_t *iters_traj, double *model_traj, int32_t *status, int nsteps, int traj_every, double eps,
                           double xcg, int fi_flag, unsigned flags, void *stream);
+/* The two closed MPC loops at a CONTROL PERIOD OF SEVERAL PLANT STEPS, as ONE launch.  `hold` >= 1 plant steps follow every solve.  At
+ * each of the nctrl control instants, for every aircraft:
+ *     cmd = calc_MPC_action(p, q, r, hzn)       the existing rules; the model and the rate rows at the plan's dt = the control period
+ *     u.values[1:] = cmd                        (F16_FLAG_HOLD_COMMAND as in f16_rollout_mpc)
+ *     for j in range(hold): step(u.values)      env.py:105-130 with the PLANT step dt; the envelope test in front of EVERY plant step
+ * f16_rollout_mpc_relin_hold: in front of the solve, forward differences at (x, u[1:4]) with the step eps, ZOH at the plan's dt (the
+ * control period), the model part of the QP -- the stage of f16_rollout_mpc_relin unchanged.
+ * `dt` is the plant's Euler step.  The plan's dt (f16_mpc_plan_create) is the control period, and the call returns F16_EINVAL unless
+ * |hold * dt - plan dt| <= 1e-12 * plan dt: a model discretised at another period than the one it is applied at is a caller's
+ * mistake, not a mode.
+ * The call equals this host loop, bit for bit, for every aircraft that stays inside its envelope (frozen aircraft: equal states and
+ * status words; the host loop goes on solving for them):
+ *     for c in range(nctrl):
+ *         f16_mpc_plan_solve(plan, x, dem, cmd, ...);  u[1:4] = cmd
+ *         f16_rollout(ctx, x, u, x, samples, B, ld, hold, traj_every, dt, xcg, fi_flag, flags | F16_FLAG_ONE_LANE, status)
+ * (re-linearised: f16_linearise_batch at (x, u[1:4]) -> f16_c2d_batch at hold * dt -> f16_mpc_batch_w in place of the plan's solve).
+ * hold = 1 with dt = the plan's dt is f16_rollout_mpc / f16_rollout_mpc_relin (the same kernel: they are this call).
+ *   - traj (may be NULL) [nctrl * hold / traj_every][18][ld]: the state after every traj_every-th PLANT step.  traj_every counts plant
+ *     steps, is independent of hold, and nctrl * hold % traj_every == 0.
+ *   - cmd_traj (may be NULL) [nctrl][3][ld] and iters_traj (may be NULL) [nctrl][ld]: one row per control step.
+ *   - model_traj (may be NULL) [nctrl / model_every][189][ld]: Ad | Bd | Cd of control step c, stored when (c + 1) % model_every == 0,
+ *     with nctrl % model_every == 0.  f16_mpc_batch_w on a stored model, the state before that control step and the demands, called
+ *     with dt = the plan's dt, returns cmd_traj[c] and iters_traj[c] exactly.
+ *   - x / u in place, the sticky status, F16_FLAG_*, NaN for infeasible or not-solved pairs, the ticket scheme: as in the two calls above.
+ *     The re-linearised call marks the plan as f16_rollout_mpc_relin does (f16_rollout_mpc_hold then refuses it, F16_EINVAL).  Not
+ *     capturable on a plan's first call.  nctrl x B < 2^32 and nctrl x hold < 2^31 per call.
+ *   - F16_EINVAL also for hold < 1, nctrl < 1, model_every < 1, eps <= 0.
+ * Per-aircraft rules at plant-step granularity: an aircraft found outside the envelope at the start of ANY plant step is frozen from
+ * that plant step on, as f16_rollout does inside a launch -- the rest of its hold is not stepped, later samples repeat the frozen state,
+ * and its later control steps are not solved for (NaN in cmd_traj, 0 iterations; re-linearised: NaN model).  F16_ST_NONFINITE is formed
+ * after the last plant step of a control step. */
+int f16_rollout_mpc_hold(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                         int32_t *iters_traj, int32_t *status, int nctrl, int hold, int traj_every, double dt,
+                         double xcg, int fi_flag, unsigned flags, void *stream);
+int f16_rollout_mpc_relin_hold(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
+                               int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold, int traj_every,
+                               int model_every, double dt, double eps, double xcg, int fi_flag, unsigned flags, void *stream);
 int f16_mpc_plan_create(f16_ctx *ctx, f16_mpc_plan **plan, const double *Ad, const double *Bd, const double *Cd,
                         long B, long ld, int hzn, double dt, const f16_qp_settings *s, void *stream);
 int f16_mpc_plan_solve(f16_mpc_plan *plan, const double *x, const double *dem, double *u_cmd, double *u_seq,
