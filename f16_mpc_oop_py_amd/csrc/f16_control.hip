@@ -200,11 +200,12 @@ __global__ __launch_bounds__(64, 3) void k_lqr(LqrArgs a) {
 // lqr_gain_wave), lane 0 takes the Euler step through euler_step_exact (the F16_FLAG_ONE_LANE step).  The state, the command and
 // the gain live in LDS between steps.
 struct RelinArgs {
-  const double *tab, *lofi, *xref, *u0;
+  const double *tab, *lofi, *xref, *u0;      // xref: [ceil(nsteps / hold)][9][ld], step t reads row t / hold
   double *x, *u, *traj, *utraj, *Ktraj;
   int32_t *status;
   long B, ld;
   int nsteps, every;
+  int hold;                // steps per row of xref (f16_rollout_lqr_relin_sched; >= nsteps: the one row of f16_rollout_lqr_relin)
   unsigned track;
   double eps, dt, xcg;
   int fi;
@@ -240,8 +241,16 @@ __global__ __launch_bounds__(64, F16_RELIN_MIN_WAVES) void k_rollout_lqr_relin(R
     __syncthreads();
     int st = a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr, *tu = a.utraj ? a.utraj + b : nullptr, *tk = a.Ktraj ? a.Ktraj + b : nullptr;
-    int until = a.every;
+    int until = a.every, seg = a.hold;
+    const double *xrow = a.xref;
     for (int t = 0; t < a.nsteps; ++t) {
+      if (seg == 0) {      // a segment boundary of the schedule (t % hold == 0): the next row of x_ref, in front of the step's first use
+        seg = a.hold;
+        xrow += 9 * a.ld;
+        if (l < 9) xr[l] = ((a.track >> l) & 1u) ? xrow[l * a.ld + b] : 0.0;
+        __syncthreads();
+      }
+      --seg;
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(xs)) st |= ST_ENVELOPE;      // env.py:117-124
       if (!(st & ST_ENVELOPE)) {
         // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps)
@@ -851,15 +860,22 @@ extern "C" int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, c
   return f16_lqr_batch_w(ctx, Ad, Bd, Cd, nullptr, K, Pare, status, B, ld, stream);
 }
 
-extern "C" int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
-                                     const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
-                                     long B, long ld, int nsteps, int traj_every, unsigned track_mask, double eps, double dt,
-                                     double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (!ctx || !x || !u || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_rollout_lqr_relin");
-  if (nsteps < 1 || traj_every < 1 || nsteps % traj_every != 0)
-    return set_error(F16_EINVAL, "f16_rollout_lqr_relin: nsteps must be >= 1 and a multiple of traj_every >= 1");
-  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_lqr_relin: eps must be > 0");
-  if ((track_mask & 0x1FFu) && !x_ref) return set_error(F16_EINVAL, "f16_rollout_lqr_relin: x_ref is NULL but track_mask selects entries");
+static int rollout_lqr_relin_launch(const char *name, f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
+                                    const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
+                                    long B, long ld, int nsteps, int hold, int traj_every, unsigned track_mask, double eps, double dt,
+                                    double xcg, int fi_flag, unsigned flags, void *stream) {
+  char msg[160];
+  if (!ctx || !x || !u || B < 0 || ld < B) { snprintf(msg, sizeof msg, "bad argument to %s", name); return set_error(F16_EINVAL, msg); }
+  if (nsteps < 1 || traj_every < 1 || nsteps % traj_every != 0) {
+    snprintf(msg, sizeof msg, "%s: nsteps must be >= 1 and a multiple of traj_every >= 1", name);
+    return set_error(F16_EINVAL, msg);
+  }
+  if (hold < 1) { snprintf(msg, sizeof msg, "%s: hold must be >= 1", name); return set_error(F16_EINVAL, msg); }
+  if (!(eps > 0)) { snprintf(msg, sizeof msg, "%s: eps must be > 0", name); return set_error(F16_EINVAL, msg); }
+  if ((track_mask & 0x1FFu) && !x_ref) {
+    snprintf(msg, sizeof msg, "%s: x_ref is NULL but track_mask selects entries", name);
+    return set_error(F16_EINVAL, msg);
+  }
   RelinArgs a{};
   mpc_default_prob(&a.pb);
   if (h_w)
@@ -867,10 +883,28 @@ extern "C" int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const d
   if (B == 0) return F16_OK;
   a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.xref = x_ref; a.u0 = u0;
   a.x = x; a.u = u; a.traj = traj; a.utraj = u_traj; a.Ktraj = K_traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.every = traj_every; a.track = track_mask & 0x1FFu;
+  a.B = B; a.ld = ld; a.nsteps = nsteps; a.every = traj_every; a.hold = hold < nsteps ? hold : nsteps; a.track = track_mask & 0x1FFu;
   a.eps = eps; a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   hipLaunchKernelGGL(k_rollout_lqr_relin, dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
-  return hip_check(hipGetLastError(), "f16_rollout_lqr_relin launch");
+  snprintf(msg, sizeof msg, "%s launch", name);
+  return hip_check(hipGetLastError(), msg);
+}
+
+extern "C" int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
+                                     const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
+                                     long B, long ld, int nsteps, int traj_every, unsigned track_mask, double eps, double dt,
+                                     double xcg, int fi_flag, unsigned flags, void *stream) {
+  return rollout_lqr_relin_launch("f16_rollout_lqr_relin", ctx, x, u, x_ref, u0, h_w, traj, u_traj, K_traj, status, B, ld, nsteps,
+                                  nsteps > 0 ? nsteps : 1, traj_every, track_mask, eps, dt, xcg, fi_flag, flags, stream);      // (one row)
+}
+
+// The same loop under a schedule of references: step t reads row t / hold of xref_seq[ceil(nsteps / hold)][9][ld].
+extern "C" int f16_rollout_lqr_relin_sched(f16_ctx *ctx, double *x, double *u, const double *xref_seq, const double *u0,
+                                           const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
+                                           long B, long ld, int nsteps, int hold, int traj_every, unsigned track_mask, double eps,
+                                           double dt, double xcg, int fi_flag, unsigned flags, void *stream) {
+  return rollout_lqr_relin_launch("f16_rollout_lqr_relin_sched", ctx, x, u, xref_seq, u0, h_w, traj, u_traj, K_traj, status, B, ld,
+                                  nsteps, hold, traj_every, track_mask, eps, dt, xcg, fi_flag, flags, stream);
 }
 
 extern "C" void f16_qp_default_settings(f16_qp_settings *s) {
@@ -1379,6 +1413,39 @@ extern "C" int f16_rollout_mpc_relin_hold(f16_mpc_plan *p, double *x, double *u,
   RolloutMpcCall c{};
   c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
   c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
+  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = model_every;
+  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+}
+
+// The two loops under a demand schedule: control step c reads row c / dem_hold of dem_seq[ceil(nctrl / dem_hold)][3][ld] (the ticket
+// loop of k_rollout_mpc picks the row; pair_prepare / pair_model read it as they read a constant demand).  Everything else is the
+// _hold calls'.
+extern "C" int f16_rollout_mpc_sched(f16_mpc_plan *p, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
+                                     int32_t *iters_traj, int32_t *status, int nctrl, int hold, int dem_hold, int traj_every, double dt,
+                                     double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (!p || !x || !u || !dem_seq) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_sched");
+  if (dem_hold < 1) return set_error(F16_EINVAL, "f16_rollout_mpc_sched: dem_hold must be >= 1");
+  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc_sched: a re-linearised loop overwrote this plan's model; create a new plan for the frozen model");
+  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_sched", p, traj, nctrl, hold, traj_every, dt)) return rc;
+  RolloutMpcCall c{};
+  c.x = x; c.u = u; c.dem = dem_seq; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
+  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags; c.dem_hold = dem_hold;
+  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+}
+
+extern "C" int f16_rollout_mpc_relin_sched(f16_mpc_plan *p, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
+                                           int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold, int dem_hold,
+                                           int traj_every, int model_every, double dt, double eps, double xcg, int fi_flag,
+                                           unsigned flags, void *stream) {
+  if (!p || !x || !u || !dem_seq) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin_sched");
+  if (dem_hold < 1) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: dem_hold must be >= 1");
+  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_relin_sched", p, traj, nctrl, hold, traj_every, dt)) return rc;
+  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: the linearisation step eps must be > 0");
+  if (model_every < 1 || (model_traj && nctrl % model_every != 0))
+    return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: model_every must be >= 1, and divide nctrl when model_traj is given");
+  RolloutMpcCall c{};
+  c.x = x; c.u = u; c.dem = dem_seq; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
+  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags; c.dem_hold = dem_hold;
   c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = model_every;
   return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
 }

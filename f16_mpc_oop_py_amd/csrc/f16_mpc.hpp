@@ -124,7 +124,7 @@ int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream);
 // the closed-loop rollout (f16_rollout_mpc): per-call arguments beside the plan's MpcArgs
 struct RolloutMpcCall {
   double *x, *u;
-  const double *dem;
+  const double *dem;          // [3][ld], or with dem_hold > 0 [ceil(T / dem_hold)][3][ld]
   double *traj, *cmd_traj;
   int32_t *iters_traj, *status;
   void *sync;                 // [8 bytes ticket counter | B x int32 progress], zeroed by the launch
@@ -132,6 +132,7 @@ struct RolloutMpcCall {
   int warm_load;              // step 0 starts from what the plan's previous call left (later steps always start from the step before)
   int T, every;               // T control steps; a sample after every `every`-th plant step
   int hold;                   // plant steps per control step (1: f16_rollout_mpc / f16_rollout_mpc_relin)
+  int dem_hold;               // control steps per demand row (f16_rollout_mpc_sched); 0: one constant demand
   double dt;                  // the plant's Euler step (hold x dt = the plan's dt)
   double xcg;
   int fi;

@@ -26,6 +26,8 @@
 //                   above, linearise at the current point -> ZOH -> the model part of the QP (pair_model)
 //   Both take `hold` Euler steps of the plant's own dt per pair (f16_rollout_mpc_hold / f16_rollout_mpc_relin_hold: a control period
 //   of several plant steps; pair_finish); f16_rollout_mpc / f16_rollout_mpc_relin are the hold = 1 calls of the same two kernels.
+//   Under a demand schedule (f16_rollout_mpc_sched / f16_rollout_mpc_relin_sched) control step t reads demand row t / dem_hold; the
+//   calls with one constant demand are the one-row case.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -1602,7 +1604,7 @@ struct RollMpcArgs {
   MpcArgs m;                     // the plan's arguments: workspace, settings, weights (m.x = x: the solver reads the actuator states)
   double *x;                     // [18][ld] x.values, in place
   double *u;                     // [4][ld] u.values: thrust command held, u[1:4] <- the command of every step
-  const double *dem;             // [3][ld] (p, q, r) demands
+  const double *dem;             // [ceil(T / dem_hold)][3][ld] (p, q, r) demands: control step t reads row t / dem_hold
   double *traj;                  // [T / every][18][ld] or null
   double *cmd_traj;              // [T][3][ld] or null: what calc_MPC_action returned at each step (NaN: infeasible / not finite / no solve)
   int32_t *iters_traj;           // [T][ld] or null
@@ -1612,6 +1614,7 @@ struct RollMpcArgs {
   const double *tab, *lofi;      // table images (global)
   int T, every;                  // T control steps (the tickets' steps); a sample after every `every`-th PLANT step
   int hold;                      // plant steps per control step (f16_rollout_mpc_hold; 1: the reference's loop)
+  int dem_hold;                  // control steps per demand row (f16_rollout_mpc_sched; >= T: one row, the constant demand of the other calls)
   double dtp;                    // the plant's Euler step (hold x dtp = m.dt, the plan's period: checked by the entry point)
   double xcg;
   int fi;
@@ -1926,7 +1929,7 @@ __global__ __launch_bounds__(64, 1) void k_rollout_mpc(typename std::conditional
     __syncthreads();
     PSTAMP(2)
     PairIO io;
-    io.x = ra.x; io.u = ra.u; io.dem = ra.dem; io.traj = ra.traj; io.cmd_traj = ra.cmd_traj; io.iters_traj = ra.iters_traj;
+    io.x = ra.x; io.u = ra.u; io.dem = ra.dem + (size_t)(t / ra.dem_hold) * 3 * a.ld; io.traj = ra.traj; io.cmd_traj = ra.cmd_traj; io.iters_traj = ra.iters_traj;
     io.status = ra.status; io.tab = ra.tab; io.lofi = ra.lofi; io.exw = a.ext + (size_t)b * mpc_ext_doubles(N);
     io.ld = a.ld; io.b = b; io.t = t; io.N = N; io.every = ra.every; io.fi = ra.fi; io.flags = ra.flags; io.xcg = ra.xcg; io.dt = a.dt;
     io.hold = ra.hold; io.dtp = ra.dtp;
@@ -2032,7 +2035,7 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   r.queue = reinterpret_cast<unsigned *>(c.sync);
   r.progress = reinterpret_cast<int32_t *>(c.sync) + 2;
   r.tab = ctx->d_tab; r.lofi = ctx->d_lofi;
-  r.T = c.T; r.every = c.every; r.hold = c.hold; r.dtp = c.dt; r.xcg = c.xcg; r.fi = c.fi; r.flags = c.flags;
+  r.T = c.T; r.every = c.every; r.hold = c.hold; r.dem_hold = c.dem_hold > 0 ? c.dem_hold : 0x7fffffff; r.dtp = c.dt; r.xcg = c.xcg; r.fi = c.fi; r.flags = c.flags;
   r.total = (unsigned)((unsigned long long)a.B * (unsigned long long)c.T);
   r.stride = 0;
   static const bool spread = [] { const char *e = getenv("F16_MPC_SPREAD"); return !(e && e[0] == '0'); }();

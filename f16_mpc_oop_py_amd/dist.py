@@ -168,7 +168,7 @@ def _relin_action_at_period(env, dem, hzn, period):
 
 
 def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, traj_every=1, gather=True, use_plan=True, stats=None,
-                            fused=None, hold_command=False, one_lane=False, relinearise=False, ctrl_every=1):
+                            fused=None, hold_command=False, one_lane=False, relinearise=False, ctrl_every=1, dem_every=None):
     """BASELINE config 5 / test_env.py:480-495 pattern on this rank's shard, then one all-gather:
     per step  cmd = calc_MPC_action(p,q,r,hzn); u.values[1:] = cmd; step(u.values).
     fused=True: the whole loop of the shard as ONE launch (F16Batch.rollout_MPC / C-ABI f16_rollout_mpc: (step, aircraft) pairs from
@@ -195,6 +195,9 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
     f16_rollout_mpc_relin_hold, one launch); host loop: per control step a solve on the plan of that period (re-linearised: the
     model discretised at that period, no plan), the command into u.values, then env.rollout(k) -- bit-identical with one_lane=True.
     The stats then count per control step.
+    Demand histories: p_dem, q_dem, r_dem as [S] or [S, B] with dem_every (F16Batch.rollout_MPC's rules: control step c takes row
+    c // dem_every) -- fused: rollout_MPC(..., dem_every=) (C-ABI f16_rollout_mpc_sched / f16_rollout_mpc_relin_sched, one launch); host
+    loop: the row of every control step picked here, the checker of the fused path.
     Returns the collated trajectory [steps//traj_every, 18, B_total] (or the local shard if gather=False)."""
     from . import lib as _lib
     ctrl_every = int(ctrl_every)
@@ -203,13 +206,17 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
     if ctrl_every > 1 and steps % traj_every:
         raise ValueError(f"steps ({steps}) must be a multiple of traj_every ({traj_every}) when ctrl_every > 1")
     T = steps // traj_every
+    dem_seq = None
+    if not fused:          # (the fused call makes these checks itself; fused=None may still end in the host loop)
+        dem_seq, dem_k = env._mpc_demand_rows(p_dem, q_dem, r_dem, dem_every, steps // ctrl_every)
     if fused is None:
         plan_ok = getattr(env, "_plan", None) is None or (env._plan_hzn == int(hzn) and getattr(env, "_plan_default_settings", False))
         fused = bool(use_plan) and int(hzn) <= 30 and plan_ok and not one_lane
     if fused:
         traj, info = env.rollout_MPC(steps, p_dem, q_dem, r_dem, hzn, traj_every=traj_every, return_info=True, hold_command=hold_command,
                                      **(dict(relinearise=True) if relinearise else {}),
-                                     **(dict(ctrl_every=ctrl_every) if ctrl_every > 1 else {}))
+                                     **(dict(ctrl_every=ctrl_every) if ctrl_every > 1 else {}),
+                                     **(dict(dem_every=dem_every) if dem_every is not None else {}))
         if stats is not None:
             its = info["iters"].to(torch.float64)
             stats["iters_mean"] = float(its.mean())
@@ -217,8 +224,9 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
         return all_gather_trajectories(traj) if gather else traj
     traj = torch.empty((T, 18, env.B), dtype=torch.float64, device=env.device)
     dem = torch.empty((3, env.B), dtype=torch.float64, device=env.device)      # demands on the device once
-    for k, v in enumerate((p_dem, q_dem, r_dem)):
-        dem[k] = torch.as_tensor(v, dtype=torch.float64, device=env.device)
+    if dem_seq is None:
+        for k, v in enumerate((p_dem, q_dem, r_dem)):
+            dem[k] = torch.as_tensor(v, dtype=torch.float64, device=env.device)
     it_sum = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
     it_max = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
     nctrl = steps // ctrl_every
@@ -228,6 +236,8 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
         env.flags = env.flags | _lib.F16_FLAG_ONE_LANE
     try:
         for k in range(nctrl):
+            if dem_seq is not None:
+                dem = dem_seq[k // dem_k]      # the demand row of this control step ([3, B], contiguous)
             if ctrl_every > 1:
                 cmd = _relin_action_at_period(env, dem, hzn, ctrl_every * env.dt) if relinearise else \
                     env._calc_MPC_action(dem, None, None, hzn, use_plan=True, ctrl_every=ctrl_every)

@@ -394,6 +394,25 @@ class F16Batch:
                 seq[:, k] = v.unsqueeze(0)
         return seq
 
+    def _mpc_demand_rows(self, p_dem, q_dem, r_dem, dem_every, nctrl):
+        """The demands of a closed MPC loop of nctrl control steps -> (dem_seq [S, 3, B], dem_every) when any of them is a history
+        ([S] or [S, B]: _demand_schedule's rule), (None, None) for constant demands -- a 2-D p_dem with q_dem is None and r_dem is None
+        is a ready [3, B] block, as it always was.  Control step c reads row c // dem_every (default 1).  Raises ValueError for
+        dem_every < 1, dem_every without a history, histories that disagree and too few rows: argument checks, no GPU call."""
+        if dem_every is not None and int(dem_every) < 1:
+            raise ValueError(f"dem_every must be >= 1 (got {dem_every})")
+        ready = torch.is_tensor(p_dem) and p_dem.dim() == 2 and q_dem is None and r_dem is None
+        seq = None if ready else self._demand_schedule(p_dem, q_dem, r_dem)
+        if seq is None:
+            if dem_every is not None:
+                raise ValueError("dem_every goes with demand histories ([S] or [S, B]); scalar / [B] demands are constant")
+            return None, None
+        k = 1 if dem_every is None else int(dem_every)
+        need = (max(int(nctrl), 0) + k - 1) // k
+        if need < 1 or need > seq.shape[0]:
+            raise ValueError(f"{nctrl} control steps with dem_every {k} need {need} demand rows (>= 1), the histories have {seq.shape[0]}")
+        return seq.contiguous(), k
+
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
                     R=None, hold=None):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
@@ -466,29 +485,55 @@ class F16Batch:
                                              self.xcg, self.fi_flag, self.flags, self._stream))
         return traj
 
-    def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None):
+    def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
+                          hold=None):
         """The per-step re-linearised LQR loop (test_env.py:625-687 `test_LQR_dynamic_nl`) in ONE launch (C-ABI
         f16_rollout_lqr_relin): per step linearise at the current (x, u[1:4]) with eps -> ZOH -> Kd = dlqr(Ad, Bd, Q, R) ->
         u[1:4] = -Kd (x9 - x_ref) + u0 -> step(u.values), the thrust command held.  x_ref [B,9] or [9] defaults to the current x9;
         track (indices into x9) selects the entries of x_ref that are held fixed, the others follow the current x9 (None: all nine);
         u0 [B,3] or None (= 0); Q [9,9] / R [3,3] default to env.py's Cd'Cd and I.  x.values, u.values (the last command) and
         status are updated in place.  Samples every k-th step, k = traj_every or gains_every or 1 (the two must agree when both
-        are given).  Returns (traj [n//k, 18, B], u_traj [n//k, 3, B], K_traj [n//k, B, 3, 9] = -dlqr or None without gains_every)."""
+        are given).  Returns (traj [n//k, 18, B], u_traj [n//k, 3, B], K_traj [n//k, B, 3, 9] = -dlqr or None without gains_every).
+        A schedule of references: x_ref [S, 9, B] (state-major rows) with hold = h runs as one launch of f16_rollout_lqr_relin_sched:
+        step t takes row t // h (h defaults to 1; S >= ceil(nsteps / h)); it equals one rollout_LQR_relin call per row.  hold is
+        not taken without such a history (ValueError)."""
         if traj_every and gains_every and int(traj_every) != int(gains_every):
             raise ValueError("the states, commands and gains are sampled at one interval: traj_every must equal gains_every")
+        if hold is not None and int(hold) < 1:
+            raise ValueError(f"hold must be >= 1 (got {hold})")
         k = int(traj_every or gains_every or 1)
+        if x_ref is not None and np.ndim(x_ref) == 3:
+            hold = 1 if hold is None else int(hold)
+            xr = torch.as_tensor(x_ref, dtype=torch.float64, device=self.device).contiguous()
+            if tuple(xr.shape[1:]) != (9, self.B):
+                raise ValueError(f"a schedule of references is [S, 9, {self.B}], not {tuple(xr.shape)}")
+            if int(nsteps) < 1 or (int(nsteps) + hold - 1) // hold > xr.shape[0]:
+                raise ValueError(f"{nsteps} steps with hold {hold} need {max(int(nsteps) + hold - 1, 0) // hold} rows (>= 1), x_ref has {xr.shape[0]}")
+            mask = 0x1FF if track is None else sum(1 << int(j) for j in track)
+            u03 = None if u0 is None else self._soa(u0, 3)
+            return self._rollout_relin(nsteps, xr, mask, u03, _lib.make_weights(Q=Q, R=R), eps, k, True, True, gains_every is not None,
+                                       hold=hold)
+        if hold is not None:
+            raise ValueError("hold goes with a schedule of references, x_ref [S, 9, B]")
         xr = self._x[P.mpc_x_idx].clone() if x_ref is None else self._soa(x_ref, 9)
         mask = 0x1FF if track is None else sum(1 << int(j) for j in track)
         u03 = None if u0 is None else self._soa(u0, 3)
         return self._rollout_relin(nsteps, xr, mask, u03, _lib.make_weights(Q=Q, R=R), eps, k, True, True, gains_every is not None)
 
-    def _rollout_relin(self, nsteps, xref, mask, u03, w, eps, k, want_x, want_u, want_k):
-        """f16_rollout_lqr_relin on the resident state: xref [9,B], u03 [3,B] or None (state-major, contiguous)."""
+    def _rollout_relin(self, nsteps, xref, mask, u03, w, eps, k, want_x, want_u, want_k, hold=None):
+        """f16_rollout_lqr_relin on the resident state: xref [9,B], u03 [3,B] or None (state-major, contiguous); with hold:
+        f16_rollout_lqr_relin_sched, xref [S,9,B]."""
         nsteps, k = int(nsteps), int(k)
         if k < 1 or nsteps % k:
             raise ValueError(f"nsteps ({nsteps}) must be a multiple of the sampling interval ({k})")
         mk = lambda want, rows: torch.empty((nsteps // k, rows, self.B), dtype=torch.float64, device=self.device) if want else None
         traj, u_traj, K_traj = mk(want_x, 18), mk(want_u, 3), mk(want_k, 27)
+        if hold is not None:
+            self._check(self.lib.f16_rollout_lqr_relin_sched(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
+                                                             ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj),
+                                                             _vp(self.status), self.B, self.B, nsteps, int(hold), k, int(mask),
+                                                             float(eps), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
+            return traj, u_traj, None if K_traj is None else K_traj.permute(0, 2, 1).reshape(nsteps // k, self.B, 3, 9)
         self._check(self.lib.f16_rollout_lqr_relin(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
                                                    ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj),
                                                    _vp(self.status), self.B, self.B, nsteps, k, int(mask), float(eps), self.dt,
@@ -676,7 +721,7 @@ class F16Batch:
     calc_MPC_action = _calc_MPC_action
 
     def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False,
-                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None):
+                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None, dem_every=None):
         """The reference's closed MPC loop (test_env.py:480-495; BASELINE config 5) as ONE launch (C-ABI f16_rollout_mpc): per step
         `cmd = _calc_MPC_action(p_dem, q_dem, r_dem, hzn); u.values[1:] = cmd; step(u.values)` from the frozen reduced model
         (env.py:49-60) with OSQP's default settings (every solve cold, as the reference's -- or warm from the step before when the plan was
@@ -696,13 +741,21 @@ class F16Batch:
         command is held for k steps of self.dt; the plan's model and rate rows are at the control period k * self.dt
         (prepare_MPC(ctrl_every=k); made here if absent).  nsteps and traj_every stay in PLANT steps, nsteps % k == 0; cmd and iters
         have one row per control step ([nsteps // k, ...]); model (relinearise) [nsteps // k // model_every, 189, B] holds the model of
-        every model_every-th control step (default 1).  The envelope is tested before every plant step."""
+        every model_every-th control step (default 1).  The envelope is tested before every plant step.
+        Demand histories (C-ABI f16_rollout_mpc_sched / f16_rollout_mpc_relin_sched; the pilot loop of flight_sim.py:141-182, whose
+        demands change while the controller runs): when any of p_dem, q_dem, r_dem is [S] or [S, B] (rollout_LQR's rule: [B] is a
+        constant demand per aircraft, scalars are broadcast) the loop still runs as one launch and control step c takes row
+        c // dem_every (default 1; S >= ceil(control steps / dem_every)), with relinearise and ctrl_every alike.  The demand of a control
+        step is held over that step's whole horizon, so the call equals one call per row.  A 2-D p_dem with q_dem is None and
+        r_dem is None stays a ready [3, B] block of constant demands.  dem_every without a history, too few rows and
+        dem_every < 1 raise ValueError."""
         nsteps, ctrl_every = int(nsteps), int(ctrl_every)
         if ctrl_every < 1 or nsteps % ctrl_every:      # (argument checks first: they need no GPU)
             raise ValueError(f"nsteps ({nsteps}) must be a multiple of ctrl_every ({ctrl_every}) >= 1")
-        if ctrl_every > 1:
+        dem_seq, dem_every = self._mpc_demand_rows(p_dem, q_dem, r_dem, dem_every, nsteps // ctrl_every)
+        if ctrl_every > 1 or dem_seq is not None:      # (a schedule at ctrl_every = 1: the same call with hold = 1)
             return self._rollout_MPC_hold(nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps,
-                                          ctrl_every, model_every)
+                                          ctrl_every, model_every, dem_seq, dem_every)
         if model_every is not None:
             raise ValueError("model_every belongs to ctrl_every > 1 (with ctrl_every = 1 the models follow traj_every)")
         if relinearise:      # (argument checks first: they need no GPU)
@@ -744,8 +797,8 @@ class F16Batch:
         return traj
 
     def _rollout_MPC_hold(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps, hold,
-                          model_every):
-        """rollout_MPC at a control period of `hold` > 1 plant steps."""
+                          model_every, dem_seq=None, dem_every=None):
+        """rollout_MPC at a control period of `hold` > 1 plant steps, and under a demand schedule (dem_seq [S,3,B]; then hold >= 1)."""
         nctrl = nsteps // hold
         model_every = 1 if model_every is None else int(model_every)
         if nctrl < 1:
@@ -753,7 +806,7 @@ class F16Batch:
         if traj_every and (int(traj_every) < 1 or nsteps % int(traj_every)):
             raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
         if int(hzn) < 1 or int(hzn) > 30:
-            raise ValueError(f"ctrl_every > 1 runs on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
+            raise ValueError(f"ctrl_every > 1 and demand histories run on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
         if relinearise and not float(eps) > 0.0:
             raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
         if model_every < 1 or (relinearise and nctrl % model_every):
@@ -763,8 +816,11 @@ class F16Batch:
         elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), hold):
             self.prepare_MPC(hzn, ctrl_every=hold)
         if not self._plan_default_settings:
-            raise ValueError("ctrl_every > 1 needs a plan with equilibrated solves (scaling > 0)")
-        dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
+            raise ValueError("ctrl_every > 1 and demand histories need a plan with equilibrated solves (scaling > 0)")
+        if dem_seq is not None:
+            dem = dem_seq
+        else:
+            dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
         k = int(traj_every or 1)
         traj = torch.empty((nsteps // k, 18, self.B), dtype=torch.float64, device=self.device) if traj_every else None
         cmd = torch.empty((nctrl, 3, self.B), dtype=torch.float64, device=self.device) if return_info else None
@@ -773,10 +829,21 @@ class F16Batch:
         if relinearise:
             model = torch.empty((nctrl // model_every, 189, self.B), dtype=torch.float64, device=self.device) if return_info else None
             self._plan_foreign = True
+            if dem_seq is not None:
+                self._check(self.lib.f16_rollout_mpc_relin_sched(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd),
+                                                                 _vp(its), _vp(model), _vp(self.status), nctrl, hold, dem_every, k,
+                                                                 model_every, self.dt, float(eps), self.xcg, self.fi_flag, flags,
+                                                                 self._stream))
+                return (traj, dict(cmd=cmd, iters=its, model=model)) if return_info else traj
             self._check(self.lib.f16_rollout_mpc_relin_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd),
                                                             _vp(its), _vp(model), _vp(self.status), nctrl, hold, k, model_every, self.dt,
                                                             float(eps), self.xcg, self.fi_flag, flags, self._stream))
             return (traj, dict(cmd=cmd, iters=its, model=model)) if return_info else traj
+        if dem_seq is not None:
+            self._check(self.lib.f16_rollout_mpc_sched(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
+                                                       _vp(self.status), nctrl, hold, dem_every, k, self.dt, self.xcg, self.fi_flag,
+                                                       flags, self._stream))
+            return (traj, dict(cmd=cmd, iters=its)) if return_info else traj
         self._check(self.lib.f16_rollout_mpc_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
                                                   _vp(self.status), nctrl, hold, k, self.dt, self.xcg, self.fi_flag, flags, self._stream))
         return (traj, dict(cmd=cmd, iters=its)) if return_info else traj

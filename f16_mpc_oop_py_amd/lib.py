@@ -260,6 +260,10 @@ def load():
         if hasattr(L, "f16_rollout_mpc_hold"):      # (absent from an older library loaded through F16HIP_SO for an A/B run)
             L.f16_rollout_mpc_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, d, d, i, u, vp]
             L.f16_rollout_mpc_relin_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, d, d, d, i, u, vp]
+        if hasattr(L, "f16_rollout_mpc_sched"):     # (absent from an older library loaded through F16HIP_SO for an A/B run)
+            L.f16_rollout_mpc_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, d, d, i, u, vp]
+            L.f16_rollout_mpc_relin_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, d, d, d, i, u, vp]
+            L.f16_rollout_lqr_relin_sched.argtypes = [vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, i, i, u, d, d, d, i, u, vp]
         L.f16_mpc_plan_warm_start.argtypes = [vp, i]
         L.f16_mpc_plan_destroy.argtypes = [vp]
         L.f16_mpc_plan_destroy.restype = None

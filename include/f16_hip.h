@@ -279,6 +279,16 @@ int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_re
                           int32_t *status, long B, long ld, int nsteps, int traj_every, unsigned track_mask,
                           double eps, double dt, double xcg, int fi_flag, unsigned flags, void *stream);
 
+/* f16_rollout_lqr_relin under a SCHEDULE of references, one launch: x_ref becomes xref_seq[S][9][ld] with S = ceil(nsteps / hold), and
+ * step t reads row t / hold (the last segment may be shorter; hold >= nsteps reads row 0 only).  Only the entries selected by
+ * track_mask are read.  Everything else is f16_rollout_lqr_relin's, so the call equals the chain of f16_rollout_lqr_relin calls, one
+ * per row with that row as x_ref, bit for bit (the chain's K_traj holds zeros for an aircraft that was frozen on entry of a call; this
+ * call keeps the last gain of the launch).  F16_EINVAL as f16_rollout_lqr_relin, and for hold < 1 or a track_mask without xref_seq. */
+int f16_rollout_lqr_relin_sched(f16_ctx *ctx, double *x, double *u, const double *xref_seq, const double *u0,
+                                const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj,
+                                int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, unsigned track_mask,
+                                double eps, double dt, double xcg, int fi_flag, unsigned flags, void *stream);
+
 typedef struct f16_qp_settings {
   double rho, sigma, alpha, eps_abs, eps_rel, eps_prim_inf;
   int max_iter, check_every, rho_every, adaptive_rho;
@@ -400,6 +410,26 @@ int f16_rollout_mpc_hold(f16_mpc_plan *plan, double *x, double *u, const double 
 int f16_rollout_mpc_relin_hold(f16_mpc_plan *plan, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold, int traj_every,
                                int model_every, double dt, double eps, double xcg, int fi_flag, unsigned flags, void *stream);
+/* The two calls above under a DEMAND SCHEDULE, as ONE launch (the pilot's p/q/r demand changes while the controller runs:
+ * flight_sim.py:141-182; _calc_MPC_action takes the demand per call).  dem becomes dem_seq[S][3][ld] with S = ceil(nctrl / dem_hold),
+ * state-major with the plan's ld, and control step c reads row c / dem_hold: the last segment may be shorter, dem_hold = 1 is a new
+ * demand at every control step, dem_hold >= nctrl reads row 0 only.  The demand of a control step is held over the whole horizon of
+ * that step's QP (x_ref[5:8] = demands, env.py:383): no preview, no QP vector built by another rule.  The call therefore equals the
+ * chain of f16_rollout_mpc_hold / f16_rollout_mpc_relin_hold calls, one per row with that row as the constant demand, bit for bit.
+ * hold = 1 with dt = the plan's dt is the reference's loop under a schedule.  Everything else is the base call's: the in-place x / u,
+ * traj / cmd_traj / iters_traj / model_traj and their strides, the sticky status, F16_FLAG_*, the frozen / non-finite / infeasible rules
+ * per (control step, aircraft) pair, the |hold * dt - plan dt| check, the plan marking of the re-linearised call, "not capturable on a
+ * plan's first call", and the size limits.  A non-finite entry in the row of a control step is that step's F16_ST_NONFINITE (NaN
+ * command, zero iterations), as a non-finite constant demand is; the next finite row is solved for again.  A frozen aircraft ignores
+ * the rest of its schedule.  The plan's opt-in warm start is untouched: step c starts from step c - 1 whatever the rows are.
+ * F16_EINVAL where the base call returns it, and for dem_hold < 1 or a NULL dem_seq. */
+int f16_rollout_mpc_sched(f16_mpc_plan *plan, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
+                          int32_t *iters_traj, int32_t *status, int nctrl, int hold, int dem_hold, int traj_every, double dt,
+                          double xcg, int fi_flag, unsigned flags, void *stream);
+int f16_rollout_mpc_relin_sched(f16_mpc_plan *plan, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
+                                int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold, int dem_hold,
+                                int traj_every, int model_every, double dt, double eps, double xcg, int fi_flag, unsigned flags,
+                                void *stream);
 int f16_mpc_plan_create(f16_ctx *ctx, f16_mpc_plan **plan, const double *Ad, const double *Bd, const double *Cd,
                         long B, long ld, int hzn, double dt, const f16_qp_settings *s, void *stream);
 int f16_mpc_plan_solve(f16_mpc_plan *plan, const double *x, const double *dem, double *u_cmd, double *u_seq,
