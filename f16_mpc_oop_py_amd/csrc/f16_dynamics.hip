@@ -53,8 +53,44 @@ struct SchedArgs : DynArgs {
   const double *seq;
   int hold, nrows;
 };
-template <bool SCHED>
-using RolloutArgs = std::conditional_t<SCHED, SchedArgs, DynArgs>;
+// The COST instantiations (f16_rollout_cost) score the scheduled rollout: a third type, the two above stay what they are.  Lane b is
+// sample b / B0 of aircraft b % B0: its state comes from column b % B0 of x0 (read-only) and nothing is integrated in place -- `out`
+// is the cost column [ld], the per-lane array the schedule rows are addressed from (RowAhead); x_end may be null.  The weights are
+// uniform and travel by value (scalar registers; nothing to allocate, so the call can be captured).
+struct CostArgs : SchedArgs {
+  const double *x0;      // [18][ld0]
+  const double *x_ref;   // [9][ld0]  MPC-state order (parameters.py:135)
+  const double *u_ref;   // [3][ld0] or null (= 0)
+  double *x_end;         // [18][ld] or null
+  long B0, ld0;
+  f16_cost_weights w;
+};
+template <bool SCHED, bool COST = false>
+using RolloutArgs = std::conditional_t<COST, CostArgs, std::conditional_t<SCHED, SchedArgs, DynArgs>>;
+
+// parameters.py:135 / 198-210: x9 = x[3, 4, 7, 8, 9, 10, 11, 17, 16]
+F16_DEV double mpc_state(const double *x, int k) { return x[k < 2 ? 3 + k : (k < 7 ? 5 + k : 24 - k)]; }
+// sum_k w[k] (x9[k] - x_ref[k])^2 added to J in the order k = 0..8; ref(k) = the lane's reference entry k
+template <typename REF>
+F16_DEV double cost_state_term(double J, const double *x, const double (&w)[9], REF ref) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const double d = mpc_state(x, k) - ref(k);
+    J += w[k] * d * d;
+  }
+  return J;
+}
+// sum_i r[i] (u[1 + i] - u_ref[i])^2 of one row: formed when the row is installed, added once per step taken under it
+F16_DEV double cost_command_term(const CostArgs &a, long b0, double u1, double u2, double u3) {
+  const double uc[3] = {u1, u2, u3};
+  double s = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double d = uc[i] - (a.u_ref ? a.u_ref[i * a.ld0 + b0] : 0.0);
+    s += a.w.r[i] * d * d;
+  }
+  return s;
+}
 
 // The schedule of one lane in a SCHED instantiation, N values per row (ld apart, the lane's first at row + lane_off).  A new row
 // must never be loaded where it is used: a load that misses to HBM is ~900 cycles, a third of a quad-kernel step.
@@ -166,15 +202,37 @@ constexpr bool INC_TRIG = true;
 #else
 constexpr bool INC_TRIG = false;
 #endif
-template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false>
-__device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
-                                              double (*tgs)[BLOCK] = nullptr) {
+// COST (f16_rollout_cost; SCHED && !LQR only): the lane's cost J is accumulated in a register pair in step order; the nine x_ref
+// entries of the lane sit in lane-indexed LDS slots xr like the inputs (XRL), or -- where those do not fit beside the fp64 image,
+// the 512-lane workgroups -- are re-read from global memory (L2) at every step.
+template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false, bool COST = false, bool XRL = false>
+__device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
+                                              double (*tgs)[BLOCK] = nullptr, double (*xr)[BLOCK] = nullptr) {
+  static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   for (long b = (long)blockIdx.x * BLOCK + threadIdx.x; b < a.B; b += (long)gridDim.x * BLOCK) {
     double x[18];
+    long b0 = b;                                         // (COST) the aircraft of this lane: the column of x0 / x_ref / u_ref
+    double J = 0, ju = 0;                                // (COST) the cost so far; the command term of the row in use
+    if constexpr (COST) {
+      b0 = b % a.B0;
+#pragma unroll
+      for (int k = 0; k < 18; ++k) x[k] = a.x0[k * a.ld0 + b0];
+      if (XRL) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) xr[k][threadIdx.x] = a.x_ref[k * a.ld0 + b0];
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) x[k] = a.out[k * a.ld + b];
+    }
+    [[maybe_unused]] const auto ref = [&](int k) {       // (COST) entry k of the lane's reference
+      if constexpr (COST) return XRL ? xr[k][threadIdx.x] : a.x_ref[k * a.ld0 + b0];
+      else return 0.0;
+    };
+    if (!COST || a.nsteps > 0) {                         // (a scored rollout of no steps has no rows)
 #pragma unroll
     for (int k = 0; k < 4; ++k) us[k][threadIdx.x] = a.u[k * a.ld + b];
+    }
     double ul[3] = {us[1][threadIdx.x], us[2][threadIdx.x], us[3][threadIdx.x]};   // (u_out of an aircraft that never steps: u0)
     if (LQR) {   // K[i][4..6] and the demands: lane-indexed LDS slots like the inputs (constant over the rollout, used once per step)
 #pragma unroll
@@ -184,10 +242,11 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T,
 #pragma unroll
       for (int j = 0; j < 3; ++j) kq[9 + j][threadIdx.x] = a.dem[j * a.ld + b];
     }
-    int st = a.status ? a.status[b] : 0;
+    int st = !COST && a.status ? a.status[b] : 0;        // (COST: status is an output, every lane starts from 0)
     double *tr = a.traj ? a.traj + b : nullptr;
     int until_store = a.traj_every;
     bool stale = true;                                   // (INCT) the first step evaluates the five pairs exactly
+    if constexpr (COST) if (a.nsteps > 0) ju = cost_command_term(a, b0, ul[0], ul[1], ul[2]);
     // SCHED: the row in use sits where the constant input does (us / kq[9..11]); the next one in registers (<= 256 lanes)
     constexpr int NR = LQR ? 3 : 4;
     // 64-lane workgroups (B <= 16,384) count the 32 steps between exact sin / cos evaluations from the start of the ROW, as the
@@ -222,6 +281,9 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T,
 #pragma unroll
         for (int k = 0; k < 18; ++k) x[k] += xd[k] * a.dt;   // env.py:126
         }
+        if constexpr (COST) J = cost_state_term(J + ju, x, a.w.q, ref);
+      } else if constexpr (COST) {
+        J += a.w.pen;                                    // a step the frozen lane does not take
       }
       if (tr && --until_store == 0) {
         until_store = a.traj_every;
@@ -236,6 +298,7 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T,
         for (int k = 0; k < NR; ++k) (LQR ? kq[9 + k] : us[k])[threadIdx.x] = r[k];
         if (LQR) { ul[0] = us[1][threadIdx.x]; ul[1] = us[2][threadIdx.x]; ul[2] = us[3][threadIdx.x]; }   // (as a new launch: u0 until it steps)
         if (ROW_TRIG) { t0 = t + 1; stale = true; }
+        if constexpr (COST) ju = cost_command_term(a, b0, r[1], r[2], r[3]);
       }
     }
     bool finite = true;
@@ -244,8 +307,16 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T,
     if (!finite) st |= ST_NONFINITE;
     // WHICH states were outside: a frozen aircraft keeps the state it was frozen with, so the bits are formed here, once
     if (st & ST_ENVELOPE) st |= envelope_state_bits(x);
+    if constexpr (COST) {
+      a.out[b] = cost_state_term(J, x, a.w.qf, ref);      // the terminal term; `out` is the cost column
+      if (a.x_end) {
+#pragma unroll
+        for (int k = 0; k < 18; ++k) a.x_end[k * a.ld + b] = x[k];
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) a.out[k * a.ld + b] = x[k];
+    }
     if (a.status) a.status[b] = st;
     if (LQR && a.u_out) {
       a.u_out[b] = us[0][threadIdx.x];
@@ -259,14 +330,29 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED> &a, TP T,
 // from global memory: no LDS staging) -- ONE instruction sequence for every batch size, the one the closed MPC loop (f16_rollout_mpc)
 // steps with.  Same rules as rollout_lanes (envelope freeze, status bits, trajectory samples, u_out); a reproducibility path, not a
 // fast one.
-template <bool LQR, bool SCHED = false>
-__global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
+template <bool LQR, bool SCHED = false, bool COST = false>
+__global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a) {
+  static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   for (long b = (long)blockIdx.x * 64 + threadIdx.x; b < a.B; b += (long)gridDim.x * 64) {
     double x[18], u[4];
+    long b0 = b;                                         // (COST: as in rollout_lanes; the reference in registers)
+    double J = 0, ju = 0, xr[COST ? 9 : 1];
+    if constexpr (COST) {
+      b0 = b % a.B0;
+#pragma unroll
+      for (int k = 0; k < 18; ++k) x[k] = a.x0[k * a.ld0 + b0];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) xr[k] = a.x_ref[k * a.ld0 + b0];
+    } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) x[k] = a.out[k * a.ld + b];
+    }
+    [[maybe_unused]] const auto ref = [&](int k) { return xr[COST ? k : 0]; };
+    if (!COST || a.nsteps > 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) u[k] = a.u[k * a.ld + b];
+    }
+    if constexpr (COST) if (a.nsteps > 0) ju = cost_command_term(a, b0, u[1], u[2], u[3]);
     double kq[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, u0[3] = {u[1], u[2], u[3]};
     if (LQR) {
 #pragma unroll
@@ -276,7 +362,7 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) kq[9 + j] = a.dem[j * a.ld + b];
     }
-    int st = a.status ? a.status[b] : 0;
+    int st = !COST && a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr;
     int until_store = a.traj_every;
     constexpr int NR = LQR ? 3 : 4;
@@ -291,6 +377,9 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
           for (int i = 0; i < 3; ++i) u[1 + i] = lqr_action(kq[3 * i], kq[3 * i + 1], kq[3 * i + 2], e0, e1, e2, u0[i]);
         }
         euler_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &st);
+        if constexpr (COST) J = cost_state_term(J + ju, x, a.w.q, ref);
+      } else if constexpr (COST) {
+        J += a.w.pen;
       }
       if (tr && --until_store == 0) {
         until_store = a.traj_every;
@@ -301,6 +390,7 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
       if constexpr (SCHED) if (ra.due(a, NR)) {
         ra.take(a, NR, LQR ? kq + 9 : u, a.out + b);
         if (LQR) { u[1] = u0[0]; u[2] = u0[1]; u[3] = u0[2]; }      // (as a new launch: u0 until it steps)
+        if constexpr (COST) ju = cost_command_term(a, b0, u[1], u[2], u[3]);
       }
     }
     bool finite = true;
@@ -308,8 +398,16 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
     for (int k = 0; k < 18; ++k) finite = finite && isfinite(x[k]);
     if (!finite) st |= ST_NONFINITE;
     if (st & ST_ENVELOPE) st |= envelope_state_bits(x);
+    if constexpr (COST) {
+      a.out[b] = cost_state_term(J, x, a.w.qf, ref);
+      if (a.x_end) {
+#pragma unroll
+        for (int k = 0; k < 18; ++k) a.x_end[k * a.ld + b] = x[k];
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) a.out[k * a.ld + b] = x[k];
+    }
     if (a.status) a.status[b] = st;
     if (LQR && a.u_out) {
 #pragma unroll
@@ -318,8 +416,8 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED> a) {
   }
 }
 
-template <int BLOCK, int FI, bool LQR = false, bool SCHED = false>
-__global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED> a) {
+template <int BLOCK, int FI, bool LQR = false, bool SCHED = false, bool COST = false>
+__global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED, COST> a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   // the four inputs of a lane are constant over the rollout and used once per step: kept in lane-indexed (conflict-free) LDS
   // slots rather than in eight registers that the 512-lane instantiation (256 registers per lane) spilled and reloaded per step
@@ -327,28 +425,35 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED> a) {
   __shared__ double kq[LQR ? 12 : 1][LQR ? BLOCK : 1];
   constexpr bool INCT = INC_TRIG && BLOCK <= 256 && !(LQR && BLOCK == 256);      // (the ten slots must fit beside the fp64 table image and, closed loop, the gain slots)
   __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
+  constexpr bool XRL = COST && BLOCK <= 256;           // (nine more slots of 512 lanes do not fit beside the fp64 image)
+  __shared__ double xr[XRL ? 9 : 1][XRL ? BLOCK : 1];
+  static_assert(sizeof(tab) + sizeof(us) + sizeof(kq) + sizeof(tgs) + sizeof(xr) <= 163840, "static LDS of a CU");
   if (a.fi == 1) stage_tables(tab, a.tab);
-  rollout_lanes<BLOCK, FI, const double *, LQR, INCT, SCHED>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
-                                                      reinterpret_cast<double (*)[BLOCK]>(tgs));
+  rollout_lanes<BLOCK, FI, const double *, LQR, INCT, SCHED, COST, XRL>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
+                                                                        reinterpret_cast<double (*)[BLOCK]>(tgs),
+                                                                        reinterpret_cast<double (*)[BLOCK]>(xr));
 }
 
 // The same rollout on the scaled-integer table image (hifi, default numerics; large batches: the LDS pipe -- 1.5 KB of
 // table vertices per aircraft-step as doubles, more than half of its cycles bank-conflict replays of the per-lane gathers --
 // is one of the two ceilings of k_rollout there).
-template <int BLOCK, bool LQR = false, bool SCHED = false>
-__global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED> a) {
+template <int BLOCK, bool LQR = false, bool SCHED = false, bool COST = false>
+__global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED, COST> a) {
   __shared__ __attribute__((aligned(16))) int tab[i32::IMAGE_INTS];
   __shared__ double us[4][BLOCK];
   __shared__ double kq[LQR ? 12 : 1][LQR ? BLOCK : 1];
   constexpr bool INCT = INC_TRIG && !LQR;              // (closed loop: the gain slots take the room)
   __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
+  __shared__ double xr[COST ? 9 : 1][COST ? BLOCK : 1];
+  static_assert(sizeof(tab) + sizeof(us) + sizeof(kq) + sizeof(tgs) + sizeof(xr) <= 163840, "static LDS of a CU");
   {
     const int4 *src = reinterpret_cast<const int4 *>(a.tab32);
     int4 *dst = reinterpret_cast<int4 *>(tab);
     for (int i = threadIdx.x; i < i32::IMAGE_INTS / 4; i += BLOCK) dst[i] = src[i];
     __syncthreads();
   }
-  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq), reinterpret_cast<double (*)[BLOCK]>(tgs));
+  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED, COST, COST>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq),
+                                                                reinterpret_cast<double (*)[BLOCK]>(tgs), reinterpret_cast<double (*)[BLOCK]>(xr));
 }
 
 // Four-wavefront rollout (latency regime, hifi): one workgroup = 64 aircraft on the four SIMDs of a CU; the state is
@@ -1130,6 +1235,58 @@ extern "C" int f16_rollout_sched(f16_ctx *ctx, double *x, const double *u_seq, d
   a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   a.seq = u_seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
   return rollout_dispatch<false, true>(ctx, a, stream);
+}
+
+// f16_rollout_cost: the launch rules of rollout_dispatch without its quad and four-wave branches (those kernels split the state
+// over four role waves and have no scored twin), so a scored batch of B <= 16,384 hifi lanes runs the 64-lane one-lane kernel.
+template <int BLOCK>
+static void launch_cost_lanes(int grid, hipStream_t st, const CostArgs &a) {
+  if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, false, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+  else hipLaunchKernelGGL((k_rollout<BLOCK, -1, false, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+}
+
+extern "C" int f16_rollout_cost(f16_ctx *ctx, const double *x0, long B0, long ld0, const double *u_seq, const double *x_ref,
+                                const double *u_ref, const f16_cost_weights *h_w, double *cost, double *x_end, double *traj,
+                                int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt, double xcg,
+                                int fi_flag, unsigned flags, void *stream) {
+  if (!u_seq || !x_ref || !h_w || !cost) return set_error(F16_EINVAL, "u_seq / x_ref / h_w / cost is NULL");
+  if (int rc = check_rollout(ctx, x0, u_seq, traj, B, ld, nsteps, traj_every)) return rc;
+  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
+  if (B > 0 && (B0 < 1 || ld0 < B0 || B % B0 != 0))
+    return set_error(F16_EINVAL, "B lanes are K samples of B0 aircraft: B0 >= 1, ld0 >= B0 and B % B0 == 0");
+  {
+    const double *w = h_w->q;       // q[9], qf[9], r[3], pen: 22 doubles in a row
+    static_assert(sizeof(f16_cost_weights) == 22 * sizeof(double), "f16_cost_weights is 22 doubles");
+    for (int k = 0; k < 22; ++k)
+      if (!(w[k] >= 0.0) || !__builtin_isfinite(w[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
+  }
+  if (B == 0) return F16_OK;
+  CostArgs a{};
+  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u_seq; a.out = cost; a.traj = traj; a.status = status;
+  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
+  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  a.seq = u_seq; a.hold = hold; a.nrows = nsteps > 0 ? (nsteps - 1) / hold + 1 : 0;
+  a.x0 = x0; a.x_ref = x_ref; a.u_ref = u_ref; a.x_end = x_end; a.B0 = B0; a.ld0 = ld0; a.w = *h_w;
+  const hipStream_t st = (hipStream_t)stream;
+  if (flags & F16_FLAG_ONE_LANE) {
+    const long blocks = (B + 63) / 64;
+    hipLaunchKernelGGL((k_rollout_exact<false, true, true>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    return hip_check(hipGetLastError(), "f16_rollout_cost launch");
+  }
+  Geometry g = geometry(B, fi_flag);
+#ifdef F16_FAST_DIV
+  static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
+  if (fi_flag == 1 && use_i32 && g.block == 512) {
+    a.tab32 = ctx->d_tab32;
+    hipLaunchKernelGGL((k_rollout_i<512, false, true, true>), dim3(g.grid), dim3(512), 0, st, a);
+    return hip_check(hipGetLastError(), "f16_rollout_cost launch");
+  }
+#endif
+  if (g.block == 64) launch_cost_lanes<64>(g.grid, st, a);
+  else if (g.block == 128) launch_cost_lanes<128>(g.grid, st, a);
+  else if (g.block == 256) launch_cost_lanes<256>(g.grid, st, a);
+  else launch_cost_lanes<512>(g.grid, st, a);
+  return hip_check(hipGetLastError(), "f16_rollout_cost launch");
 }
 
 extern "C" int f16_rollout_lqr(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem, double *traj,

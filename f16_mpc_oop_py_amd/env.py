@@ -237,6 +237,163 @@ class F16Batch:
         self._u.copy_(seq[(nsteps - 1) // hold])
         return traj
 
+    # ------------------------------------------------------------------ scored rollouts of sampled schedules (MPPI)
+    def _sample_lanes(self, actions, width=4, name="actions"):
+        """[S, K, B, width] (numpy or torch, host or device) -> contiguous state-major [S, width, K * B] fp64 on the device (lane
+        k * B + a = sample k of aircraft a), and K."""
+        t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
+        if t.dim() != 4 or t.shape[2] != self.B or t.shape[3] != width or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be [S, K, {self.B}, {width}] with S, K >= 1, not {tuple(t.shape)}")
+        S, K = t.shape[0], t.shape[1]
+        return t.to(device=self.device, dtype=torch.float64).permute(0, 3, 1, 2).reshape(S, width, K * self.B).contiguous(), K
+
+    def _score(self, seq, K, hold, nsteps, x_ref, u_ref, w, traj_every, want_final):
+        """f16_rollout_cost on seq [S, 4, K * B] from the resident state -> cost [K * B], status [K * B], x_end [18, K * B] or None,
+        traj [n, 18, K * B] or None.  x_ref [9, B], u_ref [3, B] or None (state-major, contiguous)."""
+        hold, S, lanes = int(hold), seq.shape[0], K * self.B
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        nsteps = S * hold if nsteps is None else int(nsteps)
+        if nsteps < 1 or (nsteps + hold - 1) // hold > S:
+            raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), actions has {S}")
+        traj = None
+        if traj_every:
+            if nsteps % int(traj_every):
+                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
+            traj = torch.empty((nsteps // int(traj_every), 18, lanes), dtype=torch.float64, device=self.device)
+        cost = torch.empty(lanes, dtype=torch.float64, device=self.device)
+        st = torch.empty(lanes, dtype=torch.int32, device=self.device)
+        x_end = torch.empty((18, lanes), dtype=torch.float64, device=self.device) if want_final else None
+        self._check(self.lib.f16_rollout_cost(self.ctx.handle, _vp(self._x), self.B, self.B, _vp(seq), _vp(x_ref), _vp(u_ref),
+                                              ctypes.byref(w), _vp(cost), _vp(x_end), _vp(traj), _vp(st), lanes, lanes, nsteps, hold,
+                                              int(traj_every or 1), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
+        return cost, st, x_end, traj
+
+    def _blend(self, cost, seq, K, lam):
+        """f16_mppi_blend: cost [K * B], seq [S, 4, K * B] -> blended [S, 4, B], normalised weights [K * B], stats [2, B]"""
+        lam = float(lam)
+        if not (lam > 0.0 and np.isfinite(lam)):
+            raise ValueError(f"lam must be finite and > 0 (got {lam})")
+        S, lanes = seq.shape[0], K * self.B
+        out = torch.empty((S, 4, self.B), dtype=torch.float64, device=self.device)
+        wts = torch.empty(lanes, dtype=torch.float64, device=self.device)
+        stats = torch.empty((2, self.B), dtype=torch.float64, device=self.device)
+        self._check(self.lib.f16_mppi_blend(self.ctx.handle, _vp(cost), _vp(seq), lam, _vp(out), _vp(wts), _vp(stats), lanes, lanes,
+                                            self.B, self.B, S, self._stream))
+        return out, wts, stats
+
+    def score_schedules(self, actions, hold=1, nsteps=None, x_ref=None, u_ref=None, q=None, qf=None, r=None, penalty=0.0,
+                        traj_every=None, return_final=False):
+        """K sampled command schedules per aircraft through the nonlinear plant, each scored, in ONE launch (C-ABI
+        f16_rollout_cost): actions [S, K, B, 4] (numpy or torch, host or device), step t of sample k takes actions[t // hold, k] as
+        rollout_schedule does; every sample starts from the current x.values.  The cost of a sample is
+            sum over the steps taken of [ r . (u[1:4] - u_ref)^2 + q . (x9 - x_ref)^2 ] + penalty * (steps not taken: the sample
+            left the envelope of env.py:117-124 and is frozen) + qf . (x9_end - x_ref)^2
+        with x9 the MPC states (parameters.py:135) after each step.  x_ref [B, 9] or [9] defaults to the current x9, u_ref [B, 3] or
+        [3] to 0, q = qf = ones(9), r = ones(3): the diagonals of the reference's Q = Cd'Cd and R = I3 (env.py:385-399).  nsteps
+        defaults to S * hold.  Returns cost [K, B]; with return_final also the final states [18, K, B]; with traj_every = k also the
+        samples [nsteps // k, 18, K, B] -- (cost, final), (cost, traj) or (cost, final, traj).  x.values, u.values and status are
+        not touched; the status words of the samples [K, B] (an output: every sample starts from 0) are kept in
+        `last_score_status`."""
+        seq, K = self._sample_lanes(actions)
+        xr = self._x[P.mpc_x_idx].contiguous() if x_ref is None else self._soa(x_ref, 9)
+        ur = None if u_ref is None else self._soa(u_ref, 3)
+        w = _lib.make_cost_weights(q, qf, r, penalty)
+        cost, st, x_end, traj = self._score(seq, K, hold, nsteps, xr, ur, w, traj_every, return_final)
+        self.last_score_status = st.view(K, self.B)
+        out = (cost.view(K, self.B),)
+        if return_final:
+            out += (x_end.view(18, K, self.B),)
+        if traj_every:
+            out += (traj.view(-1, 18, K, self.B),)
+        return out[0] if len(out) == 1 else out
+
+    def blend_schedules(self, cost, actions, lam, return_info=False):
+        """The softmin blend of an MPPI step (C-ABI f16_mppi_blend; the rule is stated by mppi.blend_reference): cost [K, B],
+        actions [S, K, B, 4] -> [S, B, 4] = sum_k w_k actions[:, k] / sum_k w_k with w_k = exp(-(cost_k - min cost) / lam) over the
+        samples of finite cost (an aircraft without one gets sample 0).  return_info: also dict(weights [K, B] normalised,
+        min_cost [B], ess [B] the effective sample size (sum w)^2 / sum w^2)."""
+        seq, K = self._sample_lanes(actions)
+        c = cost if isinstance(cost, torch.Tensor) else torch.as_tensor(np.asarray(cost, dtype=np.float64))
+        if tuple(c.shape) != (K, self.B):
+            raise ValueError(f"cost must be [{K}, {self.B}] for these actions, not {tuple(c.shape)}")
+        c = c.to(device=self.device, dtype=torch.float64).contiguous().view(-1)
+        out, wts, stats = self._blend(c, seq, K, lam)
+        u = out.permute(0, 2, 1)
+        return (u, dict(weights=wts.view(K, self.B), min_cost=stats[0], ess=stats[1])) if return_info else u
+
+    def calc_MPPI_action(self, p_dem, q_dem, r_dem, nominal, noise, hold=1, lam=1.0, **weights):
+        """One step of sampling-based nonlinear MPC (MPPI, model-predictive path integral control) on the plant itself -- for the
+        states from which the linear MPC's QP has no feasible point: K command sequences per aircraft, nominal
+        [S, B, 4] plus noise [S, K, B, 3] on the three surface commands (the caller's, e.g. sigma * torch.randn(..., generator=g)),
+        clipped to the command limits (parameters.py:125-126; the thrust command is the nominal one), are rolled out for S * hold
+        steps, scored against x_ref = the current x9 with x_ref[4:7] = (p, q, r)_dem (the convention of _calc_LQR_action,
+        env.py:365-367) and blended by softmin weights of temperature lam: one score_schedules plus one blend_schedules.  weights:
+        q, qf, r, penalty, u_ref as score_schedules takes them.  Returns (the blended schedule [S, B, 4], dict(cost [K, B],
+        min_cost [B], ess [B], status [K, B])); nothing resident is touched."""
+        nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal, dtype=np.float64))
+        eps = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(np.asarray(noise, dtype=np.float64))
+        if nom.dim() != 3 or tuple(nom.shape[1:]) != (self.B, 4):
+            raise ValueError(f"nominal must be [S, {self.B}, 4], not {tuple(nom.shape)}")
+        if eps.dim() != 4 or eps.shape[0] != nom.shape[0] or eps.shape[2] != self.B or eps.shape[3] != 3 or eps.shape[1] < 1:
+            raise ValueError(f"noise must be [{nom.shape[0]}, K, {self.B}, 3], not {tuple(eps.shape)}")
+        if not (float(lam) > 0.0 and np.isfinite(float(lam))):
+            raise ValueError(f"lam must be finite and > 0 (got {lam})")
+        extra = set(weights) - {"q", "qf", "r", "penalty", "u_ref"}
+        if extra:
+            raise TypeError(f"unknown weights {sorted(extra)}")
+        nom = nom.to(device=self.device, dtype=torch.float64)
+        eps = eps.to(device=self.device, dtype=torch.float64)
+        K = eps.shape[1]
+        lo = torch.as_tensor(P.u_lb[1:], dtype=torch.float64, device=self.device)
+        hi = torch.as_tensor(P.u_ub[1:], dtype=torch.float64, device=self.device)
+        samples = nom.unsqueeze(1).repeat(1, K, 1, 1)
+        samples[..., 1:] = torch.minimum(torch.maximum(samples[..., 1:] + eps, lo), hi)
+        seq, _ = self._sample_lanes(samples)
+        xr = self._x[P.mpc_x_idx].clone()
+        xr[4:7] = self._demands(p_dem, q_dem, r_dem)
+        ur = None if weights.get("u_ref") is None else self._soa(weights["u_ref"], 3)
+        w = _lib.make_cost_weights(weights.get("q"), weights.get("qf"), weights.get("r"), weights.get("penalty", 0.0))
+        cost, st, _, _ = self._score(seq, K, hold, None, xr, ur, w, None, False)
+        out, _, stats = self._blend(cost, seq, K, lam)
+        return out.permute(0, 2, 1), dict(cost=cost.view(K, self.B), min_cost=stats[0], ess=stats[1], status=st.view(K, self.B))
+
+    def rollout_MPPI(self, nsteps, p_dem, q_dem, r_dem, horizon, hold, samples, sigma, lam, seed=0, traj_every=None,
+                     return_info=False, **weights):
+        """The closed MPPI loop as a host loop (fusing it into one launch is future work).  Per control period of `hold` plant steps:
+        noise = sigma * randn([horizon, samples, B, 3]) from a device torch.Generator seeded once with `seed`; calc_MPPI_action on
+        the nominal schedule [horizon, B, 4] (at first the current u.values in every row); u.values = row 0 of the blend and
+        `rollout(hold)`; the nominal becomes the blend shifted one row, its last row repeated.  nsteps must be a multiple of hold,
+        hold of traj_every.  sigma: a scalar or the three surface deviations (deg).  x.values, u.values and status advance as under
+        `rollout`.  Returns the samples [nsteps // traj_every, 18, B] (None without traj_every); with return_info also
+        dict(min_cost [periods, B], ess [periods, B])."""
+        nsteps, horizon, hold, samples = int(nsteps), int(horizon), int(hold), int(samples)
+        if hold < 1 or horizon < 1 or samples < 1:
+            raise ValueError("horizon, hold and samples must be >= 1")
+        if nsteps < 1 or nsteps % hold:
+            raise ValueError(f"nsteps ({nsteps}) must be a positive multiple of hold ({hold})")
+        if traj_every and hold % int(traj_every):
+            raise ValueError(f"hold ({hold}) must be a multiple of traj_every ({traj_every})")
+        if not (float(lam) > 0.0 and np.isfinite(float(lam))):
+            raise ValueError(f"lam must be finite and > 0 (got {lam})")
+        sig = torch.as_tensor(sigma, dtype=torch.float64, device=self.device)
+        if sig.dim() > 1 or (sig.dim() == 1 and sig.shape[0] != 3):
+            raise ValueError(f"sigma is a scalar or the three surface deviations, not {tuple(sig.shape)}")
+        g = torch.Generator(device=self.device)
+        g.manual_seed(int(seed))
+        nominal = self._u.t().unsqueeze(0).repeat(horizon, 1, 1)
+        trajs, mins, ess = [], [], []
+        for _ in range(nsteps // hold):
+            noise = sig * torch.randn((horizon, samples, self.B, 3), generator=g, device=self.device, dtype=torch.float64)
+            u, info = self.calc_MPPI_action(p_dem, q_dem, r_dem, nominal, noise, hold=hold, lam=lam, **weights)
+            self.set_input(u[0])
+            trajs.append(self.rollout(hold, traj_every=traj_every))
+            nominal = torch.cat((u[1:], u[-1:]), 0)
+            mins.append(info["min_cost"])
+            ess.append(info["ess"])
+        traj = torch.cat(trajs, 0) if traj_every else None
+        return (traj, dict(min_cost=torch.stack(mins), ess=torch.stack(ess))) if return_info else traj
+
     # ------------------------------------------------------------------ env.py:152-193
     def _get_mpc_x(self):
         return self._x[P.mpc_x_idx].t()

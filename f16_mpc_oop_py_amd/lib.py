@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("F16HIP_SO", os.path.join(HERE, "libf16hip.so"))   # override only for A/B experiments
-SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_debug.hip", "f16_tables.cpp"]
+SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_mppi.hip", "f16_debug.hip", "f16_tables.cpp"]
 # the expression-exact (F16_STRICT) build of the plant alone: checker-side evidence that the device lookups and the plant
 # reproduce the reference bit for bit where no libm call is involved (tests/test_gpu_dynamics.py); never used by the product
 STRICT_SO_PATH = os.path.join(HERE, "libf16hip_strict.so")
@@ -54,6 +54,21 @@ class MPCWeights(ctypes.Structure):
     _fields_ = [("q_from_cd", ctypes.c_int), ("Q", ctypes.c_double * 81), ("R", ctypes.c_double * 9),
                 ("x_lb", ctypes.c_double * 9), ("x_ub", ctypes.c_double * 9), ("u_lb", ctypes.c_double * 3), ("u_ub", ctypes.c_double * 3),
                 ("udot_lb", ctypes.c_double * 3), ("udot_ub", ctypes.c_double * 3)]
+
+
+class CostWeights(ctypes.Structure):
+    """include/f16_hip.h `f16_cost_weights`: the diagonal weights of f16_rollout_cost (22 doubles, all finite and >= 0)."""
+    _fields_ = [("q", ctypes.c_double * 9), ("qf", ctypes.c_double * 9), ("r", ctypes.c_double * 3), ("pen", ctypes.c_double)]
+
+
+def make_cost_weights(q=None, qf=None, r=None, penalty=0.0):
+    """CostWeights with the defaults q = qf = ones(9), r = ones(3): the diagonals of the reference's Q = Cd'Cd (Cd = I9) and R = I3."""
+    import numpy as np
+    w = CostWeights()
+    for name, v, n in (("q", q, 9), ("qf", qf, 9), ("r", r, 3)):
+        getattr(w, name)[:] = [1.0] * n if v is None else list(np.asarray(v, dtype=np.float64).reshape(n))
+    w.pen = float(penalty)
+    return w
 
 
 def make_weights(Q=None, R=None, x_lb=None, x_ub=None, u_lb=None, u_ub=None, udot_lb=None, udot_ub=None):
@@ -227,6 +242,10 @@ def load():
     if hasattr(L, "f16_rollout_sched"):      # (absent from an older library loaded through F16HIP_SO for an A/B run: calling it then raises)
         L.f16_rollout_sched.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
         L.f16_rollout_lqr_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
+    if hasattr(L, "f16_rollout_cost"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        L.f16_rollout_cost.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
+    if hasattr(L, "f16_mppi_blend"):         # (not part of the strict build, which holds the plant sources alone)
+        L.f16_mppi_blend.argtypes = [vp, vp, vp, d, vp, vp, vp, l, l, l, l, i, vp]
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
     L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]

@@ -157,6 +157,58 @@ int f16_rollout_sched(f16_ctx *ctx, double *x, const double *u_seq, double *traj
 int f16_rollout_lqr_sched(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, double *traj,
                           double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
                           double xcg, int fi_flag, unsigned flags, void *stream);
+/* SCORED rollouts under sampled command schedules, as ONE launch: the engine of a sampling-based nonlinear MPC (MPPI, model-predictive
+ * path integral control) and of any Monte-Carlo study that wants one number per trajectory.  K = B / B0 perturbed command sequences
+ * per aircraft go through the nonlinear plant; each lane accumulates its trajectory cost in registers, so neither [T][18][B] samples
+ * nor K copies of the initial state are ever stored.
+ *   Lanes: lane j (0 <= j < B) is sample j / B0 of aircraft j % B0 and starts from column j % B0 of x0[18][ld0], which is only read.
+ *     B0 == B is an ordinary scored rollout.
+ *   u_seq[S][4][ld], S = ceil(nsteps / hold): layout and zero-order hold exactly as in f16_rollout_sched (step t uses row t / hold).
+ *   x_ref[9][ld0]: one reference per aircraft in MPC-state order (parameters.py:135: phi theta alpha beta p q r lf1 lf2);
+ *     u_ref[3][ld0] (may be NULL = 0): reference of the three surface commands.
+ *   h_w (host): diagonal weights, every entry finite and >= 0.
+ *   cost[ld] (required):
+ *       J = sum over the steps t = 0..nsteps-1 the lane TAKES of
+ *               [ sum_i r[i] (u_t[1+i] - u_ref[i])^2  +  sum_k q[k] (x9_{t+1}[k] - x_ref[k])^2 ]
+ *         + pen * (number of steps the lane does not take because the envelope check has frozen it)
+ *         + sum_k qf[k] (x9_end[k] - x_ref[k])^2
+ *     with x9_{t+1} the MPC states after step t and u_t the row in use at step t, accumulated in fp64 in step order (the command term
+ *     is formed once per row).  The thrust command is not penalised: no controller of the reference commands it.  A non-finite state
+ *     or command makes J non-finite by ordinary arithmetic.  nsteps == 0 reads no row and writes the terminal term of x0 alone
+ *     (x_end = x0, status = F16_ST_NONFINITE or 0).
+ *   x_end[18][ld] (may be NULL): the final state of every lane.  traj (may be NULL), traj_every: as in f16_rollout_sched, over the B lanes.
+ *   status[ld] (may be NULL) is an OUTPUT: every lane starts from 0, it is not sticky -- the one deliberate difference from the
+ *     siblings (K samples of one aircraft have no status column to start from).
+ * Everything else follows f16_rollout_sched: envelope freeze and F16_FLAG_NO_ENVELOPE (then no penalty is ever added), the status bits
+ * including F16_ST_ENV_STATE and F16_ST_NONFINITE, NaN / infinite commands through the actuator models.
+ * F16_EINVAL: NULL x0 / u_seq / x_ref / h_w / cost, hold < 1, nsteps < 0, ld < B, ld0 < B0, B0 < 1 while B > 0, B % B0 != 0, traj with
+ * traj_every < 1 or nsteps % traj_every != 0, a negative or non-finite weight.  B == 0 is a no-op.
+ * Kernels: F16_FLAG_ONE_LANE selects the one-kernel-for-every-size path; otherwise the one-lane-per-aircraft kernels of f16_rollout's
+ * launch rules by the number of LANES B (64 / 128 / 256 / 512 lanes per workgroup, the integer table image at 512 in the default
+ * build).  The states (x_end, traj, status) then equal f16_rollout_sched's on the K-fold replicated initial states BIT FOR BIT
+ * wherever both run the same kernel: every lofi size, hifi above 16,384 lanes, and F16_FLAG_ONE_LANE.  The four-lanes-per-aircraft and
+ * four-wavefront kernels that f16_rollout_sched runs for hifi batches of at most 16,384 have no scored twin (their state is split
+ * over four role waves), so BELOW 16,385 LANES THE SCORED ENTRY RUNS A DIFFERENT, SLOWER KERNEL than f16_rollout_sched (the 64-lane
+ * one-lane kernel: same terms, ulp-level differences); scoring on the split kernels is a possible follow-up.  cost has the same bits
+ * whether or not x_end / traj are given.  Nothing is allocated and the weights travel in the kernel argument block: the call can be
+ * captured into a graph. */
+typedef struct f16_cost_weights { double q[9], qf[9], r[3], pen; } f16_cost_weights;   /* host; all entries >= 0 and finite */
+int f16_rollout_cost(f16_ctx *ctx, const double *x0, long B0, long ld0, const double *u_seq,
+                     const double *x_ref, const double *u_ref, const f16_cost_weights *h_w,
+                     double *cost, double *x_end, double *traj, int32_t *status,
+                     long B, long ld, int nsteps, int hold, int traj_every,
+                     double dt, double xcg, int fi_flag, unsigned flags, void *stream);
+/* The softmin blend of an MPPI step over the costs f16_rollout_cost wrote.  For aircraft a and its samples k = 0..K-1 (K = B / B0) at
+ * lanes k * B0 + a:  m = the minimum over the FINITE cost,  w_k = exp(-(J_k - m) / lambda) for finite J_k and 0 otherwise,
+ *     u_blend[nrows][4][ld0] = sum_k w_k u_seq[row][c][k * B0 + a] / sum_k w_k        (all four commands; u_seq[nrows][4][ld])
+ * summed over k ascending in plain fp64, so the result does not depend on the launch geometry.  An aircraft without any finite cost
+ * gets sample 0's rows.  w_out[ld] (may be NULL): the normalised weights (0 everywhere for such an aircraft); stats[2][ld0] (may be
+ * NULL): m and the effective sample size (sum w)^2 / sum w^2, both 0 when no cost is finite.
+ * F16_EINVAL: lambda <= 0 or not finite, NULL cost / u_seq / u_blend, B0 < 1 while B > 0, B % B0 != 0, ld < B, ld0 < B0, nrows < 0.
+ * B == 0 is a no-op; nrows == 0 writes w_out / stats only.  Nothing is allocated. */
+int f16_mppi_blend(f16_ctx *ctx, const double *cost, const double *u_seq, double lambda,
+                   double *u_blend, double *w_out, double *stats,
+                   long B, long ld, long B0, long ld0, int nrows, void *stream);
 /* The reference's LINEAR-model closed loops as ONE launch (9-state reduced model, 3 inputs; one lane per aircraft, its matrices in
  * registers):   per step   u = -K (x_ref - x) + u0,   x = Ad x + Bd u
  *   test_env_mk2.py:46-62 `LQR(linear=True)` (what main.py:35 runs): the frozen model ssr.Ad / ssr.Bd under env.py:360-371
