@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <math.h>
+#include <stdarg.h>
 
 #include <mutex>
 #include <vector>
@@ -860,22 +861,26 @@ extern "C" int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, c
   return f16_lqr_batch_w(ctx, Ad, Bd, Cd, nullptr, K, Pare, status, B, ld, stream);
 }
 
+// F16_EINVAL with a formatted message (the closed-loop entry points name themselves in theirs)
+__attribute__((format(printf, 1, 2))) static int einval(const char *fmt, ...) {
+  char msg[384];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, sizeof msg, fmt, ap);
+  va_end(ap);
+  return set_error(F16_EINVAL, msg);
+}
+
 static int rollout_lqr_relin_launch(const char *name, f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
                                     const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
                                     long B, long ld, int nsteps, int hold, int traj_every, unsigned track_mask, double eps, double dt,
                                     double xcg, int fi_flag, unsigned flags, void *stream) {
-  char msg[160];
-  if (!ctx || !x || !u || B < 0 || ld < B) { snprintf(msg, sizeof msg, "bad argument to %s", name); return set_error(F16_EINVAL, msg); }
-  if (nsteps < 1 || traj_every < 1 || nsteps % traj_every != 0) {
-    snprintf(msg, sizeof msg, "%s: nsteps must be >= 1 and a multiple of traj_every >= 1", name);
-    return set_error(F16_EINVAL, msg);
-  }
-  if (hold < 1) { snprintf(msg, sizeof msg, "%s: hold must be >= 1", name); return set_error(F16_EINVAL, msg); }
-  if (!(eps > 0)) { snprintf(msg, sizeof msg, "%s: eps must be > 0", name); return set_error(F16_EINVAL, msg); }
-  if ((track_mask & 0x1FFu) && !x_ref) {
-    snprintf(msg, sizeof msg, "%s: x_ref is NULL but track_mask selects entries", name);
-    return set_error(F16_EINVAL, msg);
-  }
+  if (!ctx || !x || !u || B < 0 || ld < B) return einval("bad argument to %s", name);
+  if (nsteps < 1 || traj_every < 1 || nsteps % traj_every != 0)
+    return einval("%s: nsteps must be >= 1 and a multiple of traj_every >= 1", name);
+  if (hold < 1) return einval("%s: hold must be >= 1", name);
+  if (!(eps > 0)) return einval("%s: eps must be > 0", name);
+  if ((track_mask & 0x1FFu) && !x_ref) return einval("%s: x_ref is NULL but track_mask selects entries", name);
   RelinArgs a{};
   mpc_default_prob(&a.pb);
   if (h_w)
@@ -886,6 +891,7 @@ static int rollout_lqr_relin_launch(const char *name, f16_ctx *ctx, double *x, d
   a.B = B; a.ld = ld; a.nsteps = nsteps; a.every = traj_every; a.hold = hold < nsteps ? hold : nsteps; a.track = track_mask & 0x1FFu;
   a.eps = eps; a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   hipLaunchKernelGGL(k_rollout_lqr_relin, dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
+  char msg[64];
   snprintf(msg, sizeof msg, "%s launch", name);
   return hip_check(hipGetLastError(), msg);
 }
@@ -1306,13 +1312,62 @@ extern "C" int f16_mpc_plan_solve_w(f16_mpc_plan *p, const double *x, const doub
   return F16_OK;
 }
 
-// What the four closed-loop entry points share behind their argument checks: the counters (and, re-linearised, the device copy of
-// the weights) of the plan's first call, the warm-start switch, the launch.  nctrl control steps of `hold` plant steps of `dt` each.
-static int rollout_mpc_common(f16_mpc_plan *p, RolloutMpcCall &c, int nctrl, int hold, double dt, void *stream) {
+// One closed MPC loop as its entry point states it.  The six f16_rollout_mpc* calls are one launch (k_rollout_mpc, f16_mpc_wave.hip)
+// and differ in these values only; rollout_mpc_loop checks them in one order and fills RolloutMpcCall.
+constexpr int MPC_LOOP_NEVER = 0x7fffffff;      // traj_every of a loop without traj (pair_finish decides and indexes the traj stores
+                                                // with it, nothing else), and dem_hold of a constant demand: row 0 for every control step
+struct MpcLoop {
+  const char *name;                    // the entry point, for its messages
+  double *x, *u;
+  const double *dem;                   // [ceil(nctrl / dem_hold)][3][ld]
+  double *traj, *cmd_traj;
+  int32_t *iters_traj, *status;
+  int nctrl, traj_every;               // control steps; the sampling interval of traj in PLANT steps
+  double xcg;
+  int fi;
+  unsigned flags;
+  // what an entry point leaves alone is the value of the oldest call, f16_rollout_mpc:
+  bool allow_zero = false;             // nctrl = 0 is a no-op behind the checks (f16_rollout_mpc / _relin; the others: F16_EINVAL)
+  int hold = 1;                        // plant steps per control step
+  double dt = 0.0;                     // the plant's Euler step: hold x dt = the plan's dt
+  int dem_hold = MPC_LOOP_NEVER;       // control steps per demand row
+  bool relin = false;                  // the model re-derived at every control step (k_rollout_mpc<true>): takes and marks a foreign plan
+  double eps = 0.0;                    // relin: the linearisation step
+  double *model_traj = nullptr;        // relin: [nctrl / model_every][189][ld] or null
+  int model_every = 1;                 // relin: in control steps
+  bool models_with_traj = false;       // f16_rollout_mpc_relin: the models are sampled with the states -- model_every IS traj_every
+};
+
+static int rollout_mpc_loop(f16_mpc_plan *p, const MpcLoop &d, void *stream) {
+  if (!p || !d.x || !d.u || !d.dem) return einval("bad argument to %s", d.name);
+  if (d.dem_hold < 1) return einval("%s: dem_hold must be >= 1", d.name);
+  if (!d.relin && p->relin_model)
+    return einval("%s: a re-linearised loop overwrote this plan's model; create a new plan for the frozen model", d.name);
+  if (p->N > WAVE_MAXN || p->s.scaling <= 0)
+    return einval("%s needs a plan with hzn <= 30 and equilibrated solves (scaling > 0); other plans run the host loop "
+                  "(a solve + f16_rollout per control step)", d.name);
+  const long long nplant = (long long)d.nctrl * d.hold;
+  if (d.nctrl < (d.allow_zero ? 0 : 1) || d.hold < 1 || nplant > 0x7fffffffLL)
+    return einval("%s: the control steps must be >= %d, hold >= 1 and their product < 2^31", d.name, d.allow_zero ? 0 : 1);
+  if (!(fabs((double)d.hold * d.dt - p->dt) <= 1e-12 * p->dt))
+    return einval("%s: hold x dt (%d x %.17g) is not the plan's dt (%.17g) -- the plan's model and rate rows are discretised at the "
+                  "control period", d.name, d.hold, d.dt, p->dt);
+  const bool sampled = d.traj || (d.models_with_traj && d.model_traj);
+  if (sampled && (d.traj_every < 1 || nplant % d.traj_every != 0))
+    return einval("%s: the plant steps (nctrl x hold) must be a multiple of traj_every >= 1 when %s is given", d.name,
+                  d.models_with_traj ? "traj or model_traj" : "traj");
+  const int model_every = !d.models_with_traj ? d.model_every : sampled ? d.traj_every : 1;
+  if (d.relin) {
+    if (!(d.eps > 0)) return einval("%s: the linearisation step eps must be > 0", d.name);
+    if (model_every < 1 || (d.model_traj && d.nctrl % model_every != 0))
+      return einval("%s: model_every must be >= 1, and divide nctrl when model_traj is given", d.name);
+  }
+  if (d.nctrl == 0) return F16_OK;      // (allow_zero: nothing allocated, the plan not marked)
+  // the counters (and, re-linearised, the device copy of the weights) of the plan's first call
   if (!p->roll_sync) {
     if (int rc = hip_check(hipMalloc(&p->roll_sync, 8 + (size_t)p->B * sizeof(int32_t)), "hipMalloc f16_rollout_mpc counters")) return rc;
   }
-  if (c.relin && !p->relin_w) {
+  if (d.relin && !p->relin_w) {
     if (int rc = hip_check(hipMalloc(&p->relin_w, 99 * sizeof(double)), "hipMalloc f16_rollout_mpc_relin weights")) return rc;
     double h[99];
     for (int i = 0; i < 81; ++i) h[i] = p->a.pb.Q[i];
@@ -1320,8 +1375,12 @@ static int rollout_mpc_common(f16_mpc_plan *p, RolloutMpcCall &c, int nctrl, int
     if (int rc = hip_check(hipMemcpy(p->relin_w, h, sizeof(h), hipMemcpyHostToDevice), "f16_rollout_mpc_relin weights")) return rc;
   }
   p->last_stream = stream;
-  if (c.relin) p->relin_model = true;
-  c.sync = p->roll_sync; c.T = nctrl; c.hold = hold; c.dt = dt; c.wq = p->relin_w;
+  if (d.relin) p->relin_model = true;
+  RolloutMpcCall c{};
+  c.x = d.x; c.u = d.u; c.dem = d.dem; c.traj = d.traj; c.cmd_traj = d.cmd_traj; c.iters_traj = d.iters_traj; c.status = d.status;
+  c.sync = p->roll_sync; c.T = d.nctrl; c.every = d.traj ? d.traj_every : MPC_LOOP_NEVER; c.hold = d.hold; c.dem_hold = d.dem_hold;
+  c.dt = d.dt; c.xcg = d.xcg; c.fi = d.fi; c.flags = d.flags;
+  c.relin = d.relin; c.eps = d.eps; c.model_traj = d.model_traj; c.model_every = model_every; c.wq = p->relin_w;
   c.warm = p->warm_on ? p->warm : nullptr;
   c.warm_load = p->warm_on && p->have_prev;
   const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
@@ -1329,125 +1388,61 @@ static int rollout_mpc_common(f16_mpc_plan *p, RolloutMpcCall &c, int nctrl, int
   return rc;
 }
 
+// The entry points: each states what distinguishes it.  f16_rollout_mpc / _relin: the control period IS the plant step (hold = 1 at
+// the plan's own dt); _hold: `hold` plant steps of dt per control step (pair_finish, f16_mpc_wave.hip); _sched: control step c reads
+// row c / dem_hold of dem_seq[ceil(nctrl / dem_hold)][3][ld] (the ticket loop of k_rollout_mpc picks the row); _relin*: the model
+// re-derived at every control step, the weights the in-kernel QP build reads from memory, the model record.
 extern "C" int f16_rollout_mpc(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                int32_t *iters_traj, int32_t *status, int nsteps, int traj_every, double xcg, int fi_flag,
                                unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc");
-  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc: f16_rollout_mpc_relin overwrote this plan's model; create a new plan for the frozen model");
-  if (p->N > WAVE_MAXN || p->s.scaling <= 0)
-    return set_error(F16_EINVAL, "f16_rollout_mpc needs a plan with hzn <= 30 and equilibrated solves (scaling > 0); "
-                                 "other plans run the host loop (f16_mpc_plan_solve + f16_rollout per step)");
-  if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
-    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj is given");
-  if (nsteps == 0) return F16_OK;
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = traj ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  return rollout_mpc_common(p, c, nsteps, 1, p->dt, stream);      // (the control period IS the plant step)
+  MpcLoop d{"f16_rollout_mpc", x, u, dem, traj, cmd_traj, iters_traj, status, nsteps, traj_every, xcg, fi_flag, flags};
+  d.allow_zero = true; d.dt = p ? p->dt : 0.0;
+  return rollout_mpc_loop(p, d, stream);
 }
 
-// The closed loop with the model re-derived at every step (k_rollout_mpc<true>, f16_mpc_wave.hip): f16_rollout_mpc's launch with the
-// linearisation step, the model record and the weights the in-kernel QP build reads from memory.
 extern "C" int f16_rollout_mpc_relin(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                      int32_t *iters_traj, double *model_traj, int32_t *status, int nsteps, int traj_every, double eps,
                                      double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin");
-  if (p->N > WAVE_MAXN || p->s.scaling <= 0)
-    return set_error(F16_EINVAL, "f16_rollout_mpc_relin needs a plan with hzn <= 30 and equilibrated solves (scaling > 0); "
-                                 "other plans run the host loop (linearise + f16_mpc_batch + f16_rollout per step)");
-  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin: the linearisation step eps must be > 0");
-  if (nsteps < 0 || ((traj || model_traj) && (traj_every < 1 || nsteps % traj_every != 0)))
-    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj or model_traj is given");
-  if (nsteps == 0) return F16_OK;
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = (traj || model_traj) ? traj_every : nsteps + 1; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = c.every;
-  return rollout_mpc_common(p, c, nsteps, 1, p->dt, stream);
-}
-
-// The two loops at a control period of `hold` plant steps (pair_finish, f16_mpc_wave.hip): the argument rules they share.
-static int rollout_mpc_hold_check(const char *name, const f16_mpc_plan *p, const void *traj, int nctrl, int hold, int traj_every, double dt) {
-  char msg[256];
-  if (p->N > WAVE_MAXN || p->s.scaling <= 0) {
-    snprintf(msg, sizeof msg, "%s needs a plan with hzn <= 30 and equilibrated solves (scaling > 0)", name);
-    return set_error(F16_EINVAL, msg);
-  }
-  if (nctrl < 1 || hold < 1 || (long long)nctrl * hold > 0x7fffffffLL) {
-    snprintf(msg, sizeof msg, "%s: nctrl and hold must be >= 1 and nctrl x hold < 2^31", name);
-    return set_error(F16_EINVAL, msg);
-  }
-  if (!(fabs((double)hold * dt - p->dt) <= 1e-12 * p->dt)) {
-    snprintf(msg, sizeof msg, "%s: hold x dt (%d x %.17g) is not the plan's dt (%.17g) -- the plan's model and rate rows are "
-             "discretised at the control period", name, hold, dt, p->dt);
-    return set_error(F16_EINVAL, msg);
-  }
-  if (traj && (traj_every < 1 || (long long)nctrl * hold % traj_every != 0)) {
-    snprintf(msg, sizeof msg, "%s: nctrl x hold must be a multiple of traj_every >= 1 when traj is given", name);
-    return set_error(F16_EINVAL, msg);
-  }
-  return F16_OK;
+  MpcLoop d{"f16_rollout_mpc_relin", x, u, dem, traj, cmd_traj, iters_traj, status, nsteps, traj_every, xcg, fi_flag, flags};
+  d.allow_zero = true; d.dt = p ? p->dt : 0.0;
+  d.relin = true; d.eps = eps; d.model_traj = model_traj; d.models_with_traj = true;
+  return rollout_mpc_loop(p, d, stream);
 }
 
 extern "C" int f16_rollout_mpc_hold(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                     int32_t *iters_traj, int32_t *status, int nctrl, int hold, int traj_every, double dt,
                                     double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_hold");
-  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc_hold: a re-linearised loop overwrote this plan's model; create a new plan for the frozen model");
-  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_hold", p, traj, nctrl, hold, traj_every, dt)) return rc;
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+  MpcLoop d{"f16_rollout_mpc_hold", x, u, dem, traj, cmd_traj, iters_traj, status, nctrl, traj_every, xcg, fi_flag, flags};
+  d.hold = hold; d.dt = dt;
+  return rollout_mpc_loop(p, d, stream);
 }
 
 extern "C" int f16_rollout_mpc_relin_hold(f16_mpc_plan *p, double *x, double *u, const double *dem, double *traj, double *cmd_traj,
                                           int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold,
                                           int traj_every, int model_every, double dt, double eps, double xcg, int fi_flag,
                                           unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin_hold");
-  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_relin_hold", p, traj, nctrl, hold, traj_every, dt)) return rc;
-  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_hold: the linearisation step eps must be > 0");
-  if (model_every < 1 || (model_traj && nctrl % model_every != 0))
-    return set_error(F16_EINVAL, "f16_rollout_mpc_relin_hold: model_every must be >= 1, and divide nctrl when model_traj is given");
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags;
-  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = model_every;
-  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+  MpcLoop d{"f16_rollout_mpc_relin_hold", x, u, dem, traj, cmd_traj, iters_traj, status, nctrl, traj_every, xcg, fi_flag, flags};
+  d.hold = hold; d.dt = dt;
+  d.relin = true; d.eps = eps; d.model_traj = model_traj; d.model_every = model_every;
+  return rollout_mpc_loop(p, d, stream);
 }
 
-// The two loops under a demand schedule: control step c reads row c / dem_hold of dem_seq[ceil(nctrl / dem_hold)][3][ld] (the ticket
-// loop of k_rollout_mpc picks the row; pair_prepare / pair_model read it as they read a constant demand).  Everything else is the
-// _hold calls'.
 extern "C" int f16_rollout_mpc_sched(f16_mpc_plan *p, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
                                      int32_t *iters_traj, int32_t *status, int nctrl, int hold, int dem_hold, int traj_every, double dt,
                                      double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem_seq) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_sched");
-  if (dem_hold < 1) return set_error(F16_EINVAL, "f16_rollout_mpc_sched: dem_hold must be >= 1");
-  if (p->relin_model) return set_error(F16_EINVAL, "f16_rollout_mpc_sched: a re-linearised loop overwrote this plan's model; create a new plan for the frozen model");
-  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_sched", p, traj, nctrl, hold, traj_every, dt)) return rc;
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem_seq; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags; c.dem_hold = dem_hold;
-  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+  MpcLoop d{"f16_rollout_mpc_sched", x, u, dem_seq, traj, cmd_traj, iters_traj, status, nctrl, traj_every, xcg, fi_flag, flags};
+  d.hold = hold; d.dt = dt; d.dem_hold = dem_hold;
+  return rollout_mpc_loop(p, d, stream);
 }
 
 extern "C" int f16_rollout_mpc_relin_sched(f16_mpc_plan *p, double *x, double *u, const double *dem_seq, double *traj, double *cmd_traj,
                                            int32_t *iters_traj, double *model_traj, int32_t *status, int nctrl, int hold, int dem_hold,
                                            int traj_every, int model_every, double dt, double eps, double xcg, int fi_flag,
                                            unsigned flags, void *stream) {
-  if (!p || !x || !u || !dem_seq) return set_error(F16_EINVAL, "bad argument to f16_rollout_mpc_relin_sched");
-  if (dem_hold < 1) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: dem_hold must be >= 1");
-  if (int rc = rollout_mpc_hold_check("f16_rollout_mpc_relin_sched", p, traj, nctrl, hold, traj_every, dt)) return rc;
-  if (!(eps > 0)) return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: the linearisation step eps must be > 0");
-  if (model_every < 1 || (model_traj && nctrl % model_every != 0))
-    return set_error(F16_EINVAL, "f16_rollout_mpc_relin_sched: model_every must be >= 1, and divide nctrl when model_traj is given");
-  RolloutMpcCall c{};
-  c.x = x; c.u = u; c.dem = dem_seq; c.traj = traj; c.cmd_traj = cmd_traj; c.iters_traj = iters_traj; c.status = status;
-  c.every = traj ? traj_every : 0x7fffffff; c.xcg = xcg; c.fi = fi_flag; c.flags = flags; c.dem_hold = dem_hold;
-  c.relin = 1; c.eps = eps; c.model_traj = model_traj; c.model_every = model_every;
-  return rollout_mpc_common(p, c, nctrl, hold, dt, stream);
+  MpcLoop d{"f16_rollout_mpc_relin_sched", x, u, dem_seq, traj, cmd_traj, iters_traj, status, nctrl, traj_every, xcg, fi_flag, flags};
+  d.hold = hold; d.dt = dt; d.dem_hold = dem_hold;
+  d.relin = true; d.eps = eps; d.model_traj = model_traj; d.model_every = model_every;
+  return rollout_mpc_loop(p, d, stream);
 }
 
 extern "C" int f16_mpc_plan_warm_start(f16_mpc_plan *p, int on) {

@@ -148,23 +148,12 @@ def _relin_action_at_period(env, dem, hzn, period):
     """One solve of the re-linearised host loop at a control period of `period` seconds: linearise at the current (x.values,
     u.values[1:4]), ZOH at that period, calc_MPC_action on that model with the rate rows at the same period (OSQP's defaults).
     env.ssr, the environment's own frozen model, is not touched."""
-    import ctypes
-    from . import lib as _lib
     from .env import _vp
     env._linearise_na()
     Ac, Bc, Cc = env._lin
     Ad, Bd = torch.empty_like(Ac), torch.empty_like(Bc)
     env._check(env.lib.f16_c2d_batch(env.ctx.handle, _vp(Ac), _vp(Bc), _vp(Ad), _vp(Bd), env.B, env.B, period, env._stream))
-    s = _lib.QPSettings()
-    env.lib.f16_qp_default_settings(ctypes.byref(s))
-    ucmd = torch.empty((3, env.B), dtype=torch.float64, device=env.device)
-    info = torch.empty((4, env.B), dtype=torch.float64, device=env.device)
-    st = torch.zeros(env.B, dtype=torch.int32, device=env.device)
-    env._check(env.lib.f16_mpc_batch_w(env.ctx.handle, _vp(Ad), _vp(Bd), _vp(Cc), _vp(env._x), _vp(dem), None, None, _vp(ucmd), None,
-                                       _vp(info), _vp(st), env.B, env.B, int(hzn), period, ctypes.byref(s), env._stream))
-    env.last_status, env.last_iters = st, info[0]
-    env.status |= st
-    return ucmd.t()
+    return env._calc_MPC_action(dem, None, None, hzn, model=(Ad, Bd, Cc), period=period)
 
 
 def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, traj_every=1, gather=True, use_plan=True, stats=None,
@@ -223,10 +212,7 @@ def closed_loop_mpc_rollout(env, steps, hzn, p_dem=0.0, q_dem=0.0, r_dem=0.0, tr
             stats["iters_max_mean"] = float(its.max(1).values.mean())
         return all_gather_trajectories(traj) if gather else traj
     traj = torch.empty((T, 18, env.B), dtype=torch.float64, device=env.device)
-    dem = torch.empty((3, env.B), dtype=torch.float64, device=env.device)      # demands on the device once
-    if dem_seq is None:
-        for k, v in enumerate((p_dem, q_dem, r_dem)):
-            dem[k] = torch.as_tensor(v, dtype=torch.float64, device=env.device)
+    dem = env._demands(p_dem, q_dem, r_dem) if dem_seq is None else None      # demands on the device once
     it_sum = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
     it_max = torch.zeros((), dtype=torch.float64, device=env.device) if stats is not None else None
     nctrl = steps // ctrl_every

@@ -520,8 +520,11 @@ class F16Batch:
         x_ref[:, 4], x_ref[:, 5], x_ref[:, 6] = p_dem, q_dem, r_dem
         return -(K @ (x_ref - x).unsqueeze(-1)).squeeze(-1) + u0
 
-    def _demands(self, p_dem, q_dem, r_dem):
-        """(p, q, r) demands, scalars or [B], as a state-major [3,B] device tensor."""
+    def _demands(self, p_dem, q_dem=None, r_dem=None):
+        """(p, q, r) demands, scalars or [B], as a state-major [3,B] device tensor; a 2-D p_dem is that block already (demands on the
+        device: graph capture, the host loops) and is returned as it is."""
+        if torch.is_tensor(p_dem) and p_dem.dim() == 2:
+            return p_dem
         dem = torch.empty((3, self.B), dtype=torch.float64, device=self.device)
         for k, v in enumerate((p_dem, q_dem, r_dem)):
             if isinstance(v, (int, float)):
@@ -529,6 +532,14 @@ class F16Batch:
             else:
                 dem[k] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
         return dem
+
+    def _qp_settings(self, overrides=None):
+        """The library's default QP settings (OSQP's) with the fields of `overrides` replaced."""
+        s = _lib.QPSettings()
+        self.lib.f16_qp_default_settings(ctypes.byref(s))
+        for k, v in (overrides or {}).items():
+            setattr(s, k, v)
+        return s
 
     def _demand_schedule(self, p_dem, q_dem, r_dem):
         """Demands of which at least one is a time history [S] or [S, B] (scalars broadcast) -> state-major [S, 3, B] on the device;
@@ -685,16 +696,11 @@ class F16Batch:
             raise ValueError(f"nsteps ({nsteps}) must be a multiple of the sampling interval ({k})")
         mk = lambda want, rows: torch.empty((nsteps // k, rows, self.B), dtype=torch.float64, device=self.device) if want else None
         traj, u_traj, K_traj = mk(want_x, 18), mk(want_u, 3), mk(want_k, 27)
-        if hold is not None:
-            self._check(self.lib.f16_rollout_lqr_relin_sched(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
-                                                             ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj),
-                                                             _vp(self.status), self.B, self.B, nsteps, int(hold), k, int(mask),
-                                                             float(eps), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
-            return traj, u_traj, None if K_traj is None else K_traj.permute(0, 2, 1).reshape(nsteps // k, self.B, 3, 9)
-        self._check(self.lib.f16_rollout_lqr_relin(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
-                                                   ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj),
-                                                   _vp(self.status), self.B, self.B, nsteps, k, int(mask), float(eps), self.dt,
-                                                   self.xcg, self.fi_flag, self.flags, self._stream))
+        name, hold = ("f16_rollout_lqr_relin", []) if hold is None else ("f16_rollout_lqr_relin_sched", [int(hold)])
+        self._check(getattr(self.lib, name)(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(xref), _vp(u03),
+                                            ctypes.byref(w) if w else None, _vp(traj), _vp(u_traj), _vp(K_traj), _vp(self.status),
+                                            self.B, self.B, nsteps, *hold, k, int(mask), float(eps), self.dt, self.xcg, self.fi_flag,
+                                            self.flags, self._stream))
         return traj, u_traj, None if K_traj is None else K_traj.permute(0, 2, 1).reshape(nsteps // k, self.B, 3, 9)
 
     def rollout_linear(self, x9, Ad, Bd, K, x_ref, u0, nsteps, track=None, traj_every=None, state_major=False):
@@ -749,10 +755,7 @@ class F16Batch:
             plan_dt = ctrl_every * self.dt
             Ad, Bd = torch.empty_like(Ac), torch.empty_like(Bc)
             self._check(self.lib.f16_c2d_batch(self.ctx.handle, _vp(Ac), _vp(Bc), _vp(Ad), _vp(Bd), self.B, self.B, plan_dt, self._stream))
-        s = _lib.QPSettings()
-        self.lib.f16_qp_default_settings(ctypes.byref(s))
-        for k, v in (settings or {}).items():
-            setattr(s, k, v)
+        s = self._qp_settings(settings)
         h = ctypes.c_void_p()
         w = _lib.make_weights(**weights) if weights else None           # (utils.py:21 Q, R and the six bound vectors; fixed for the plan)
         self._check(self.lib.f16_mpc_plan_create_w(self.ctx.handle, ctypes.byref(h), _vp(Ad), _vp(Bd), _vp(Cd),
@@ -806,9 +809,7 @@ class F16Batch:
         if self.ssr is None:
             self.build_ssr()
         Ad, Bd, Cd = self.ssr
-        dem = torch.empty((3, self.B), dtype=torch.float64, device=self.device)
-        for k, v in enumerate((p_dem, q_dem, r_dem)):
-            dem[k] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
+        dem = self._demands(p_dem, q_dem, r_dem)
         n, rows = 3 * int(hzn), 15 * int(hzn)
         P, q, A = np.zeros((n, n)), np.zeros(n), np.zeros((rows, n))
         l, u = np.zeros(rows), np.zeros(rows)
@@ -821,56 +822,44 @@ class F16Batch:
         return P, q, A, l, u
 
     def _calc_MPC_action(self, p_dem, q_dem, r_dem, hzn, settings=None, return_info=False, relinearise=False,
-                         use_plan=False, weights=None, x_ref=None, ctrl_every=1):
+                         use_plan=False, weights=None, x_ref=None, ctrl_every=1, model=None, period=None):
         """First MPC move [B,3] (dh,da,dr commands) for demands p,q,r (scalars or [B]) over horizon hzn, from the
         frozen reduced model self.ssr (env.py:385-387) and the current state.  The QP of utils.py:21-167 is solved
         on the GPU by OSQP-style ADMM (the reference calls the `osqp` package, env.py:420-422).
         weights / x_ref: as in setup_OSQP (the solvers keep the reference's pattern of bounded rows; a plan fixes its weights at
         prepare_MPC, x_ref is per call).  ctrl_every = k > 1 (use_plan only): the plan of control period k * self.dt
-        (prepare_MPC(ctrl_every=k)) -- the solve of the multi-rate loop rollout_MPC(..., ctrl_every=k)."""
+        (prepare_MPC(ctrl_every=k)) -- the solve of the multi-rate loop rollout_MPC(..., ctrl_every=k).
+        model = (Ad, Bd, Cd) (state-major [81,B], [27,B], [81,B]) and period (seconds, default self.dt; the dt of the rate rows), not
+        with use_plan: the solve on that model instead of self.ssr, which is then neither read nor written."""
         if int(ctrl_every) != 1 and not use_plan:
             raise ValueError("ctrl_every > 1 is a property of a prepared plan: use_plan=True")
         # relinearise=True: SURVEY.md 8f-2 -- the reduced model is re-derived at the CURRENT state on every call (the
         # reference freezes it at construction, env.py:49-60; its test_env.py:625-687 loops re-linearise per step)
-        if self.ssr is None or relinearise:
-            self.build_ssr()
-        Ad, Bd, Cd = self.ssr
-        if torch.is_tensor(p_dem) and p_dem.dim() == 2:       # demands already on the device as [3,B] (graph capture)
-            dem = p_dem
-        else:
-            dem = torch.empty((3, self.B), dtype=torch.float64, device=self.device)
-            for k, v in enumerate((p_dem, q_dem, r_dem)):
-                if isinstance(v, (int, float)):
-                    dem[k].fill_(float(v))            # scalar demand: a fill kernel, no host-to-device copy
-                else:
-                    dem[k] = torch.as_tensor(v, dtype=torch.float64, device=self.device)
+        if model is None:
+            if self.ssr is None or relinearise:
+                self.build_ssr()
+            model = self.ssr
+        dem = self._demands(p_dem, q_dem, r_dem)
         ucmd = torch.empty((3, self.B), dtype=torch.float64, device=self.device)
         info = torch.empty((4, self.B), dtype=torch.float64, device=self.device)
         useq = torch.empty((3 * hzn, self.B), dtype=torch.float64, device=self.device) if return_info else None
         st = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        xr = self._soa(x_ref, 9) if x_ref is not None else None
         if use_plan:
-            if relinearise or settings or weights:
-                raise ValueError("a prepared plan fixes the model, the QP settings and the weights (prepare_MPC)")
+            if relinearise or settings or weights or model is not self.ssr or period is not None:
+                raise ValueError("a prepared plan fixes the model, the period, the QP settings and the weights (prepare_MPC)")
             self._frozen_plan(hzn, ctrl_every)
-            xr = self._soa(x_ref, 9) if x_ref is not None else None
             self._check(self.lib.f16_mpc_plan_solve_w(self._plan, _vp(self._x), _vp(dem), _vp(xr), _vp(ucmd), _vp(useq), _vp(info),
                                                       _vp(st), self._stream))
-            self.last_status, self.last_iters = st, info[0]
-            self.status |= st          # sticky: F16_ST_QP_INFEASIBLE / QP_MAXITER of ANY step stay visible after a closed loop
-            if return_info:
-                return ucmd.t(), dict(iters=info[0], r_prim=info[1], r_dual=info[2], rho=info[3], u_seq=useq.t(), status=st)
-            return ucmd.t()
-        s = _lib.QPSettings()
-        self.lib.f16_qp_default_settings(ctypes.byref(s))
-        for k, v in (settings or {}).items():
-            setattr(s, k, v)
-        w = _lib.make_weights(**weights) if weights else None
-        xr = self._soa(x_ref, 9) if x_ref is not None else None
-        self._check(self.lib.f16_mpc_batch_w(self.ctx.handle, _vp(Ad), _vp(Bd), _vp(Cd), _vp(self._x), _vp(dem), _vp(xr),
-                                             ctypes.byref(w) if w else None, _vp(ucmd), _vp(useq), _vp(info), _vp(st), self.B, self.B,
-                                             int(hzn), self.dt, ctypes.byref(s), self._stream))
+        else:
+            Ad, Bd, Cd = model
+            s = self._qp_settings(settings)
+            w = _lib.make_weights(**weights) if weights else None
+            self._check(self.lib.f16_mpc_batch_w(self.ctx.handle, _vp(Ad), _vp(Bd), _vp(Cd), _vp(self._x), _vp(dem), _vp(xr),
+                                                 ctypes.byref(w) if w else None, _vp(ucmd), _vp(useq), _vp(info), _vp(st), self.B, self.B,
+                                                 int(hzn), self.dt if period is None else period, ctypes.byref(s), self._stream))
         self.last_status, self.last_iters = st, info[0]
-        self.status |= st
+        self.status |= st          # sticky: F16_ST_QP_INFEASIBLE / QP_MAXITER of ANY step stay visible after a closed loop
         if return_info:
             return ucmd.t(), dict(iters=info[0], r_prim=info[1], r_dual=info[2], rho=info[3], u_seq=useq.t(), status=st)
         return ucmd.t()
@@ -906,104 +895,60 @@ class F16Batch:
         step is held over that step's whole horizon, so the call equals one call per row.  A 2-D p_dem with q_dem is None and
         r_dem is None stays a ready [3, B] block of constant demands.  dem_every without a history, too few rows and
         dem_every < 1 raise ValueError."""
-        nsteps, ctrl_every = int(nsteps), int(ctrl_every)
-        if ctrl_every < 1 or nsteps % ctrl_every:      # (argument checks first: they need no GPU)
-            raise ValueError(f"nsteps ({nsteps}) must be a multiple of ctrl_every ({ctrl_every}) >= 1")
-        dem_seq, dem_every = self._mpc_demand_rows(p_dem, q_dem, r_dem, dem_every, nsteps // ctrl_every)
-        if ctrl_every > 1 or dem_seq is not None:      # (a schedule at ctrl_every = 1: the same call with hold = 1)
-            return self._rollout_MPC_hold(nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps,
-                                          ctrl_every, model_every, dem_seq, dem_every)
-        if model_every is not None:
+        nsteps, hold = int(nsteps), int(ctrl_every)
+        if hold < 1 or nsteps % hold:      # (argument checks first: they need no GPU)
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of ctrl_every ({hold}) >= 1")
+        nctrl = nsteps // hold
+        dem_seq, dem_every = self._mpc_demand_rows(p_dem, q_dem, r_dem, dem_every, nctrl)
+        # f16_rollout_mpc / f16_rollout_mpc_relin, the oldest calls: zero steps are a no-op, the models are sampled with the states, and
+        # without relinearise the library alone checks the arguments.  (A schedule at ctrl_every = 1 is the _sched call with hold = 1.)
+        oldest = hold == 1 and dem_seq is None
+        if oldest and model_every is not None:
             raise ValueError("model_every belongs to ctrl_every > 1 (with ctrl_every = 1 the models follow traj_every)")
-        if relinearise:      # (argument checks first: they need no GPU)
-            if not float(eps) > 0.0:
-                raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
-            if int(hzn) < 1 or int(hzn) > 30:
-                raise ValueError(f"relinearise=True runs on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
+        model_every = int(traj_every or 1) if oldest else 1 if model_every is None else int(model_every)
+        if not oldest and nctrl < 1:
+            raise ValueError(f"ctrl_every={hold} needs nsteps >= {hold} (got {nsteps})")
+        if relinearise or not oldest:
             if nsteps < 0 or (traj_every and (int(traj_every) < 1 or nsteps % int(traj_every))):
                 raise ValueError(f"nsteps ({nsteps}) must be >= 0 and a multiple of traj_every ({traj_every})")
-        if not relinearise:
-            self._frozen_plan(hzn)
-        elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), 1):
-            self.prepare_MPC(hzn)
-        if relinearise and not self._plan_default_settings:
-            raise ValueError("relinearise=True needs a plan with equilibrated solves (scaling > 0)")
-        dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
-        traj = None
-        if traj_every:
-            assert nsteps % traj_every == 0
-            traj = torch.empty((nsteps // traj_every, 18, self.B), dtype=torch.float64, device=self.device)
-        cmd = torch.empty((nsteps, 3, self.B), dtype=torch.float64, device=self.device) if return_info else None
-        its = torch.empty((nsteps, self.B), dtype=torch.int32, device=self.device) if return_info else None
-        flags = self.flags | (_lib.F16_FLAG_HOLD_COMMAND if hold_command else 0)
-        if relinearise:
-            k = int(traj_every or 1)
-            model = torch.empty((nsteps // k, 189, self.B), dtype=torch.float64, device=self.device) if return_info else None
-            self._plan_foreign = nsteps > 0 or self._plan_foreign      # its model blocks are per-step models from here on, not self.ssr
-            self._check(self.lib.f16_rollout_mpc_relin(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
-                                                       _vp(model), _vp(self.status), nsteps, k, float(eps), self.xcg,
-                                                       self.fi_flag, flags, self._stream))
-            if return_info:
-                return traj, dict(cmd=cmd, iters=its, model=model)
-            return traj
-        self._check(self.lib.f16_rollout_mpc(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
-                                             _vp(self.status), int(nsteps), int(traj_every or 1), self.xcg, self.fi_flag, flags,
-                                             self._stream))
-        if return_info:
-            return traj, dict(cmd=cmd, iters=its)
-        return traj
+            if int(hzn) < 1 or int(hzn) > 30:
+                raise ValueError(f"relinearise=True, ctrl_every > 1 and demand histories run on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
+            if relinearise and not float(eps) > 0.0:
+                raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
+            if model_every < 1 or (relinearise and nctrl % model_every):
+                raise ValueError(f"the control steps ({nctrl}) must be a multiple of model_every ({model_every}) >= 1")
+        dem = self._demands(p_dem, q_dem, r_dem) if dem_seq is None else dem_seq
+        return self._rollout_mpc_call(hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command)
 
-    def _rollout_MPC_hold(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every, return_info, hold_command, relinearise, eps, hold,
-                          model_every, dem_seq=None, dem_every=None):
-        """rollout_MPC at a control period of `hold` > 1 plant steps, and under a demand schedule (dem_seq [S,3,B]; then hold >= 1)."""
-        nctrl = nsteps // hold
-        model_every = 1 if model_every is None else int(model_every)
-        if nctrl < 1:
-            raise ValueError(f"ctrl_every={hold} needs nsteps >= {hold} (got {nsteps})")
-        if traj_every and (int(traj_every) < 1 or nsteps % int(traj_every)):
-            raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
-        if int(hzn) < 1 or int(hzn) > 30:
-            raise ValueError(f"ctrl_every > 1 and demand histories run on the one-launch loop: 1 <= hzn <= 30 (got {hzn})")
-        if relinearise and not float(eps) > 0.0:
-            raise ValueError(f"relinearise=True needs a forward-difference step eps > 0 (got {eps})")
-        if model_every < 1 or (relinearise and nctrl % model_every):
-            raise ValueError(f"the control steps ({nctrl}) must be a multiple of model_every ({model_every}) >= 1")
+    def _rollout_mpc_call(self, hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command):
+        """rollout_MPC behind its argument checks: the plan, the outputs, the ONE call into the library.  nctrl control steps of `hold`
+        plant steps; dem [3,B], or [S,3,B] with dem_every control steps per row; the narrowest entry point that can run the loop."""
+        sched, nsteps = dem_every is not None, nctrl * hold
+        wide = sched or hold > 1      # the _hold / _sched parameter lists: nctrl, hold and the plant's dt beside the oldest calls' own
         if not relinearise:
             self._frozen_plan(hzn, hold)
         elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), hold):
             self.prepare_MPC(hzn, ctrl_every=hold)
-        if not self._plan_default_settings:
-            raise ValueError("ctrl_every > 1 and demand histories need a plan with equilibrated solves (scaling > 0)")
-        if dem_seq is not None:
-            dem = dem_seq
-        else:
-            dem = p_dem if (torch.is_tensor(p_dem) and p_dem.dim() == 2) else self._demands(p_dem, q_dem, r_dem)
+        if (relinearise or wide) and not self._plan_default_settings:
+            raise ValueError("relinearise=True, ctrl_every > 1 and demand histories need a plan with equilibrated solves (scaling > 0)")
         k = int(traj_every or 1)
-        traj = torch.empty((nsteps // k, 18, self.B), dtype=torch.float64, device=self.device) if traj_every else None
-        cmd = torch.empty((nctrl, 3, self.B), dtype=torch.float64, device=self.device) if return_info else None
-        its = torch.empty((nctrl, self.B), dtype=torch.int32, device=self.device) if return_info else None
+        assert nsteps % k == 0
+        new = lambda want, *shape, dtype=torch.float64: torch.empty(shape + (self.B,), dtype=dtype, device=self.device) if want else None
+        traj, cmd, its = new(traj_every, nsteps // k, 18), new(return_info, nctrl, 3), new(return_info, nctrl, dtype=torch.int32)
+        model = new(return_info and relinearise, nctrl // model_every, 189)
         flags = self.flags | (_lib.F16_FLAG_HOLD_COMMAND if hold_command else 0)
         if relinearise:
-            model = torch.empty((nctrl // model_every, 189, self.B), dtype=torch.float64, device=self.device) if return_info else None
-            self._plan_foreign = True
-            if dem_seq is not None:
-                self._check(self.lib.f16_rollout_mpc_relin_sched(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd),
-                                                                 _vp(its), _vp(model), _vp(self.status), nctrl, hold, dem_every, k,
-                                                                 model_every, self.dt, float(eps), self.xcg, self.fi_flag, flags,
-                                                                 self._stream))
-                return (traj, dict(cmd=cmd, iters=its, model=model)) if return_info else traj
-            self._check(self.lib.f16_rollout_mpc_relin_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd),
-                                                            _vp(its), _vp(model), _vp(self.status), nctrl, hold, k, model_every, self.dt,
-                                                            float(eps), self.xcg, self.fi_flag, flags, self._stream))
-            return (traj, dict(cmd=cmd, iters=its, model=model)) if return_info else traj
-        if dem_seq is not None:
-            self._check(self.lib.f16_rollout_mpc_sched(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
-                                                       _vp(self.status), nctrl, hold, dem_every, k, self.dt, self.xcg, self.fi_flag,
-                                                       flags, self._stream))
-            return (traj, dict(cmd=cmd, iters=its)) if return_info else traj
-        self._check(self.lib.f16_rollout_mpc_hold(self._plan, _vp(self._x), _vp(self._u), _vp(dem), _vp(traj), _vp(cmd), _vp(its),
-                                                  _vp(self.status), nctrl, hold, k, self.dt, self.xcg, self.fi_flag, flags, self._stream))
-        return (traj, dict(cmd=cmd, iters=its)) if return_info else traj
+            self._plan_foreign = nctrl > 0 or self._plan_foreign      # its model blocks are per-step models from here on, not self.ssr
+        # the six parameter lists of include/f16_hip.h are this one list; an entry point takes the entries that apply to it
+        name = "f16_rollout_mpc" + ("_relin" if relinearise else "") + ("_sched" if sched else "_hold" if wide else "")
+        args = [v for v, taken in (
+            (self._plan, True), (_vp(self._x), True), (_vp(self._u), True), (_vp(dem), True), (_vp(traj), True), (_vp(cmd), True),
+            (_vp(its), True), (_vp(model), relinearise), (_vp(self.status), True), (nctrl, True), (hold, wide), (dem_every, sched),
+            (k, True), (model_every, wide and relinearise), (self.dt, wide), (float(eps), relinearise), (self.xcg, True),
+            (self.fi_flag, True), (flags, True), (self._stream, True)) if taken]
+        self._check(getattr(self.lib, name)(*args))
+        info = dict(cmd=cmd, iters=its, **(dict(model=model) if relinearise else {}))
+        return (traj, info) if return_info else traj
 
     def _calc_constr_checking_hzn(self, max_hzn=150, settings=None, return_info=False):
         """env.py:426-436: the first move of calc_MPC_action(0, 0, 0, N) for every horizon N = 1..max_hzn (the reference
@@ -1016,10 +961,7 @@ class F16Batch:
         ucmd = torch.empty((max_hzn, 3, self.B), dtype=torch.float64, device=self.device)
         info = torch.empty((max_hzn, 4, self.B), dtype=torch.float64, device=self.device)
         st = torch.zeros((max_hzn, self.B), dtype=torch.int32, device=self.device)
-        s = _lib.QPSettings()
-        self.lib.f16_qp_default_settings(ctypes.byref(s))
-        for k, v in (settings or {}).items():
-            setattr(s, k, v)
+        s = self._qp_settings(settings)
         self._check(self.lib.f16_mpc_hzn_sweep(self.ctx.handle, _vp(Ad), _vp(Bd), _vp(Cd), _vp(self._x), _vp(dem), _vp(ucmd),
                                                _vp(info), _vp(st), self.B, self.B, 1, int(max_hzn), self.dt, ctypes.byref(s),
                                                self._stream))
