@@ -1076,53 +1076,49 @@ static Geometry geometry(long B, int fi) {
   return g;
 }
 
-#define LAUNCH_BY_BLOCK(KERN, g, stream, args)                                       \
-  do {                                                                               \
-    if ((g).block == 64) hipLaunchKernelGGL(KERN<64>, dim3((g).grid), dim3(64), 0, stream, args);        \
-    else if ((g).block == 128) hipLaunchKernelGGL(KERN<128>, dim3((g).grid), dim3(128), 0, stream, args); \
-    else if ((g).block == 256) hipLaunchKernelGGL(KERN<256>, dim3((g).grid), dim3(256), 0, stream, args); \
-    else hipLaunchKernelGGL(KERN<512>, dim3((g).grid), dim3(512), 0, stream, args);                       \
-  } while (0)
-// same; the lofi model gets an instantiation with the fidelity fixed at compile time (3.94 vs 4.6 ms per 1000 steps at
-// B=4096).  For hifi the run-time-flag kernel measured FASTER than a compile-time one (4.59 vs 4.65 ms; 5.31 vs 4.85 G
-// steps/s at B=262144: the scheduler does worse on the merged basic block), so hifi keeps the run-time path.
-#define LAUNCH_BY_BLOCK_FI(KERN, g, stream, args)                                                              \
-  do {                                                                                                         \
-    const int fi_ = (args).fi;                                                                                  \
-    if ((g).block == 64) {                                                                                     \
-      if (fi_ == 0) hipLaunchKernelGGL((KERN<64, 0>), dim3((g).grid), dim3(64), 0, stream, args);             \
-      else hipLaunchKernelGGL((KERN<64, -1>), dim3((g).grid), dim3(64), 0, stream, args);                      \
-    } else if ((g).block == 128) {                                                                             \
-      if (fi_ == 0) hipLaunchKernelGGL((KERN<128, 0>), dim3((g).grid), dim3(128), 0, stream, args);           \
-      else hipLaunchKernelGGL((KERN<128, -1>), dim3((g).grid), dim3(128), 0, stream, args);                    \
-    } else if ((g).block == 256) {                                                                             \
-      if (fi_ == 0) hipLaunchKernelGGL((KERN<256, 0>), dim3((g).grid), dim3(256), 0, stream, args);           \
-      else hipLaunchKernelGGL((KERN<256, -1>), dim3((g).grid), dim3(256), 0, stream, args);                    \
-    } else {                                                                                                   \
-      if (fi_ == 0) hipLaunchKernelGGL((KERN<512, 0>), dim3((g).grid), dim3(512), 0, stream, args);           \
-      else hipLaunchKernelGGL((KERN<512, -1>), dim3((g).grid), dim3(512), 0, stream, args);                    \
-    }                                                                                                          \
-  } while (0)
+// Geometry::block as a compile-time constant: f(std::integral_constant<int, BLOCK>) for the workgroup size of g
+template <typename F>
+static void by_block(const Geometry &g, F f) {
+  if (g.block == 64) f(std::integral_constant<int, 64>{});
+  else if (g.block == 128) f(std::integral_constant<int, 128>{});
+  else if (g.block == 256) f(std::integral_constant<int, 256>{});
+  else f(std::integral_constant<int, 512>{});
+}
 
 static int check_common(f16_ctx *ctx, const void *p0, const void *p1, long B, long ld) {
   if (!ctx || !p0 || !p1 || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument (NULL pointer, B < 0 or ld < B)");
   return F16_OK;
 }
 
+// what every launcher of this file fills alike (ARGS: DynArgs or one of its rollout extensions; the rest stays zero)
+template <typename ARGS>
+static ARGS base_args(const f16_ctx *ctx, long B, long ld, double xcg, int fi_flag, unsigned flags, int32_t *status) {
+  ARGS a{};
+  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.status = status;
+  a.B = B; a.ld = ld; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  return a;
+}
+
 }  // namespace f16
 
 using namespace f16;
 
+// (k_xdot: the lofi model gets an instantiation with the fidelity fixed at compile time (3.94 vs 4.6 ms per 1000 steps at
+// B=4096).  For hifi the run-time-flag kernel measured FASTER than a compile-time one (4.59 vs 4.65 ms; 5.31 vs 4.85 G
+// steps/s at B=262144: the scheduler does worse on the merged basic block), so hifi keeps the run-time path.)
 extern "C" int f16_xdot_batch(f16_ctx *ctx, const double *x, const double *u, double *xdot, int32_t *status, long B,
                               long ld, double xcg, int fi_flag, unsigned flags, void *stream) {
   if (int rc = check_common(ctx, x, xdot, B, ld)) return rc;
   if (!u) return set_error(F16_EINVAL, "u is NULL");
   if (B == 0) return F16_OK;
-  DynArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.x = x; a.u = u; a.out = xdot; a.status = status;
-  a.B = B; a.ld = ld; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  Geometry g = geometry(B, fi_flag);
-  LAUNCH_BY_BLOCK_FI(k_xdot, g, (hipStream_t)stream, a);
+  DynArgs a = base_args<DynArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
+  a.x = x; a.u = u; a.out = xdot;
+  const Geometry g = geometry(B, fi_flag);
+  by_block(g, [&](auto block) {
+    constexpr int BLOCK = decltype(block)::value;
+    if (fi_flag == 0) hipLaunchKernelGGL((k_xdot<BLOCK, 0>), dim3(g.grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((k_xdot<BLOCK, -1>), dim3(g.grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  });
   return hip_check(hipGetLastError(), "f16_xdot_batch launch");
 }
 
@@ -1130,79 +1126,78 @@ extern "C" int f16_nlplant_batch(f16_ctx *ctx, const double *xu, double *xdot, i
                                  double xcg, int fi_flag, unsigned flags, void *stream) {
   if (int rc = check_common(ctx, xu, xdot, B, ld)) return rc;
   if (B == 0) return F16_OK;
-  DynArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.x = xu; a.out = xdot; a.status = status;
-  a.B = B; a.ld = ld; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
+  DynArgs a = base_args<DynArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
+  a.x = xu; a.out = xdot;
   if (B <= 256) {
     hipLaunchKernelGGL((k_nlplant<64, false>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   } else {
-    Geometry g = geometry(B, fi_flag);
-    if (g.block == 64) hipLaunchKernelGGL((k_nlplant<64, true>), dim3(g.grid), dim3(64), 0, (hipStream_t)stream, a);
-    else if (g.block == 128) hipLaunchKernelGGL((k_nlplant<128, true>), dim3(g.grid), dim3(128), 0, (hipStream_t)stream, a);
-    else if (g.block == 256) hipLaunchKernelGGL((k_nlplant<256, true>), dim3(g.grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_nlplant<512, true>), dim3(g.grid), dim3(512), 0, (hipStream_t)stream, a);
+    const Geometry g = geometry(B, fi_flag);
+    by_block(g, [&](auto block) {
+      constexpr int BLOCK = decltype(block)::value;
+      hipLaunchKernelGGL((k_nlplant<BLOCK, true>), dim3(g.grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
+    });
   }
   return hip_check(hipGetLastError(), "f16_nlplant_batch launch");
 }
 
+// The launch rules of the five plant rollouts, in this one place.
 // LQR = true: the closed loop of f16_rollout_lqr (same launch rules; the one-lane kernels keep K[i][4..6] and the demands in
 // lane-indexed LDS slots, which a 512-lane workgroup has room for only beside the integer table image)
 // SCHED = true: the same rules for f16_rollout_sched / f16_rollout_lqr_sched -- every kernel has a scheduled twin, so a schedule
 // never moves a batch to another kernel family.
-template <int BLOCK, bool LQR, bool SCHED>
-static void launch_lanes(int grid, hipStream_t st, const RolloutArgs<SCHED> &a) {
-  if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED>), dim3(grid), dim3(BLOCK), 0, st, a);
-  else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED>), dim3(grid), dim3(BLOCK), 0, st, a);
-}
-
-template <bool LQR, bool SCHED = false>
-static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED> &a, void *stream) {
+// COST = true: f16_rollout_cost takes the same rules without the quad and four-wave branches (those kernels split the state
+// over four role waves and have no scored twin), so a scored batch of B <= 16,384 hifi lanes runs the 64-lane one-lane kernel.
+template <bool LQR, bool SCHED, bool COST>
+static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const long B = a.B;
-  const int fi_flag = a.fi;
+  const bool hifi = a.fi == 1;
   static const long max4w = [] { const char *e = getenv("F16_ROLLOUT_4W_MAXB"); return e ? atol(e) : 64L * 256; }();
   static const long maxq = [] { const char *e = getenv("F16_ROLLOUT_QUAD_MAXB"); return e ? atol(e) : 16L * 256; }();
+  const char *const what = COST ? "f16_rollout_cost launch" : "f16_rollout launch";
   if (a.flags & F16_FLAG_ONE_LANE) {
     // results independent of the batch size: ONE kernel for every B, its step an out-of-line function (k_rollout_exact)
     const long blocks = (B + 63) / 64;
-    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, (hipStream_t)stream, a);
-    return hip_check(hipGetLastError(), "f16_rollout launch");
+    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    return hip_check(hipGetLastError(), what);
   }
-  if (fi_flag == 1 && B <= maxq) {
-    // at most 16 aircraft per CU: four lanes per aircraft, one 16-aircraft workgroup per CU
-    hipLaunchKernelGGL((k_rollout_q<1, LQR, SCHED>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, (hipStream_t)stream, a);
-    return hip_check(hipGetLastError(), "f16_rollout launch");
+  if constexpr (!COST) {
+    if (hifi && B <= 2 * maxq) {
+      // four lanes per aircraft.  At most 16 aircraft per CU: one 16-aircraft workgroup per CU; at most 32: two 16-aircraft
+      // groups per workgroup
+      if (B <= maxq) hipLaunchKernelGGL((k_rollout_q<1, LQR, SCHED>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((k_rollout_q<2, LQR, SCHED>), dim3((unsigned)((B + 31) / 32)), dim3(512), 0, st, a);
+      return hip_check(hipGetLastError(), what);
+    }
+    // (three groups per workgroup leave 168 registers per lane: the roles spill, 3.96 ms against the 4-wave kernel's 2.13)
+    if (hifi && B <= max4w) {
+      // latency regime: four wavefronts per 64 aircraft, one workgroup per CU
+      hipLaunchKernelGGL((k_rollout_4w<LQR, SCHED>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, a);
+      return hip_check(hipGetLastError(), what);
+    }
   }
-  if (fi_flag == 1 && B <= 2 * maxq) {
-    // at most 32 per CU: two 16-aircraft groups per workgroup
-    hipLaunchKernelGGL((k_rollout_q<2, LQR, SCHED>), dim3((unsigned)((B + 31) / 32)), dim3(512), 0, (hipStream_t)stream, a);
-    return hip_check(hipGetLastError(), "f16_rollout launch");
-  }
-  // (three groups per workgroup leave 168 registers per lane: the roles spill, 3.96 ms against the 4-wave kernel's 2.13)
-  if (fi_flag == 1 && B <= max4w) {
-    // latency regime: four wavefronts per 64 aircraft, one workgroup per CU
-    hipLaunchKernelGGL((k_rollout_4w<LQR, SCHED>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, (hipStream_t)stream, a);
-    return hip_check(hipGetLastError(), "f16_rollout launch");
-  }
-  Geometry g = geometry(B, fi_flag);
+  Geometry g = geometry(B, a.fi);
 #ifdef F16_FAST_DIV
   // throughput regime, default numerics: lookups on the scaled-integer image
   static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
-  if (fi_flag == 1 && use_i32 && g.block == 512) {
+  if (hifi && use_i32 && g.block == 512) {
     a.tab32 = ctx->d_tab32;
-    hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED>), dim3(g.grid), dim3(512), 0, (hipStream_t)stream, a);
-    return hip_check(hipGetLastError(), "f16_rollout launch");
+    hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED, COST>), dim3(g.grid), dim3(512), 0, st, a);
+    return hip_check(hipGetLastError(), what);
   }
 #endif
   if (LQR && g.block == 512) g.block = 256;  // (fp64 image + 16 slots of 512 lanes would not fit the 160 KB of a CU)
-  const hipStream_t st = (hipStream_t)stream;
-  if (g.block == 64) launch_lanes<64, LQR, SCHED>(g.grid, st, a);
-  else if (g.block == 128) launch_lanes<128, LQR, SCHED>(g.grid, st, a);
-  else if (LQR || g.block == 256) launch_lanes<256, LQR, SCHED>(g.grid, st, a);
-  else launch_lanes<512, false, SCHED>(g.grid, st, a);
-  return hip_check(hipGetLastError(), "f16_rollout launch");
+  by_block(g, [&](auto block) {
+    constexpr int BLOCK = decltype(block)::value;
+    if constexpr (!(LQR && BLOCK == 512)) {    // (never reached, and not instantiated)
+      if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED, COST>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+      else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED, COST>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+    }
+  });
+  return hip_check(hipGetLastError(), what);
 }
 
-// the argument rules f16_rollout and its scheduled / closed-loop siblings share
+// the argument rules f16_rollout and its scheduled / closed-loop / scored siblings share
 static int check_rollout(f16_ctx *ctx, const double *x, const double *u, const double *traj, long B, long ld, int nsteps, int traj_every) {
   if (int rc = check_common(ctx, x, u, B, ld)) return rc;
   if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
@@ -1210,115 +1205,96 @@ static int check_rollout(f16_ctx *ctx, const double *x, const double *u, const d
   return F16_OK;
 }
 
+// One rollout on the nonlinear plant as its entry point states it.  The five f16_rollout* calls differ in these values and in
+// the kernel variant <LQR, SCHED, COST> only; plant_rollout checks them in one order and fills RolloutArgs<SCHED, COST>.
+struct PlantRollout {
+  const char *missing;                 // the message for a NULL among the pointers the variant needs beyond x and u
+  const double *x;                     // [18][ld], stepped in place (`out`); the scored call: x0 [18][ld0], read only
+  const double *u;                     // [4][ld]: the constant input; u0 under the LQR law; row 0 of u_seq
+  double *out;                         // x again; the scored call: the cost column [ld]
+  double *traj;
+  int32_t *status;
+  long B, ld;
+  int nsteps, traj_every;
+  double dt, xcg;
+  int fi;
+  unsigned flags;
+  // what an entry point leaves alone is the value of the oldest call, f16_rollout:
+  const double *seq = nullptr;         // SCHED: u_seq [nrows][4][ld], under the LQR law dem_seq [nrows][3][ld]
+  int hold = 1;                        // SCHED: steps per row
+  const double *K = nullptr, *dem = nullptr;      // LQR: the gain and the demands (row 0 of dem_seq)
+  double *u_out = nullptr;             // LQR: the last action, may be null
+  // COST: lane b is sample b / B0 of aircraft b % B0
+  long B0 = 0, ld0 = 0;
+  const double *x_ref = nullptr, *u_ref = nullptr;
+  double *x_end = nullptr;
+  const f16_cost_weights *w = nullptr;
+};
+
+template <bool LQR, bool SCHED, bool COST>
+static int plant_rollout(f16_ctx *ctx, const PlantRollout &d, void *stream) {
+  if ((SCHED && !d.seq) || (LQR && (!d.K || !d.dem)) || (COST && (!d.x_ref || !d.w || !d.out))) return set_error(F16_EINVAL, d.missing);
+  if (int rc = check_rollout(ctx, d.x, d.u, d.traj, d.B, d.ld, d.nsteps, d.traj_every)) return rc;
+  if (d.hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
+  if constexpr (COST) {
+    if (d.B > 0 && (d.B0 < 1 || d.ld0 < d.B0 || d.B % d.B0 != 0))
+      return set_error(F16_EINVAL, "B lanes are K samples of B0 aircraft: B0 >= 1, ld0 >= B0 and B % B0 == 0");
+    const double *w = d.w->q;       // q[9], qf[9], r[3], pen: 22 doubles in a row
+    static_assert(sizeof(f16_cost_weights) == 22 * sizeof(double), "f16_cost_weights is 22 doubles");
+    for (int k = 0; k < 22; ++k)
+      if (!(w[k] >= 0.0) || !__builtin_isfinite(w[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
+  }
+  // nothing to step; the scored call still launches for nsteps = 0: its cost is then the terminal term
+  if (d.B == 0 || (!COST && d.nsteps == 0)) return F16_OK;
+  auto a = base_args<RolloutArgs<SCHED, COST>>(ctx, d.B, d.ld, d.xcg, d.fi, d.flags, d.status);
+  a.u = d.u; a.out = d.out; a.traj = d.traj;
+  a.nsteps = d.nsteps; a.traj_every = d.traj ? d.traj_every : d.nsteps + 1; a.dt = d.dt;
+  a.K = d.K; a.dem = d.dem; a.u_out = d.u_out;
+  if constexpr (SCHED) { a.seq = d.seq; a.hold = d.hold; a.nrows = d.nsteps > 0 ? (d.nsteps - 1) / d.hold + 1 : 0; }
+  if constexpr (COST) { a.x0 = d.x; a.x_ref = d.x_ref; a.u_ref = d.u_ref; a.x_end = d.x_end; a.B0 = d.B0; a.ld0 = d.ld0; a.w = *d.w; }
+  return rollout_dispatch<LQR, SCHED, COST>(ctx, a, stream);
+}
+
+// The entry points: each states what distinguishes it.
 extern "C" int f16_rollout(f16_ctx *ctx, double *x, const double *u, double *traj, int32_t *status, long B, long ld,
                            int nsteps, int traj_every, double dt, double xcg, int fi_flag, unsigned flags,
                            void *stream) {
-  if (int rc = check_rollout(ctx, x, u, traj, B, ld, nsteps, traj_every)) return rc;
-  if (B == 0 || nsteps == 0) return F16_OK;
-  DynArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u; a.out = x; a.traj = traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
-  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  return rollout_dispatch<false>(ctx, a, stream);
+  PlantRollout d{nullptr, x, u, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  return plant_rollout<false, false, false>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_sched(f16_ctx *ctx, double *x, const double *u_seq, double *traj, int32_t *status, long B, long ld,
                                  int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, unsigned flags,
                                  void *stream) {
-  if (!u_seq) return set_error(F16_EINVAL, "u_seq is NULL");
-  if (int rc = check_rollout(ctx, x, u_seq, traj, B, ld, nsteps, traj_every)) return rc;
-  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
-  if (B == 0 || nsteps == 0) return F16_OK;
-  SchedArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u_seq; a.out = x; a.traj = traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
-  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  a.seq = u_seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
-  return rollout_dispatch<false, true>(ctx, a, stream);
-}
-
-// f16_rollout_cost: the launch rules of rollout_dispatch without its quad and four-wave branches (those kernels split the state
-// over four role waves and have no scored twin), so a scored batch of B <= 16,384 hifi lanes runs the 64-lane one-lane kernel.
-template <int BLOCK>
-static void launch_cost_lanes(int grid, hipStream_t st, const CostArgs &a) {
-  if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, false, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
-  else hipLaunchKernelGGL((k_rollout<BLOCK, -1, false, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+  PlantRollout d{"u_seq is NULL", x, u_seq, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = u_seq; d.hold = hold;
+  return plant_rollout<false, true, false>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_cost(f16_ctx *ctx, const double *x0, long B0, long ld0, const double *u_seq, const double *x_ref,
                                 const double *u_ref, const f16_cost_weights *h_w, double *cost, double *x_end, double *traj,
                                 int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt, double xcg,
                                 int fi_flag, unsigned flags, void *stream) {
-  if (!u_seq || !x_ref || !h_w || !cost) return set_error(F16_EINVAL, "u_seq / x_ref / h_w / cost is NULL");
-  if (int rc = check_rollout(ctx, x0, u_seq, traj, B, ld, nsteps, traj_every)) return rc;
-  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
-  if (B > 0 && (B0 < 1 || ld0 < B0 || B % B0 != 0))
-    return set_error(F16_EINVAL, "B lanes are K samples of B0 aircraft: B0 >= 1, ld0 >= B0 and B % B0 == 0");
-  {
-    const double *w = h_w->q;       // q[9], qf[9], r[3], pen: 22 doubles in a row
-    static_assert(sizeof(f16_cost_weights) == 22 * sizeof(double), "f16_cost_weights is 22 doubles");
-    for (int k = 0; k < 22; ++k)
-      if (!(w[k] >= 0.0) || !__builtin_isfinite(w[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
-  }
-  if (B == 0) return F16_OK;
-  CostArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u_seq; a.out = cost; a.traj = traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
-  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  a.seq = u_seq; a.hold = hold; a.nrows = nsteps > 0 ? (nsteps - 1) / hold + 1 : 0;
-  a.x0 = x0; a.x_ref = x_ref; a.u_ref = u_ref; a.x_end = x_end; a.B0 = B0; a.ld0 = ld0; a.w = *h_w;
-  const hipStream_t st = (hipStream_t)stream;
-  if (flags & F16_FLAG_ONE_LANE) {
-    const long blocks = (B + 63) / 64;
-    hipLaunchKernelGGL((k_rollout_exact<false, true, true>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
-    return hip_check(hipGetLastError(), "f16_rollout_cost launch");
-  }
-  Geometry g = geometry(B, fi_flag);
-#ifdef F16_FAST_DIV
-  static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
-  if (fi_flag == 1 && use_i32 && g.block == 512) {
-    a.tab32 = ctx->d_tab32;
-    hipLaunchKernelGGL((k_rollout_i<512, false, true, true>), dim3(g.grid), dim3(512), 0, st, a);
-    return hip_check(hipGetLastError(), "f16_rollout_cost launch");
-  }
-#endif
-  if (g.block == 64) launch_cost_lanes<64>(g.grid, st, a);
-  else if (g.block == 128) launch_cost_lanes<128>(g.grid, st, a);
-  else if (g.block == 256) launch_cost_lanes<256>(g.grid, st, a);
-  else launch_cost_lanes<512>(g.grid, st, a);
-  return hip_check(hipGetLastError(), "f16_rollout_cost launch");
+  PlantRollout d{"u_seq / x_ref / h_w / cost is NULL", x0, u_seq, cost, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = u_seq; d.hold = hold;
+  d.B0 = B0; d.ld0 = ld0; d.x_ref = x_ref; d.u_ref = u_ref; d.x_end = x_end; d.w = h_w;
+  return plant_rollout<false, true, true>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem, double *traj,
                                double *u_out, int32_t *status, long B, long ld, int nsteps, int traj_every, double dt,
                                double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (int rc = check_common(ctx, x, u0, B, ld)) return rc;
-  if (!K || !dem) return set_error(F16_EINVAL, "K / dem is NULL");
-  if (nsteps < 0 || (traj && (traj_every < 1 || nsteps % traj_every != 0)))
-    return set_error(F16_EINVAL, "nsteps must be >= 0 and a multiple of traj_every >= 1 when traj is given");
-  if (B == 0 || nsteps == 0) return F16_OK;
-  DynArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u0; a.out = x; a.traj = traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
-  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  a.K = K; a.dem = dem; a.u_out = u_out;
-  return rollout_dispatch<true>(ctx, a, stream);
+  PlantRollout d{"K / dem is NULL", x, u0, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.K = K; d.dem = dem; d.u_out = u_out;
+  return plant_rollout<true, false, false>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr_sched(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq,
                                      double *traj, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
                                      int traj_every, double dt, double xcg, int fi_flag, unsigned flags, void *stream) {
-  if (int rc = check_rollout(ctx, x, u0, traj, B, ld, nsteps, traj_every)) return rc;
-  if (!K || !dem_seq) return set_error(F16_EINVAL, "K / dem_seq is NULL");
-  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
-  if (B == 0 || nsteps == 0) return F16_OK;
-  SchedArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.u = u0; a.out = x; a.traj = traj; a.status = status;
-  a.B = B; a.ld = ld; a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1;
-  a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  a.K = K; a.dem = dem_seq; a.u_out = u_out;
-  a.seq = dem_seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
-  return rollout_dispatch<true, true>(ctx, a, stream);
+  PlantRollout d{"K / dem_seq is NULL", x, u0, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = dem_seq; d.hold = hold; d.K = K; d.dem = dem_seq; d.u_out = u_out;
+  return plant_rollout<true, true, false>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr_linear(f16_ctx *ctx, double *x9, const double *Ad, const double *Bd, const double *K, const double *x_ref,
@@ -1342,11 +1318,13 @@ extern "C" int f16_xdot_na_batch(f16_ctx *ctx, const double *x_full, const doubl
   if (int rc = check_common(ctx, x_full, xdot9, B, ld)) return rc;
   if (!x9 || !u3) return set_error(F16_EINVAL, "x9/u3 is NULL");
   if (B == 0) return F16_OK;
-  DynArgs a{};
-  a.tab = ctx->d_tab; a.lofi = ctx->d_lofi; a.x = x_full; a.u = x9; a.u3 = u3; a.out = xdot9; a.status = status;
-  a.B = B; a.ld = ld; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
-  Geometry g = geometry(B, fi_flag);
-  LAUNCH_BY_BLOCK(k_xdot_na, g, (hipStream_t)stream, a);
+  DynArgs a = base_args<DynArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
+  a.x = x_full; a.u = x9; a.u3 = u3; a.out = xdot9;
+  const Geometry g = geometry(B, fi_flag);
+  by_block(g, [&](auto block) {
+    constexpr int BLOCK = decltype(block)::value;
+    hipLaunchKernelGGL(k_xdot_na<BLOCK>, dim3(g.grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
+  });
   return hip_check(hipGetLastError(), "f16_xdot_na_batch launch");
 }
 

@@ -106,6 +106,28 @@ class F16Batch:
     def _check(self, rc):
         _lib.check(rc, self.lib)
 
+    @staticmethod
+    def _schedule_steps(hold, nsteps, rows, name):
+        """A zero-order-hold schedule of `rows` rows (held by `name`), step t reading row t // hold: hold >= 1, nsteps defaults to
+        rows * hold, and the ceil(nsteps / hold) rows it reads must be there.  Returns (hold, nsteps) as ints."""
+        hold = int(hold)
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        nsteps = rows * hold if nsteps is None else int(nsteps)
+        if nsteps < 1 or (nsteps + hold - 1) // hold > rows:
+            raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1); {name}: {rows}")
+        return hold, nsteps
+
+    def _samples(self, nsteps, traj_every, rows=18, lanes=None):
+        """The buffer of a rollout's samples, one after every traj_every-th step: [nsteps // traj_every, rows, lanes] (lanes: B), or
+        None without traj_every, which must divide nsteps."""
+        if not traj_every:
+            return None
+        k = int(traj_every)
+        if k < 1 or nsteps % k:
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
+        return torch.empty((nsteps // k, rows, self.B if lanes is None else lanes), dtype=torch.float64, device=self.device)
+
     # x.values / u.values as [B,18] / [B,4] views of the resident state
     @property
     def x_values(self):
@@ -191,14 +213,19 @@ class F16Batch:
         """nsteps Euler steps in ONE launch with the state held in registers (the reference's
         `for ...: self.step(u)` loops, test_env.py:456-462).  traj_every=k stores the state after every k-th
         step and returns it as [nsteps//k, 18, B] (state-major)."""
-        us = self._u if action is None else self._soa(action, 4)
-        traj = None
-        if traj_every:
-            assert nsteps % traj_every == 0
-            traj = torch.empty((nsteps // traj_every, 18, self.B), dtype=torch.float64, device=self.device)
-        self._check(self.lib.f16_rollout(self.ctx.handle, _vp(self._x), _vp(us), _vp(traj), _vp(self.status), self.B,
-                                         self.B, int(nsteps), int(traj_every or 1), self.dt, self.xcg, self.fi_flag,
-                                         self.flags, self._stream))
+        return self._rollout_call(self._u if action is None else self._soa(action, 4), nsteps, traj_every)
+
+    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None):
+        """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
+        into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
+        around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values."""
+        traj = self._samples(nsteps, traj_every)
+        # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
+        name, law, u_out = ("f16_rollout", (), ()) if K is None else ("f16_rollout_lqr", (_vp(K), _vp(dem)), (_vp(self._u),))
+        name, held = (name, ()) if hold is None else (name + "_sched", (hold,))
+        self._check(getattr(self.lib, name)(self.ctx.handle, _vp(self._x), _vp(u), *law, _vp(traj), *u_out, _vp(self.status), self.B,
+                                            self.B, int(nsteps), *held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag,
+                                            self.flags, self._stream))
         return traj
 
     def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None):
@@ -209,9 +236,6 @@ class F16Batch:
         pass a host array or a non-contiguous view to say otherwise).  nsteps defaults to S * hold and needs
         S >= ceil(nsteps / hold) rows.  Returns what `rollout` returns; u.values ends up holding the last row used, as the
         reference's caller leaves it."""
-        hold = int(hold)
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
         t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
         if t.dim() != 3:
             raise ValueError(f"actions must be [S, B, 4] or a state-major [S, 4, B] device tensor, not {tuple(t.shape)}")
@@ -222,18 +246,8 @@ class F16Batch:
         else:
             raise ValueError(f"actions must be [S, {self.B}, 4] or a contiguous fp64 [S, 4, {self.B}] tensor on {self.device}, "
                              f"not {tuple(t.shape)} ({t.dtype}, {t.device})")
-        S = seq.shape[0]
-        nsteps = S * hold if nsteps is None else int(nsteps)
-        if nsteps < 1 or (nsteps + hold - 1) // hold > S:
-            raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), actions has {S}")
-        traj = None
-        if traj_every:
-            if nsteps % int(traj_every):
-                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
-            traj = torch.empty((nsteps // int(traj_every), 18, self.B), dtype=torch.float64, device=self.device)
-        self._check(self.lib.f16_rollout_sched(self.ctx.handle, _vp(self._x), _vp(seq), _vp(traj), _vp(self.status), self.B,
-                                               self.B, nsteps, hold, int(traj_every or 1), self.dt, self.xcg, self.fi_flag,
-                                               self.flags, self._stream))
+        hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
+        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold)
         self._u.copy_(seq[(nsteps - 1) // hold])
         return traj
 
@@ -250,17 +264,9 @@ class F16Batch:
     def _score(self, seq, K, hold, nsteps, x_ref, u_ref, w, traj_every, want_final):
         """f16_rollout_cost on seq [S, 4, K * B] from the resident state -> cost [K * B], status [K * B], x_end [18, K * B] or None,
         traj [n, 18, K * B] or None.  x_ref [9, B], u_ref [3, B] or None (state-major, contiguous)."""
-        hold, S, lanes = int(hold), seq.shape[0], K * self.B
-        if hold < 1:
-            raise ValueError("hold must be >= 1")
-        nsteps = S * hold if nsteps is None else int(nsteps)
-        if nsteps < 1 or (nsteps + hold - 1) // hold > S:
-            raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), actions has {S}")
-        traj = None
-        if traj_every:
-            if nsteps % int(traj_every):
-                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every})")
-            traj = torch.empty((nsteps // int(traj_every), 18, lanes), dtype=torch.float64, device=self.device)
+        lanes = K * self.B
+        hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
+        traj = self._samples(nsteps, traj_every, lanes=lanes)
         cost = torch.empty(lanes, dtype=torch.float64, device=self.device)
         st = torch.empty(lanes, dtype=torch.int32, device=self.device)
         x_end = torch.empty((18, lanes), dtype=torch.float64, device=self.device) if want_final else None
@@ -603,11 +609,7 @@ class F16Batch:
         if dem_seq is not None:
             if linear or relinearise:
                 raise ValueError("demand histories run on the nonlinear loop with a fixed gain (not with linear=True / relinearise=True)")
-            hold = 1 if hold is None else int(hold)
-            if hold < 1:
-                raise ValueError("hold must be >= 1")
-            if nsteps < 1 or (nsteps + hold - 1) // hold > dem_seq.shape[0]:
-                raise ValueError(f"{nsteps} steps with hold {hold} need {max(nsteps + hold - 1, 0) // hold} rows (>= 1), the demands have {dem_seq.shape[0]}")
+            hold, nsteps = self._schedule_steps(1 if hold is None else hold, nsteps, dem_seq.shape[0], "the demands")
         elif hold is not None:
             raise ValueError("hold goes with demand histories ([S] or [S, B]); scalar / [B] demands are constant")
         if relinearise:
@@ -639,19 +641,7 @@ class F16Batch:
             u0s = torch.cat((self._u[0:1], self._u_init[1:4]), 0).contiguous()
         else:
             u0s = self._soa(u0, 4)
-        traj = None
-        if traj_every:
-            assert nsteps % traj_every == 0
-            traj = torch.empty((nsteps // traj_every, 18, self.B), dtype=torch.float64, device=self.device)
-        if dem_seq is not None:
-            self._check(self.lib.f16_rollout_lqr_sched(self.ctx.handle, _vp(self._x), _vp(u0s), _vp(Ks), _vp(dem_seq), _vp(traj),
-                                                       _vp(self._u), _vp(self.status), self.B, self.B, int(nsteps), hold,
-                                                       int(traj_every or 1), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
-            return traj
-        self._check(self.lib.f16_rollout_lqr(self.ctx.handle, _vp(self._x), _vp(u0s), _vp(Ks), _vp(dem), _vp(traj), _vp(self._u),
-                                             _vp(self.status), self.B, self.B, int(nsteps), int(traj_every or 1), self.dt,
-                                             self.xcg, self.fi_flag, self.flags, self._stream))
-        return traj
+        return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq)
 
     def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
                           hold=None):
@@ -667,16 +657,12 @@ class F16Batch:
         not taken without such a history (ValueError)."""
         if traj_every and gains_every and int(traj_every) != int(gains_every):
             raise ValueError("the states, commands and gains are sampled at one interval: traj_every must equal gains_every")
-        if hold is not None and int(hold) < 1:
-            raise ValueError(f"hold must be >= 1 (got {hold})")
         k = int(traj_every or gains_every or 1)
         if x_ref is not None and np.ndim(x_ref) == 3:
-            hold = 1 if hold is None else int(hold)
             xr = torch.as_tensor(x_ref, dtype=torch.float64, device=self.device).contiguous()
             if tuple(xr.shape[1:]) != (9, self.B):
                 raise ValueError(f"a schedule of references is [S, 9, {self.B}], not {tuple(xr.shape)}")
-            if int(nsteps) < 1 or (int(nsteps) + hold - 1) // hold > xr.shape[0]:
-                raise ValueError(f"{nsteps} steps with hold {hold} need {max(int(nsteps) + hold - 1, 0) // hold} rows (>= 1), x_ref has {xr.shape[0]}")
+            hold, nsteps = self._schedule_steps(1 if hold is None else hold, nsteps, xr.shape[0], "x_ref")
             mask = 0x1FF if track is None else sum(1 << int(j) for j in track)
             u03 = None if u0 is None else self._soa(u0, 3)
             return self._rollout_relin(nsteps, xr, mask, u03, _lib.make_weights(Q=Q, R=R), eps, k, True, True, gains_every is not None,
@@ -722,9 +708,7 @@ class F16Batch:
         Ads, Bds, Ks, xr = sm(Ad, 81), sm(Bd, 27), sm(K, 27), sm(x_ref, 9)
         u0s = sm(u0, 3) if u0 is not None else None
         k = int(traj_every or 1)
-        assert nsteps % k == 0
-        trx = torch.empty((nsteps // k, 9, self.B), dtype=torch.float64, device=self.device)
-        tru = torch.empty((nsteps // k, 3, self.B), dtype=torch.float64, device=self.device)
+        trx, tru = self._samples(nsteps, k, 9), self._samples(nsteps, k, 3)
         mask = 0x1FF if track is None else sum(1 << int(j) for j in track)
         self._check(self.lib.f16_rollout_lqr_linear(self.ctx.handle, _vp(xs), _vp(Ads), _vp(Bds), _vp(Ks), _vp(xr), _vp(u0s), _vp(trx),
                                                     _vp(tru), self.B, self.B, int(nsteps), k, mask, self._stream))
