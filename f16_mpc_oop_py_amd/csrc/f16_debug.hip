@@ -5,6 +5,11 @@
 //                 (br_load / br_cell / br_axis / lerp / ld4 / bil4 on the node-major LDS image, f16_plant.hpp), one lane
 //                 per query point.  The kernels never evaluate a single table -- lookups are fused per table group -- so
 //                 without this entry the bracket / interpolation code is only checked through whole-Nlplant sums.
+//   k_dbg_sincos  the branch-free sin/cos pair in its two forms on the same arguments: sincos_bf (constants as literals) and
+//                 sincos_bf_k (the same table loaded into scalar registers, the form of the quad rollout).  The two must agree
+//                 bit for bit; the rollouts only show that through whole trajectories.
+//   k_dbg_pow     the atmosphere's exp(0.14 log tfac) as the device library composes it and as exp_k / log_k repeat it with
+//                 the constants in scalar registers, and qbar / ps of atmos_dev through either: the same bits.
 #include <hip/hip_runtime.h>
 
 #include "../../include/f16_hip.h"
@@ -82,6 +87,32 @@ __global__ __launch_bounds__(64) void k_dbg_table(const double *__restrict__ tab
   }
 }
 
+#ifdef F16_FAST_TRIG
+// out: [4][n] = sin, cos by sincos_bf | sin, cos by sincos_bf_k
+__global__ __launch_bounds__(64) void k_dbg_sincos(const double *__restrict__ x, double *__restrict__ out, long n) {
+  const SinCosK sk = reloaded(QUAD_K.sc);
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double s0, c0, s1, c1;
+    sincos_bf(x[p], &s0, &c0);
+    sincos_bf_k(sk, x[p], &s1, &c1);
+    out[p] = s0; out[n + p] = c0; out[2 * n + p] = s1; out[3 * n + p] = c1;
+  }
+}
+#endif
+
+#ifdef F16_FAST_POW
+// out: [6][n] = the power factor, qbar, ps (vt = 500 ft/s) by the library composition | the same three by exp_k / log_k
+__global__ __launch_bounds__(64) void k_dbg_pow(const double *__restrict__ alt, double *__restrict__ out, long n) {
+  const PowK pk = reloaded(QUAD_K.pw);
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double pw0 = 0, pw1 = 0, mach, q0, p0, q1, p1;
+    atmos_with(alt[p], 500.0, mach, q0, p0, [&](double tfac) { return pw0 = exp(0.14 * log(tfac)); });
+    atmos_with(alt[p], 500.0, mach, q1, p1, [&](double tfac) { return pw1 = exp_k(pk, 0.14 * log_k(pk, tfac)); });
+    out[p] = pw0; out[n + p] = q0; out[2 * n + p] = p0; out[3 * n + p] = pw1; out[4 * n + p] = q1; out[5 * n + p] = p1;
+  }
+}
+#endif
+
 }  // namespace f16
 
 using namespace f16;
@@ -110,4 +141,44 @@ extern "C" int f16_debug_table_lookup(f16_ctx *ctx, int tid, const double *h_alp
   (void)hipFree(d);
   (void)hipFree(ds);
   return rc;
+}
+
+extern "C" int f16_debug_sincos(f16_ctx *ctx, const double *h_x, long n, double *h_out) {
+  if (!ctx || !h_x || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_sincos");
+#ifdef F16_FAST_TRIG
+  if (n == 0) return F16_OK;
+  double *d = nullptr;
+  int rc;
+  if ((rc = hip_check(hipMalloc(&d, 5 * (size_t)n * sizeof(double)), "hipMalloc dbg sincos"))) return rc;
+  if (!(rc = hip_check(hipMemcpy(d, h_x, (size_t)n * sizeof(double), hipMemcpyHostToDevice), "copy x"))) {
+    const long blocks = (n + 63) / 64;
+    hipLaunchKernelGGL(k_dbg_sincos, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(64), 0, nullptr, d, d + n, n);
+    rc = hip_check(hipGetLastError(), "f16_debug_sincos launch");
+    if (!rc) rc = hip_check(hipMemcpy(h_out, d + n, 4 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "copy out");
+  }
+  (void)hipFree(d);
+  return rc;
+#else
+  return set_error(F16_EINVAL, "f16_debug_sincos: this library was built without F16_FAST_TRIG (libm sincos, one form only)");
+#endif
+}
+
+extern "C" int f16_debug_pow(f16_ctx *ctx, const double *h_alt, long n, double *h_out) {
+  if (!ctx || !h_alt || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_pow");
+#ifdef F16_FAST_POW
+  if (n == 0) return F16_OK;
+  double *d = nullptr;
+  int rc;
+  if ((rc = hip_check(hipMalloc(&d, 7 * (size_t)n * sizeof(double)), "hipMalloc dbg pow"))) return rc;
+  if (!(rc = hip_check(hipMemcpy(d, h_alt, (size_t)n * sizeof(double), hipMemcpyHostToDevice), "copy alt"))) {
+    const long blocks = (n + 63) / 64;
+    hipLaunchKernelGGL(k_dbg_pow, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(64), 0, nullptr, d, d + n, n);
+    rc = hip_check(hipGetLastError(), "f16_debug_pow launch");
+    if (!rc) rc = hip_check(hipMemcpy(h_out, d + n, 6 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "copy out");
+  }
+  (void)hipFree(d);
+  return rc;
+#else
+  return set_error(F16_EINVAL, "f16_debug_pow: this library was built without F16_FAST_POW (libm pow, one form only)");
+#endif
 }

@@ -672,6 +672,12 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // Owned states are replicated over the sub-lanes of their wave; two barriers per step as in k_rollout_4w.
 // GROUPS = 2 (4096 < B <= 8192): two independent 16-aircraft groups per workgroup share the LDS table image, one role
 // wave of each on every SIMD -- the two dependency chains interleave.
+// GROUPS = 1 takes the constants of its sin/cos pair and of the atmosphere's exp / log from SCALAR registers: each role loads
+// its own from QUAD_K (constant memory, f16_plant.hpp) at the top of its part of a step -- a few scalar loads that land while the
+// role waits for its LDS reads anyway -- and uses them as the scalar operand of its FMAs.  As literals they cost the
+// trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28 vector registers for
+// the sin/cos table; kept in scalar registers for the whole loop (43 doubles) they push loop masks out into lane moves.
+// Same operations, same operands, same order.
 template <int GROUPS, bool LQR = false, bool SCHED = false>
 __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a) {
   constexpr int NA = 16 * GROUPS;
@@ -720,12 +726,20 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
     }
     if (G1 && wave == 0 && s == 0) {                       // sin / cos of the first step's psi (the loop's first barrier publishes it)
       double sp, cp;
-      F16_SINCOS(x[5], &sp, &cp);
+      F16_SINCOS_K(reloaded(QUAD_K.sc), x[5], &sp, &cp);    // (the form of the loop: on a NaN psi the two differ in the sign of the NaN)
       xpsi[1][ac] = sp; xpsi[2][ac] = cp;
     }
 #ifdef F16_EXP_STAMPQ
     unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
-#define QSTAMP(acc) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
+    // -DF16_EXP_STAMPQ (or =1): every stamp waits for ALL counters, wave 2's sample stores included.  -DF16_EXP_STAMPQ=2: for the
+    // LDS / scalar counter alone (vmcnt and expcnt left at their maxima), so that wave 2's first half reads without the
+    // completion of its stores folded in.
+#if F16_EXP_STAMPQ + 0 == 2
+#define QSTAMP_WAIT 0xC07F
+#else
+#define QSTAMP_WAIT 0
+#endif
+#define QSTAMP(acc) { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); unsigned long long t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
 #else
 #define QSTAMP(acc)
 #endif
@@ -758,23 +772,47 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
       // trajectory sample of the step that just finished: all 18 states straight from the published copy, by the wave
       // with the most slack in the first half (wave 2 since the actuator wave became the longest; sub-lane s stores states
       // s, s+4, s+8, ...)
+      // GROUPS = 1: the step's own reads of the published copy are issued FIRST and the sample's five reads right behind them,
+      // all before the first store -- one LDS round trip for both (read, wait, store per state, this wave paid three in a row
+      // with nothing to switch to, and only then asked for its step inputs).  The extra trip reads the copy for nothing.
+      double xa[17];
+      int env_any = 0;
+      if constexpr (G1) {
+        env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
+#pragma unroll
+        for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+      }
       if (wave == 2 && tr && t > 0 && --until_store == 0) {
         until_store = a.traj_every;
         if (valid) {
+          if constexpr (G1) {
+            double smp[5];
 #pragma unroll
-          for (int j = 0; j < 5; ++j) {
-            const int kk = s + 4 * j;
-            if (kk < 18) __builtin_nontemporal_store(xs[kk][ac], tr + kk * a.ld);
+            for (int j = 0; j < 5; ++j) smp[j] = xs[s + 4 * j < 18 ? s + 4 * j : s][ac];
+            __builtin_amdgcn_sched_barrier(0);             // every read above, every store below
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+              const int kk = s + 4 * j;
+              if (kk < 18) __builtin_nontemporal_store(smp[j], tr + kk * a.ld);
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+              const int kk = s + 4 * j;
+              if (kk < 18) __builtin_nontemporal_store(xs[kk][ac], tr + kk * a.ld);
+            }
           }
         }
         tr += 18 * a.ld;
       }
       if (t == a.nsteps) break;
-      if (xenv[0][ac] | xenv[1][ac] | xenv[2][ac]) st |= ST_ENVELOPE;
-      const bool live = !(st & ST_ENVELOPE);
-      double xa[17];
+      if constexpr (!G1) {
+        env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
 #pragma unroll
-      for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+        for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+      }
+      if (env_any) st |= ST_ENVELOPE;
+      const bool live = !(st & ST_ENVELOPE);
       // first-half results wave 2 keeps in registers for the second half
       double xd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       double U = 0, V = 0, W = 0, s_t = 0, c_t = 0, s_phi = 0, c_phi = 0, cb = 0, vtc = 0, r1 = 0, r2 = 0, r3 = 0;
@@ -805,7 +843,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
         // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
         const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
         double sn, cs, sb, s_psi, c_psi;
-        F16_SINCOS(ang, &sn, &cs);
+        if constexpr (G1) F16_SINCOS_K(reloaded(QUAD_K.sc), ang, &sn, &cs); else F16_SINCOS(ang, &sn, &cs);
         // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
         //  changes x[1] in the last place)
         if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
@@ -854,7 +892,12 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
         double vt = xa[6];
         if (vt <= 0.01) vt = 0.01;
         double mach, qbar, ps;
-        atmos_dev(xa[2], vt, mach, qbar, ps);
+        double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
+        if constexpr (G1) {
+          const PowK pk = reloaded(QUAD_K.pw);
+          atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(pk, 0.14 * log_k(pk, tfac)); });
+        } else
+          atmos_dev(xa[2], vt, mach, qbar, ps);
         if (s == 0) { xt[6][ac] = qbar; xt[7][ac] = ps; }
         if (live) {
           // utils.py:308-330: thrust on sub-lane 0, elevator / aileron / rudder on 1..3 (same form, own limits)
@@ -869,7 +912,13 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
           const double dth = actuator_rate(ucmd, 1000, 19000, 1.0, xact, 10000);
           const double dsf = actuator_rate(uc, -lim, lim, 20.2, xact, rate);
           double lf1_dot, lf2_dot;
-          upd_lef_dev(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot);
+          if constexpr (G1)
+            upd_lef_with(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot,
+                         [pw](double h_, double V_, double &m_, double &q_, double &p_) {      // (h_ is the altitude pw was taken at)
+                           atmos_with(h_, V_, m_, q_, p_, [pw](double) { return pw; });
+                         });
+          else
+            upd_lef_dev(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot);
           xact += (s == 0 ? dth : dsf) * a.dt;             // env.py:126 on the actuator / flap states
           x[16] += lf2_dot * a.dt;
           x[17] += lf1_dot * a.dt;
@@ -925,7 +974,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
         }
       } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
         double sp, cp;
-        F16_SINCOS(xpsi[0][ac], &sp, &cp);
+        F16_SINCOS_K(reloaded(QUAD_K.sc), xpsi[0][ac], &sp, &cp);
         xpsi[1][ac] = sp; xpsi[2][ac] = cp;
       }
     }

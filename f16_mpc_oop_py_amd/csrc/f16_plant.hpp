@@ -59,8 +59,108 @@ struct Axis {
 
 F16_DEV double lerp(double f1, double f2, const Axis &a) { return a.l * f2 + a.m * f1; }  // mexndinterp.c:197
 
-// C/nlplant.c:467-490
-F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double &ps) {
+// fp64 FMAs pinned to the three-address form with ONE uniform (scalar-register) operand: the plain vector FMA, nothing else.
+// Left to itself the compiler prefers the two-address v_fmac_f64 and copies the uniform value into a vector register first.
+F16_DEV double fma_vvs(double a, double b, double c) {        // a * b + c, c uniform
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+  return d;
+}
+F16_DEV double fma_svv(double a, double b, double c) {        // a * b + c, a uniform
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "s"(a), "v"(b), "v"(c));
+  return d;
+}
+
+// ---- exp(0.14 log tfac) of F16_FAST_POW with its constants as uniform values
+// The device library's exp and log are inlined from bitcode, so their literals cannot be redirected; in the quad rollout they
+// cost the atmosphere wave a register move (accumulation register, 64-bit copy or a pair of scalar moves) in front of almost
+// every polynomial step.  exp_k / log_k repeat the library's operation sequence (ROCm device library, double-precision exp and
+// log: frexp, an extended-precision quotient and sum for log; reduction by ln 2 in two parts and a degree-11 polynomial for
+// exp), operation by operation, in the contracted form the compiler gives it in this build (-ffp-contract=fast: every product
+// that feeds a sum is fused with it, also where the product has other uses).  Each such product-sum is WRITTEN as an fma here
+// and no product feeds a plain sum, so nothing is left to contract.  tests/test_gpu_quad_constants.py holds the two
+// compositions to the same bits.
+struct PowK {
+  double log2e, ln2_hi, ln2_lo, nln2_hi, nln2_lo, two_thirds;     // (ln 2 in two parts, and negated: exp's reduction)
+  double E[10];                    // exp: e^r = 1 + r (1 + r (E9 + r (E8 + ... r E0))), highest degree first
+  double L[7];                     // log: highest degree first
+};
+constexpr PowK POW_K = {
+    1.44269504088896338700e+00, 6.93147180559945286227e-01, 2.31904681384629955842e-17, -6.93147180559945286227e-01,
+    -2.31904681384629955842e-17, 6.66666666666666629659e-01,
+    {2.50223225676461415e-08, 2.76309034901126543e-07, 2.75575145458253105e-06, 2.48014910390950412e-05, 1.98412695891155217e-04,
+     1.38888889459163820e-03, 8.33333333345504315e-03, 4.16666666665197541e-02, 1.66666666666664770e-01, 5.00000000000001221e-01},
+    {1.53670161652585818e-01, 1.52503063567000663e-01, 1.81863527724766383e-01, 2.22221384831011309e-01, 2.85714293974435540e-01,
+     3.99999999961319630e-01, 6.66666666666728247e-01}};
+
+F16_DEV double log_k(const PowK &K, double x) {
+  const double m = __builtin_amdgcn_frexp_mant(x);
+  const bool lo = m < K.two_thirds;
+  const double sc = lo ? 2.0 : 1.0;
+  const int e = __builtin_amdgcn_frexp_exp(x) + (lo ? -1 : 0);
+  // y = m sc; (y - 1) / (y + 1) in two parts
+  const double ym1 = fma(m, sc, -1.0), yp1 = fma(m, sc, 1.0);
+  const double ylo = fma(m, sc, -(yp1 + -1.0));
+  double r = __builtin_amdgcn_rcp(yp1);
+  r = fma(fma(-yp1, r, 1.0), r, r);
+  r = fma(fma(-yp1, r, 1.0), r, r);
+  const double q = ym1 * r;
+  const double p = yp1 * q;
+  const double pl = fma(q, ylo, fma(q, yp1, -p));
+  const double s25 = fma(yp1, q, pl);
+  const double s27 = pl - fma(-yp1, q, s25);
+  const double d28 = ym1 - s25;
+  const double d32 = d28 + (((ym1 - d28) - s25) - s27);
+  const double h = fma(r, d32, q);                         // quotient, high part
+  const double l = fma(r, d32, -fma(-ym1, r, h));          // low part
+  const double z = h * h;
+  double c = fma_vvs(z, K.L[0], K.L[1]);
+#pragma unroll
+  for (int k = 2; k < 7; ++k) c = fma_vvs(z, c, K.L[k]);
+  const double a44 = __builtin_ldexp(h, 1), a45 = __builtin_ldexp(l, 1);
+  const double t46 = h * z;
+  const double u48 = fma(t46, c, a44);
+  const double u50 = fma(t46, c, -(u48 - a44));
+  const double u51 = a45 + u50;
+  const double u52 = u48 + u51;
+  const double u54 = u51 - (u52 - u48);
+  // + e ln 2 in two parts
+  const double f = (double)e;
+  const double g56n = f * K.nln2_hi;
+  const double g59 = fma_svv(K.ln2_lo, f, fma_svv(K.ln2_hi, f, g56n));
+  const double g60 = fma_svv(K.ln2_hi, f, g59);
+  const double g62 = g59 - fma_svv(K.nln2_hi, f, g60);
+  const double w63 = g60 + u52;
+  const double w64 = w63 - g60;
+  const double w68 = (u52 - w64) + (g60 - (w63 - w64));
+  const double v69 = g62 + u54;
+  const double v70 = v69 - g62;
+  const double v74 = (u54 - v70) + (g62 - (v69 - v70));
+  const double k75 = v69 + w68;
+  const double k76 = w63 + k75;
+  const double k80 = k76 + (v74 + (k75 - (k76 - w63)));
+  double res = __builtin_fabs(x) == __builtin_inf() ? x : k80;
+  res = x < 0.0 ? __builtin_nan("") : res;
+  return x == 0.0 ? -__builtin_inf() : res;
+}
+
+F16_DEV double exp_k(const PowK &K, double x) {
+  const double n = rint(x * K.log2e);
+  const double r = fma_svv(K.nln2_lo, n, fma_svv(K.nln2_hi, n, x));      // (as the library's fma(-n, ln2, x) compiles: sign on the constant)
+  double c = fma_vvs(r, K.E[0], K.E[1]);
+#pragma unroll
+  for (int k = 2; k < 10; ++k) c = fma_vvs(r, c, K.E[k]);
+  c = fma(r, c, 1.0);
+  c = fma(r, c, 1.0);
+  double res = __builtin_ldexp(c, (int)n);
+  res = x > 1024.0 ? __builtin_inf() : res;
+  return x < -1075.0 ? 0.0 : res;
+}
+
+// C/nlplant.c:467-490; pw(tfac) = exp(0.14 log tfac) of the default build (below)
+template <typename PW>
+F16_DEV void atmos_with(double alt, double vt, double &mach, double &qbar, double &ps, PW pw) {
   const double rho0 = 2.377e-3;
   const double tfac = 1 - .703e-5 * alt;
   double temp = 519.0 * tfac;
@@ -69,7 +169,7 @@ F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double
   // tfac^4.14 = (tfac^2)^2 * exp(0.14 log tfac): |0.14 log tfac| < 0.2 on the flight envelope keeps the
   // exp-of-log error below 1 ulp; two exact-to-0.5ulp squarings on top => <= 2 ulp vs libm pow.
   const double t2 = tfac * tfac;
-  const double rho = rho0 * ((t2 * t2) * exp(0.14 * log(tfac)));
+  const double rho = rho0 * ((t2 * t2) * pw(tfac));
 #else
   const double rho = rho0 * pow(tfac, 4.14);
 #endif
@@ -78,7 +178,44 @@ F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double
   ps = 1715.0 * rho * temp;
   if (ps == 0) ps = 1715;
 }
+F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double &ps) {
+  atmos_with(alt, vt, mach, qbar, ps, [](double tfac) { return exp(0.14 * log(tfac)); });
+}
+// the same with the constants of exp and log as uniform values (quad rollout)
+F16_DEV void atmos_dev_k(const PowK &K, double alt, double vt, double &mach, double &qbar, double &ps) {
+  atmos_with(alt, vt, mach, qbar, ps, [&K](double tfac) { return exp_k(K, 0.14 * log_k(K, tfac)); });
+}
 
+
+// The constants of the branch-free sin/cos pair below live in ONE table: sincos_bf folds them to literals, sincos_bf_k takes the same table as uniform values
+// (scalar registers, loaded from QUAD_K below), so the two cannot drift.
+struct SinCosK {
+  double two_over_pi, npio2[3];    // 2/pi; -pi/2 in three parts
+  double S[8], C[9];               // sin: r + r z (S0 + S1 z + ...), cos: 1 + z (C0 + C1 z + ...), z = r^2
+};
+constexpr SinCosK SINCOS_K = {
+    6.36619772367581382433e-01, {-1.57079632673412561417e+00, -6.07710050630396597660e-11, -2.02226624879595063154e-21},
+    {-1.66666666666666657e-01, 8.33333333333333322e-03, -1.98412698412698413e-04, 2.75573192239858925e-06, -2.50521083854417202e-08, 1.60590438368216133e-10, -7.64716373181981641e-13, 2.81145725434552060e-15},
+    {-5.00000000000000000e-01, 4.16666666666666644e-02, -1.38888888888888894e-03, 2.48015873015873016e-05, -2.75573192239858883e-07, 2.08767569878681002e-09, -1.14707455977297245e-11, 4.77947733238738525e-14, -1.56192069685862253e-16}};
+
+// Both tables as ONE object in constant memory, for code that wants them in scalar registers.  Read at a constant offset the
+// values fold back into literals; reloaded() hides the address (passed through a scalar register the compiler cannot see through), so
+// that the values are LOADED -- by scalar loads, the address being uniform -- where the call stands, on every pass through it.
+// The scalar unit only reads here.
+struct QuadK { SinCosK sc; PowK pw; };
+static __constant__ const QuadK QUAD_K = {SINCOS_K, POW_K};
+template <typename T>
+F16_DEV T reloaded(const T &t) {
+  static_assert(sizeof(T) % sizeof(double) == 0, "a table of doubles");
+  unsigned long p = reinterpret_cast<unsigned long>(&t);
+  asm volatile("" : "+s"(p));
+  const __attribute__((address_space(4))) double *q = (const __attribute__((address_space(4))) double *)p;
+  T k;
+  double *d = reinterpret_cast<double *>(&k);
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / sizeof(double); ++i) d[i] = q[i];
+  return k;
+}
 
 #ifdef F16_FAST_TRIG
 // Branch-free sin/cos pair: 3-part Cody-Waite reduction by pi/2 (exact for |x| < ~1e6 rad) + Taylor polynomials on
@@ -86,28 +223,56 @@ F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double
 // [-1e5, 1e5].  Unlike the libm call it contains no large-argument branch, so the five independent evaluations of a
 // plant step sit in ONE basic block and the scheduler interleaves their dependency chains (the kernel is bound by
 // fp64 dependent-issue latency at one wave per SIMD).
-F16_DEV void sincos_bf(double x, double *sn, double *cs) {
-  const double n = rint(x * 6.36619772367581382433e-01);
-  double r = fma(-n, 1.57079632673412561417e+00, x);
-  r = fma(-n, 6.07710050630396597660e-11, r);
-  r = fma(-n, 2.02226624879595063154e-21, r);
-  const double z = r * r;
-  const double S[8] = {-1.66666666666666657e-01, 8.33333333333333322e-03, -1.98412698412698413e-04, 2.75573192239858925e-06, -2.50521083854417202e-08, 1.60590438368216133e-10, -7.64716373181981641e-13, 2.81145725434552060e-15};
-  const double C[9] = {-5.00000000000000000e-01, 4.16666666666666644e-02, -1.38888888888888894e-03, 2.48015873015873016e-05, -2.75573192239858883e-07, 2.08767569878681002e-09, -1.14707455977297245e-11, 4.77947733238738525e-14, -1.56192069685862253e-16};
-  double p = S[7], q = C[8];
-#pragma unroll
-  for (int k = 6; k >= 0; --k) p = fma(p, z, S[k]);
-#pragma unroll
-  for (int k = 7; k >= 0; --k) q = fma(q, z, C[k]);
-  const double s0 = fma(r * z, p, r), c0 = fma(z, q, 1.0);
+// quadrant selection shared by both forms
+F16_DEV void sincos_quadrant(double n, double s0, double c0, double *sn, double *cs) {
   const int k = (int)n & 3;
   const double a = (k & 1) ? c0 : s0, b = (k & 1) ? s0 : c0;
   *sn = (k & 2) ? -a : a;
   *cs = ((k + 1) & 2) ? -b : b;
 }
+
+F16_DEV void sincos_bf(double x, double *sn, double *cs) {
+  constexpr SinCosK K = SINCOS_K;
+  const double n = rint(x * K.two_over_pi);
+  double r = fma(-n, -K.npio2[0], x);
+  r = fma(-n, -K.npio2[1], r);
+  r = fma(-n, -K.npio2[2], r);
+  const double z = r * r;
+  double p = K.S[7], q = K.C[8];
+#pragma unroll
+  for (int k = 6; k >= 0; --k) p = fma(p, z, K.S[k]);
+#pragma unroll
+  for (int k = 7; k >= 0; --k) q = fma(q, z, K.C[k]);
+  const double s0 = fma(r * z, p, r), c0 = fma(z, q, 1.0);
+  sincos_quadrant(n, s0, c0, sn, cs);
+}
+
+// The same operations on the same operands in the same order, with every constant a UNIFORM value the caller holds in scalar
+// registers (K: QUAD_K.sc below, defined from SINCOS_K).  As literals the 17 coefficients cost the quad rollout a
+// 64-bit register move in front of every Horner step (the compiler prefers the two-address v_fmac_f64) and 28 vector registers
+// for the table; an fp64 FMA whose addend is the scalar operand needs neither and issues faster (4.6 against 6.1 cycles at
+// one wave per SIMD).  The FMA is pinned to its three-address form: it is the plain vector FMA, nothing else.
+F16_DEV void sincos_bf_k(const SinCosK &K, double x, double *sn, double *cs) {
+  const double n = rint(x * K.two_over_pi);
+  // (operand for operand what the compiler makes of fma(-n, C, r) with a literal C: (-C) n + r, the sign on the constant --
+  //  on a NaN argument the sign of the result follows the operand that carries it)
+  double r = fma_svv(K.npio2[0], n, x);
+  r = fma_svv(K.npio2[1], n, r);
+  r = fma_svv(K.npio2[2], n, r);
+  const double z = r * r;
+  double p = K.S[7], q = K.C[8];
+#pragma unroll
+  for (int k = 6; k >= 0; --k) p = fma_vvs(p, z, K.S[k]);
+#pragma unroll
+  for (int k = 7; k >= 0; --k) q = fma_vvs(q, z, K.C[k]);
+  const double s0 = fma(r * z, p, r), c0 = fma(z, q, 1.0);
+  sincos_quadrant(n, s0, c0, sn, cs);
+}
 #define F16_SINCOS(x, s, c) sincos_bf(x, s, c)
+#define F16_SINCOS_K(K, x, s, c) sincos_bf_k(K, x, s, c)
 #else
 #define F16_SINCOS(x, s, c) sincos(x, s, c)
+#define F16_SINCOS_K(K, x, s, c) sincos(x, s, c)
 #endif
 
 struct Aero {  // everything C/nlplant.c:185-240 (or :245-323) hands to the coefficient build-up
@@ -832,12 +997,14 @@ F16_DEV double actuator_rate(double cmd, double lo, double hi, double k, double 
 
 // utils.py:289-306 -> lf1_dot (7.25*LF_err), lf2_dot (lef_err).  qbar/ps are those of atmos(h, V) with the
 // RAW V (utils.py:291); plant() evaluates atmos with vt clamped to >= 0.01, identical whenever V > 0.01.
-F16_DEV void upd_lef_dev(double h, double V, double alpha, double lf1, double lf2, double qbar_p, double ps_p,
-                         double &lf1_dot, double &lf2_dot) {
+// atm: the atmosphere function the caller took qbar_p / ps_p from (the two evaluations then share their exp / log).
+template <typename ATM>
+F16_DEV void upd_lef_with(double h, double V, double alpha, double lf1, double lf2, double qbar_p, double ps_p,
+                          double &lf1_dot, double &lf2_dot, ATM atm) {
   double qbar = qbar_p, ps = ps_p;
   if (V <= 0.01) {
     double mach;
-    atmos_dev(h, V, mach, qbar, ps);
+    atm(h, V, mach, qbar, ps);
   }
   const double atmos_out = qbar / ps * 9.05;
   const double alpha_deg = F16_DIVC(alpha * 180, 3.141592653589793);
@@ -846,6 +1013,11 @@ F16_DEV void upd_lef_dev(double h, double V, double alpha, double lf1, double lf
   const double lef_cmd = LF_out + 1.45 - atmos_out;
   lf2_dot = actuator_rate(lef_cmd, 0., 25, 1 / 0.136, lf2, 25);     // utils.py:303-305 (np.clip: NaN in -> NaN out)
   lf1_dot = LF_err * 7.25;
+}
+F16_DEV void upd_lef_dev(double h, double V, double alpha, double lf1, double lf2, double qbar_p, double ps_p,
+                         double &lf1_dot, double &lf2_dot) {
+  upd_lef_with(h, V, alpha, lf1, lf2, qbar_p, ps_p, lf1_dot, lf2_dot,
+               [](double h_, double V_, double &m, double &q, double &p) { atmos_dev(h_, V_, m, q, p); });
 }
 
 // utils.py:308-330 + env.py:90-102: actuator and leading-edge-flap state derivatives xdot[12..17].

@@ -249,6 +249,9 @@ def load():
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
     L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]
+    if hasattr(L, "f16_debug_sincos"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        L.f16_debug_sincos.argtypes = [vp, vp, l, vp]
+        L.f16_debug_pow.argtypes = [vp, vp, l, vp]
     if hasattr(L, "f16_trim_batch"):
         L.f16_trim_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, d, i, u, i, vp, vp]
     if hasattr(L, "f16_linearise_batch"):

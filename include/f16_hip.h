@@ -89,6 +89,17 @@ int f16_debug_read_tables_i32(f16_ctx *ctx, int32_t *h_out);
 int f16_debug_table_lookup(f16_ctx *ctx, int tid, const double *h_alpha, const double *h_beta, const double *h_el,
                            int n, double *h_out, int32_t *h_status);
 
+/* Tests: the branch-free sin/cos pair of the default build in its two forms on n arguments given on the HOST -- constants as
+ * literals (every kernel but one) and the same table in scalar registers (the four-lane rollout at B <= 4096).
+ * h_out [4][n]: sin, cos of the first form, sin, cos of the second.  The two agree bit for bit.  F16_EINVAL from a library
+ * built without F16_FAST_TRIG (one form only: libm). */
+int f16_debug_sincos(f16_ctx *ctx, const double *h_x, long n, double *h_out);
+/* Tests: the atmosphere's exp(0.14 log tfac), tfac = 1 - 0.703e-5 alt, at n altitudes [ft] given on the HOST, composed from the
+ * device library's exp and log (every kernel but one) and by the restatement of the same operation sequence with its constants
+ * in scalar registers (the four-lane rollout at B <= 4096).  h_out [6][n]: the factor, qbar and ps (at 500 ft/s) of the first
+ * form, then of the second.  The two agree bit for bit.  F16_EINVAL from a library built without F16_FAST_POW. */
+int f16_debug_pow(f16_ctx *ctx, const double *h_alt, long n, double *h_out);
+
 /* ---- (1) drop-in symbols of the reference .so ---------------------------------------------- */
 /* replaces C/nlplant.c:23  void Nlplant(double *xu, double *xdot, int fidelity)
  * host pointers; reads xu[0..16], writes xdot[0..17]; runs ONE aircraft on the GPU. */

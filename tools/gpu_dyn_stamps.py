@@ -1,4 +1,6 @@
 """Diagnostic: per-wave cycles of the quad rollout from a -DF16_EXP_STAMPQ build (run on the GPU box).
+-DF16_EXP_STAMPQ (or =1): every stamp waits for all counters, wave 2's sample stores included; -DF16_EXP_STAMPQ=2: for the LDS /
+scalar counter only, so that wave 2's first half reads without the completion of its stores.
 usage: F16HIP_SO=build/libf16hip_stampq.so python tools/gpu_dyn_stamps.py [B]"""
 import sys
 sys.path.insert(0, ".")
