@@ -29,6 +29,12 @@ F16_DEV int quad_bcast_i(int v) {
   return __builtin_amdgcn_mov_dpp(v, ctrl, 0xF, 0xF, true);
 }
 
+// The values are computed where this call stands: the compiler may neither move the arithmetic that forms them behind it nor
+// fuse it with their later uses (an empty statement that claims to rewrite each of them in its vector registers).
+F16_DEV void quad_taken_here_1(double &v) { asm volatile("" : "+v"(v)); }
+template <typename... T>
+F16_DEV void quad_taken_here(T &...v) { (quad_taken_here_1(v), ...); }
+
 // The three axis brackets of a role, ONE PER SUB-LANE (0: alpha on ALPHA1, 1: beta, 2/3: elevator on DH1 or DH2), shared
 // across the quad by DPP broadcasts: first the cell indices (the table addresses need nothing else), later lambda.
 struct QuadBr { BrCell c; int ja, jb, jd; bool offa, offb, offd; };

@@ -1,0 +1,245 @@
+// f16_quad_steps.inc -- the step loop of k_rollout_q (f16_dynamics.hip), included there once per role and once for all roles.
+// `wave` is defined by the including scope: a compile-time constant 0..3 in a role's own loop (GROUPS = 1: every `if (wave == ...)`
+// below is resolved then, and that copy keeps the statements, the published states and the loop-carried registers of its role
+// alone), the wave's role index itself in the shared loop (GROUPS = 2).  Every copy executes the same barriers: A and B per step,
+// A alone on the extra trip.  Text, not a function: the shared loop then compiles exactly as it did inside the kernel.
+    for (int t = 0; t <= a.nsteps; ++t) {                  // the extra trip only publishes + stores the final sample
+      // ---- step start: envelope test on the owned states (env.py:117-124), publish them
+      if (wave == 2) {
+        xenv[0][ac] = envchk && (x[2] < 0 || x[2] > 100000 || x[6] < 0 || x[6] > 900 || x[7] < -20. || x[7] > 90 ||
+                                 x[8] < -30. || x[8] > 30);
+        if (s == 0) {
+#pragma unroll
+          for (int k = 0; k < 9; ++k) xs[k][ac] = x[k];
+        }
+      } else if (wave == 1) {
+        xenv[1][ac] = envchk && (x[9] < -300 || x[9] > 300 || x[10] < -100 || x[10] > 100 || x[11] < -50 || x[11] > 50);
+        if (s < 3) xs[9 + s][ac] = s == 0 ? x[9] : (s == 1 ? x[10] : x[11]);
+      } else if (wave == 3) {
+        const double lim = s == 1 ? 25.0 : (s == 2 ? 21.5 : 30.0);
+        const bool bad = s == 0 ? (xact < 1000 || xact > 19000) : (xact < -lim || xact > lim);
+        const bool badl = x[16] < 0. || x[16] > 25;
+        // any sub-lane out of range flags the aircraft: combine over the quad through LDS writes of `true` only
+        if (s == 0) xenv[2][ac] = 0;
+        xs[12 + s][ac] = xact;
+        if (s < 2) xs[16 + s][ac] = s == 0 ? x[16] : x[17];
+        __builtin_amdgcn_wave_barrier();
+        if (envchk && (bad || badl)) xenv[2][ac] = 1;
+      }
+      QSTAMP(tD)
+      __syncthreads();
+      QSTAMP(tA)
+      // trajectory sample of the step that just finished: all 18 states straight from the published copy, by the wave
+      // with the most slack in the first half (wave 2 since the actuator wave became the longest; sub-lane s stores states
+      // s, s+4, s+8, ...)
+      // GROUPS = 1: the step's own reads of the published copy are issued FIRST and the sample's five reads right behind them,
+      // all before the first store -- one LDS round trip for both (read, wait, store per state, this wave paid three in a row
+      // with nothing to switch to, and only then asked for its step inputs).  The extra trip reads the copy for nothing.
+      double xa[17];
+      int env_any = 0;
+      if constexpr (G1) {
+        env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
+#pragma unroll
+        for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+      }
+      if (wave == 2 && tr && t > 0 && --until_store == 0) {
+        until_store = a.traj_every;
+        if (valid) {
+          if constexpr (G1) {
+            double smp[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) smp[j] = xs[s + 4 * j < 18 ? s + 4 * j : s][ac];
+            __builtin_amdgcn_sched_barrier(0);             // every read above, every store below
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+              const int kk = s + 4 * j;
+              if (kk < 18) __builtin_nontemporal_store(smp[j], tr + kk * a.ld);
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+              const int kk = s + 4 * j;
+              if (kk < 18) __builtin_nontemporal_store(xs[kk][ac], tr + kk * a.ld);
+            }
+          }
+        }
+        tr += 18 * a.ld;
+      }
+      if (t == a.nsteps) break;
+      if constexpr (!G1) {
+        env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
+#pragma unroll
+        for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+      }
+      if ((!G1 || wave != 0) && env_any) st |= ST_ENVELOPE;   // (a wave 0 with a loop of its own reads no flag: it reports no status)
+      const bool live = !(st & ST_ENVELOPE);
+      // first-half results wave 2 keeps in registers for the second half
+      double xd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      double U = 0, V = 0, W = 0, s_t = 0, c_t = 0, s_phi = 0, c_phi = 0, cb = 0, vtc = 0, r1 = 0, r2 = 0, r3 = 0;
+      double fu0 = 0, fv0 = 0, fw0 = 0, mo0 = 0, mo1 = 0, mo2 = 0;
+      bool newrow = false;
+      if constexpr (SCHED) newrow = ra.due(a, LQR ? 3 : 4);
+      if (wave == 0) {
+        int sa_ = 0;
+        double latd;
+        const double tot = quad_long<G1>((const double *)tab, xa, s, a.xcg, a.flags, qc, latd, sa_);
+        if (s < 3) { xt[s][ac] = tot; xt[8 + s][ac] = latd; }
+        xst[0][ac] = sa_;
+      } else if (wave == 1) {
+        int sa_ = 0;
+        const double tot = quad_lat<G1>((const double *)tab, xa, s, a.flags, qc, sa_);
+        if (s < 3) xt[3 + s][ac] = tot;
+        xst[1][ac] = sa_;
+        {   // the rate-product terms of the moment equations (C/nlplant.c:413-436, Heng = 0) do not need the totals: first half
+          const double Jy = 55814.0, Jxz = 982.0, Jz = 63100.0, Jx = 9496.0;
+          const double rden = 1.0 / (9496.0 * 63100.0 - 982.0 * 982.0);
+          const double P = x[9], Q = x[10], R = x[11];
+          mo0 = (Jxz * (Jx - Jy + Jz) * P * Q - (Jz * (Jz - Jy) + Jxz * Jxz) * Q * R) * rden;
+          mo1 = F16_DIVC((Jz - Jx) * P * R - Jxz * (P * P - R * R), Jy);
+          mo2 = ((Jx * (Jx - Jy) + Jxz * Jxz) * P * Q - Jxz * (Jx - Jy + Jz) * Q * R) * rden;
+        }
+        if constexpr (G1) quad_taken_here(mo0, mo1, mo2);  // (as on wave 2 below: first-half work stays in the first half)
+      } else if (wave == 2) {
+        // sin / cos of phi, theta, beta, alpha: one angle per sub-lane, then shared across the quad; psi's from wave 0
+        // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
+        const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
+        double sn, cs, sb, s_psi, c_psi;
+        if constexpr (G1) F16_SINCOS_K(reloaded(QUAD_K.sc), ang, &sn, &cs); else F16_SINCOS(ang, &sn, &cs);
+        // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
+        //  changes x[1] in the last place)
+        if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
+        s_phi = quad_bcast<0>(sn); c_phi = quad_bcast<0>(cs);
+        s_t = quad_bcast<1>(sn); c_t = quad_bcast<1>(cs);
+        if constexpr (G1) { s_psi = xpsi[1][ac]; c_psi = xpsi[2][ac]; } else { s_psi = quad_bcast<2>(sn); c_psi = quad_bcast<2>(cs); }
+        const double sal = quad_bcast<3>(sn), cal = quad_bcast<3>(cs);
+        vtc = xa[6];
+        if (vtc <= 0.01) vtc = 0.01;
+        U = vtc * cal * cb; V = vtc * sb; W = vtc * sal * cb;                       // C/nlplant.c:148-150
+        const double P = xa[9], Q = xa[10], R = xa[11];
+#ifdef F16_FAST_DIV
+        const double rct = f16_rcp(c_t);
+        const double tt = s_t * rct;
+#elif defined(F16_FAST_TAN)
+        const double rct = 0.0, tt = s_t / c_t;
+#else
+        const double rct = 0.0, tt = tan(xa[4]);
+#endif
+        xd[0] = U * (c_t * c_psi) + V * (s_phi * c_psi * s_t - c_phi * s_psi) + W * (c_phi * s_t * c_psi + s_phi * s_psi);
+        xd[1] = U * (c_t * s_psi) + V * (s_phi * s_psi * s_t + c_phi * c_psi) + W * (c_phi * s_t * s_psi - s_phi * c_psi);
+        xd[2] = U * s_t - V * (s_phi * c_t) - W * (c_phi * c_t);
+        xd[3] = P + tt * (Q * s_phi + R * c_phi);                                     // :169-176
+        xd[4] = Q * c_phi - R * s_phi;
+#ifdef F16_FAST_DIV
+        xd[5] = (Q * s_phi + R * c_phi) * rct;
+        r1 = f16_rcp(vtc); r2 = f16_rcp(U * U + W * W); r3 = f16_rcp(vtc * vtc * cb);   // divisors of :393-405, hoisted
+#else
+        xd[5] = (Q * s_phi + R * c_phi) / c_t;
+        (void)rct;
+#endif
+        // this wave has slack in the first half and sets the pace of the second: what the force equations and the Euler
+        // update do not need the coefficient totals for is done here (same expressions, :383-387 regrouped)
+        {
+          const double g = 32.17, m = 636.94;
+          fu0 = R * V - Q * W - g * s_t + F16_DIVC(xa[12], m);
+          fv0 = P * W - R * U + g * c_t * s_phi;
+          fw0 = Q * U - P * V + g * c_t * c_phi;
+          if (live) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) x[k] += xd[k] * a.dt;   // env.py:126 (navigation / kinematic states)
+          }
+          if (G1 && s == 0) xpsi[0][ac] = x[5];                  // wave 0 evaluates its sin / cos in the second half
+        }
+        // (in a loop of its own a role's two halves are one piece of code: left alone, the compiler moves what only the second
+        //  half uses -- the three reciprocals, fu0 .. fw0 -- behind barrier B, into the half this wave sets the pace of, and
+        //  contracts it with the force equations there: other last bits)
+        if constexpr (G1) quad_taken_here(U, V, W, vtc, r1, r2, r3, fu0, fv0, fw0);
+      } else {
+        double vt = xa[6];
+        if (vt <= 0.01) vt = 0.01;
+        double mach, qbar, ps;
+        double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
+        if constexpr (G1) {
+          const PowK pk = reloaded(QUAD_K.pw);
+          atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(pk, 0.14 * log_k(pk, tfac)); });
+        } else
+          atmos_dev(xa[2], vt, mach, qbar, ps);
+        if (s == 0) { xt[6][ac] = qbar; xt[7][ac] = ps; }
+        if (live) {
+          // utils.py:308-330: thrust on sub-lane 0, elevator / aileron / rudder on 1..3 (same form, own limits)
+          const double lim = s == 1 ? 25.0 : (s == 2 ? 21.5 : 30.0), rate = s == 1 ? 60.0 : (s == 2 ? 80.0 : 120.0);
+          double uc = ucmd;
+          if (LQR) {
+            if constexpr (SCHED) { dm0 = quad_bcast<0>(dmq); dm1 = quad_bcast<1>(dmq); dm2 = quad_bcast<2>(dmq); }   // (live is the same over a quad)
+            const double ua = lqr_action(kr0, kr1, kr2, dm0 - xa[9], dm1 - xa[10], dm2 - xa[11], ucmd);
+            uc = s > 0 ? ua : ucmd;
+            ulast = uc;
+          }
+          const double dth = actuator_rate(ucmd, 1000, 19000, 1.0, xact, 10000);
+          const double dsf = actuator_rate(uc, -lim, lim, 20.2, xact, rate);
+          double lf1_dot, lf2_dot;
+          if constexpr (G1)
+            upd_lef_with(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot,
+                         [pw](double h_, double V_, double &m_, double &q_, double &p_) {      // (h_ is the altitude pw was taken at)
+                           atmos_with(h_, V_, m_, q_, p_, [pw](double) { return pw; });
+                         });
+          else
+            upd_lef_dev(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot);
+          xact += (s == 0 ? dth : dsf) * a.dt;             // env.py:126 on the actuator / flap states
+          x[16] += lf2_dot * a.dt;
+          x[17] += lf1_dot * a.dt;
+        }
+        if constexpr (SCHED) if (newrow) {
+          // (the sub-lane from the lane number, inside this branch: neither a register kept through the step for it nor -- GROUPS = 2
+          //  spills -- a scratch reload in front of the load; volatile so that it is not hoisted out again)
+          int rv;
+          asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(rv));
+          rv &= 3;
+          if (LQR && rv == 3) rv = 2;
+          ra.take(a, LQR ? 3 : 4, LQR ? &dmq : &ucmd, a.out + b, rv * a.ld);
+          if (LQR) ulast = ucmd;                          // (as a new launch: u0 until it steps)
+        }
+      }
+      QSTAMP(tB)
+      __syncthreads();
+      QSTAMP(tC)
+      // ---- second half: force equations on wave 2 || moment equations on wave 1
+      if (wave == 2) {
+        if (live) {
+          st |= xst[0][ac] | xst[1][ac];
+          const double Cx = xt[0][ac], Cz = xt[1][ac], Cy = xt[3][ac] + xt[8][ac], qbar = xt[6][ac];
+          const double m = 636.94, S = 300.0;
+          const double qsm = F16_DIVC(qbar * S, m);
+          const double Udot = fu0 + qsm * Cx;                                                          // :383-387
+          const double Vdot = fv0 + qsm * Cy;
+          const double Wdot = fw0 + qsm * Cz;
+#ifdef F16_FAST_DIV
+          xd[6] = (U * Udot + V * Vdot + W * Wdot) * r1;                                                 // :393-405
+          xd[7] = (U * Wdot - W * Udot) * r2;
+          xd[8] = (Vdot * vtc - V * xd[6]) * r3;
+#else
+          xd[6] = (U * Udot + V * Vdot + W * Wdot) / vtc;
+          xd[7] = (U * Wdot - W * Udot) / (U * U + W * W);
+          xd[8] = (Vdot * vtc - V * xd[6]) / (vtc * vtc * cb);
+#endif
+#pragma unroll
+          for (int k = 6; k < 9; ++k) x[k] += xd[k] * a.dt;   // env.py:126 (x[0..5] were advanced in the first half)
+        }
+      } else if (wave == 1) {
+        if (live) {
+          const double Cy = xt[3][ac] + xt[8][ac];
+          const double Cn = xt[4][ac] + xt[9][ac] - Cy * (0.35 - a.xcg) * (11.32 / 30.0);   // C/nlplant.c:367
+          const double Cl = xt[5][ac] + xt[10][ac];
+          const double Jy = 55814.0, Jxz = 982.0, Jz = 63100.0, Jx = 9496.0, S = 300.0;
+          const double rden = 1.0 / (9496.0 * 63100.0 - 982.0 * 982.0);
+          const double qs = xt[6][ac] * S;
+          const double L_tot = Cl * qs * 30.0, M_tot = xt[2][ac] * qs * 11.32, N_tot = Cn * qs * 30.0;   // :413-415
+          x[9] += (mo0 + (Jz * L_tot + Jxz * N_tot) * rden) * a.dt;                                  // :417-436 + env.py:126
+          x[10] += (mo1 + F16_DIVC(M_tot, Jy)) * a.dt;
+          x[11] += (mo2 + (Jx * N_tot + Jxz * L_tot) * rden) * a.dt;
+        }
+      } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
+        double sp, cp;
+        F16_SINCOS_K(reloaded(QUAD_K.sc), xpsi[0][ac], &sp, &cp);
+        xpsi[1][ac] = sp; xpsi[2][ac] = cp;
+      }
+    }

@@ -1,6 +1,7 @@
 // Microbenchmark (diagnostic): what ONE resident wavefront per SIMD pays per fp64 FMA on gfx950, and what changes it:
 // operand sources (three VGPR pairs / one SGPR pair / an inline constant), register banks of the operands, dependent chains, and
-// other instruction classes issued between the FMAs (v_accvgpr_read, v_mov, ds_read_b128, v_mov_dpp).  Cycles come from s_memtime
+// other instruction classes issued between the FMAs (v_accvgpr_read, v_mov, ds_read_b128, v_mov_dpp; a taken s_branch over 384 bytes of
+// s_nop, a not-taken s_cbranch_execz, an s_and_saveexec / s_or exec pair: what a role wave pays to step over another role's block).  Cycles come from s_memtime
 // (shader clock) and from s_memrealtime (100 MHz), so the clock the part really runs at under this load is printed too.
 //   hipcc --offload-arch=gfx950 -O3 -o issue_mix issue_mix.hip && ./issue_mix
 #include <hip/hip_runtime.h>
@@ -52,7 +53,9 @@
 
 #define CLOB "v32","v33","v34","v35","v36","v37","v38","v39","v40","v41","v42","v43","v44","v45","v46","v47","v48","v49","v50","v51", \
   "v52","v53","v54","v55","v56","v57","v58","v59","v60","v61","v62","v63","v64","v65","v66","v67","v68","v69","v70","v71","v72","v73","v74","v75", \
-  "a0","a1","a2","a3","s40","s41"
+  "a0","a1","a2","a3","s40","s41","s42","s43"
+// a forward jump over 96 s_nop (384 bytes, six 64-byte lines): the target is never in the instruction buffer when the branch issues
+#define JUMP_FAR "s_branch 1f\n" REP16(REP4("s_nop 0\n")) REP16("s_nop 0\n s_nop 0\n") "1:\n"
 
 template <int V, int LDS_KB>
 __global__ __launch_bounds__(64) void k(unsigned long long *out, int iters) {
@@ -91,6 +94,9 @@ __global__ __launch_bounds__(64) void k(unsigned long long *out, int iters) {
     if (V == 12) asm volatile(REP4(MIX("s_nop 0\n")) ::: CLOB);
     if (V == 13) asm volatile(REP4(MIX("v_cndmask_b32 v72, v73, v74, vcc\n")) ::: CLOB);
     if (V == 14) asm volatile(REP4(MIX("ds_bpermute_b32 v72, v70, v73\n")) "s_waitcnt lgkmcnt(0)\n" ::: CLOB);
+    if (V == 15) asm volatile(REP4(MIX(JUMP_FAR)) ::: CLOB);                             // taken: every FMA sits 384 bytes behind the last
+    if (V == 16) asm volatile(REP4(MIX("s_cbranch_execz 1f\n1:\n")) ::: CLOB);           // EXEC is never empty here: not taken
+    if (V == 17) asm volatile(REP4(MIX("s_and_saveexec_b64 s[42:43], exec\n s_or_b64 exec, exec, s[42:43]\n")) ::: CLOB, "scc");   // EXEC unchanged; SCC is not (undeclared, the loop test may be set in front of the block and read behind it)
   }
   __builtin_amdgcn_s_waitcnt(0);
   const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -132,5 +138,8 @@ int main() {
   BOTH(12, "fma + s_nop 1:1", 64, 64)
   BOTH(13, "fma + v_cndmask_b32 1:1", 64, 64)
   BOTH(14, "fma + ds_bpermute_b32 1:1", 64, 64)
+  BOTH(15, "fma + taken s_branch over 384 B 1:1", 64, 64)
+  BOTH(16, "fma + not-taken s_cbranch_execz 1:1", 64, 64)
+  BOTH(17, "fma + s_and_saveexec / s_or exec pair 1:2", 64, 128)
   return 0;
 }

@@ -1,6 +1,7 @@
 """Instructions of the quad rollout's step loop that only MOVE values (compiler ISA, product flags; no GPU needed).
 usage: python tools/quad_isa_moves.py [kernel-substring] [extra hipcc flags ...]      (default: k_rollout_qILi1ELb0ELb0E)
-Per basic block of the step loop (loop depth 2, program order; blocks of 20 instructions or more) and in total: all instructions, fp64 arithmetic, AGPR reads / writes,
+Per basic block of the step loops (loop depth 2, program order; blocks of 20 instructions or more; GROUPS = 1 has one loop per
+role wave, each announced by its header) and in total over the loops: all instructions, fp64 arithmetic, AGPR reads / writes,
 64-bit and 32-bit vector moves, scalar moves (literal rebuilding), lane moves (spilled scalar registers), scalar loads, LDS
 instructions, vector-memory instructions.  The four role waves are separate blocks: the block that holds the v_rndne_f64 of a
 sin/cos is the trigonometry role (first half) or the psi role (after barrier B), the one with v_log_f32 / v_exp_f32 or v_ldexp_f64
@@ -48,9 +49,12 @@ for m in re.finditer(r"\n(_Z\w+):[^\n]*\n", txt):
     print(m.group(1))
     tot = dict.fromkeys(CL, 0)
     for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body):
-        d = re.search(r"Depth=(\d+)", b[:400])
+        own = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", b[:400])     # (a header names its parent loop's depth first)
+        d = own or re.search(r"Depth=(\d+)", b[:400])
         if not d or int(d.group(1)) < 2:                 # depth 1 is the loop over batches of 16 aircraft: prologue and epilogue
             continue
+        if own:                                          # GROUPS = 1: one step loop per role wave, GROUPS = 2: one for all
+            print(f"  step loop at {b.split(':')[0]}")
         ops = [l.split()[0] for l in b.split("\n")[1:] if l.startswith("\t") and not l.strip().startswith((".", ";"))]
         c = dict.fromkeys(CL, 0)
         for op in ops:
