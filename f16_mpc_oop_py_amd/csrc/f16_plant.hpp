@@ -679,11 +679,12 @@ F16_DEV double lofi_bilin(const double *T, int m, int n, const LofiAlpha &a, dou
 
 F16_DEV void aero_lofi(const double *__restrict__ LT, double alpha, double beta, double el, double dail, double drud,
                        Aero &c, int &status) {
-  // off-table guard: the reference indexes outside its arrays for alpha < -10, alpha > 45, |beta| >= 30
-  if (!(alpha >= -10.0 && alpha <= 45.0)) status |= ST_ALPHA1;
-  if (!(fabs(beta) < 30.0)) status |= ST_BETA;
-  if (!(fabs(el) <= 25.0)) status |= ST_EL;
-  alpha = fmin(fmax(alpha, -10.0), 45.0);
+  // Beyond alpha -10 / 45 deg and beyond the elevator rows the reference EXTRAPOLATES along the last cell (k held at -1 / 8,
+  // "bounds of table for extrapolation", :33-38; m held at -1 / 1, :303-308) with every index inside its array: defined
+  // behaviour, restated as it is, no status bit (k, L and m, n stay inside 1..12 and 1..5 for any input, NaN included).
+  // Only the beta rows of dmomdcon are read past their 7-row tables (:141-150), where fix(0.2 |beta|) >= 6: the row index is
+  // held at 7 and F16_ST_BETA is raised there, on the reference's own index (the product rounds to 6.0 one double below 30 deg
+  // already, so a test on beta itself would miss that value).  A NaN beta raises the bit as well.
   const LofiAlpha a = lofi_alpha(alpha);
   {  // damping :12-56
     const double *A = LT + LOFI_DAMP;
@@ -699,7 +700,8 @@ F16_DEV void aero_lofi(const double *__restrict__ LT, double alpha, double beta,
     const double db = s - m;
     int n = m + 1;
     m = m + 1; n = n + 1;
-    if (n > 7) n = 7;
+    if (n > 7) { n = 7; status |= ST_BETA; }
+    if (beta != beta) status |= ST_BETA;
     c.dCl_a20 = lofi_bilin(LT + LOFI_DLDA, m, n, a, db);
     c.dCl_r30 = lofi_bilin(LT + LOFI_DLDR, m, n, a, db);
     c.dCn_a20 = lofi_bilin(LT + LOFI_DNDA, m, n, a, db);

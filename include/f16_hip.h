@@ -43,6 +43,9 @@ typedef struct f16_ctx f16_ctx;
 #define F16_ST_ALPHA2 2     /* alpha left the ALPHA2 grid [-20,45] deg (lef tables): clamped  */
 #define F16_ST_BETA 4       /* |beta| > 30 deg: clamped                                       */
 #define F16_ST_EL 8         /* |el| > 25 deg: clamped                                         */
+/* (the four grid bits above belong to the hifi tables.  The lofi model extrapolates beyond alpha -10 / 45 deg and beyond its
+ *  elevator rows exactly as the reference's lofi_F16_AeroData.c does, inside its arrays and without a bit; its only off-table
+ *  read is at fix(0.2 |beta|) >= 6, i.e. |beta| >= 30 deg and the one double below it: row held, F16_ST_BETA) */
 #define F16_ST_ENVELOPE 16  /* env.py:117-124 box check failed: aircraft frozen from then on  */
 #define F16_ST_ENV_STATE(k) (1 << (8 + (k))) /* ... and WHICH of the 18 states were outside their box at that step (set with
                                                 F16_ST_ENVELOPE; the reference prints the offending state before it exits)       */

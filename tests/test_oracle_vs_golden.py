@@ -419,6 +419,40 @@ def test_reference_c_rebuilt_here_agrees_with_the_restatement(oracle):
         assert rel(mine, g[f"xdot_hifi_xcg{xcg}"]) < TOL, xcg
 
 
+def test_reference_c_rebuilt_here_agrees_with_the_restatement_on_the_lattice(oracle):
+    """Fixture G18 = the same rebuilt reference C (tools/make_golden.py --g2r) on the whole-grid batch of tests/envelope_cases.py:
+    one aircraft per (alpha, beta, elevator) cell and the edge rows (values on a node, on the first / last node, one ulp beside a
+    node, -0.0, 35,000 ft), wherever the reference is defined: alpha in [-20, 45] (its leading-edge-flap tables end there and its
+    bracket search is undefined off a grid), |beta| <= 30, |elevator| <= 25.  The fixture carries its inputs; they must still be
+    the batch's rows."""
+    import envelope_cases as ec
+    g = golden("g18_lattice_nlplant.npz")
+    b = ec.hifi_lattice(int(g["seed"]))
+    rows, xu = g["rows"], g["xu"]
+    assert np.array_equal(xu.view(np.int64), b.x[rows].view(np.int64))
+    cells = b.cell[rows[rows < b.n_lattice]]
+    assert len(set(map(tuple, cells))) == 13 * 18 * 4 and set(cells[:, 0]) == set(range(13))      # every cell up to alpha = 45
+    named = {k for k, r in b.edge.items() if r in set(rows)}
+    assert {"alpha_node", "beta_node", "el_node", "all_nodes", "alpha_first", "alpha2_last", "beta_first", "beta_last", "el_first",
+            "el_last", "alpha_node_up", "alpha_node_dn", "beta_node_up", "beta_node_dn", "el_node_up", "el_node_dn", "beta_neg_zero",
+            "el_neg_zero", "alt_35000", "alt_below_35000", "climb_0"} <= named
+    for xcg in (25, 35):
+        mine = np.array([oracle.nlplant(x, 1, xcg / 100) for x in xu])
+        assert rel(mine, g[f"xdot_hifi_xcg{xcg}"]) < TOL, xcg
+        assert all(oracle.nlplant(x, 1, xcg / 100) is not None and oracle.lib.f16o_last_status() == 0 for x in xu[::7])
+    # the lofi model: a quarter of its lattice and its edge rows; beyond alpha -10 / 45 deg the reference extrapolates along the last
+    # cell (lofi_F16_AeroData.c:33-38) and so must the restatement, without a status bit
+    lb = ec.lofi_lattice(int(g["seed"]))
+    rows, xu = g["rows_lofi"], g["xu_lofi"]
+    assert np.array_equal(xu.view(np.int64), lb.x[rows].view(np.int64))
+    assert {lb.edge[k] for k in ("off_alpha_hi", "off_alpha_lo", "alpha_first", "alpha_last", "alpha_zero", "el_box", "beta_last")} <= set(rows)
+    assert len(set(lb.cell[rows[rows < lb.n_lattice], 0])) == 11
+    for xcg in (25, 35):
+        mine = np.array([oracle.nlplant(x, 0, xcg / 100) for x in xu])
+        assert rel(mine, g[f"xdot_lofi_xcg{xcg}"]) < TOL, xcg
+        assert oracle.nlplant(lb.x[lb.edge["off_alpha_hi"]], 0, xcg / 100) is not None and oracle.lib.f16o_last_status() == 0
+
+
 def test_closed_mpc_loop_of_the_checker_and_its_rules_for_flagged_aircraft(oracle):
     """oracle.mpc_closed_loop (oracle/f16_mpc_oracle.c: f16o_mpc_closed_loop) = test_env.py:480-495 for B aircraft with a frozen model:
     equal to the same loop written out call by call (QP of the reference's setup_OSQP, the C solve, one `step`), and the stated rules for

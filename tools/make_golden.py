@@ -624,6 +624,53 @@ def g2r_ref_rebuilt(n=400):
             raise SystemExit("_CLr stopped reading ~0 during the run: run the script again")
     np.savez_compressed(os.path.join(OUT, "g2r_ref_rebuilt.npz"), **g)
     print("g2r_ref_rebuilt.npz", os.path.getsize(os.path.join(OUT, "g2r_ref_rebuilt.npz")))
+    g18_lattice_nlplant(libs)
+
+
+def g18_lattice_nlplant(libs, limit=586653):
+    """G18: the same rebuilt reference C on the whole-grid batch of tests/envelope_cases.py (hifi_lattice: one aircraft per table cell
+    plus the edge rows), both xcg builds.  Only rows on which the reference is defined: off the grid of ANY table its bracket search
+    leaves the cell index uninitialised (C/mexndinterp.c:121-124), and the leading-edge-flap tables end at alpha = 45 deg, so the rows
+    are those with alpha in [-20, 45], |beta| <= 30, |elevator| <= 25 (13 of the 19 alpha cells; the ALPHA1-only tables above 45 deg
+    are pinned per table by G1), and the lofi model on a quarter of lofi_lattice and its edge rows, the rows beyond alpha -10 / 45 deg
+    included (defined there: it extrapolates).  Row numbers, inputs and outputs -- data only; subsampled if it would outgrow the largest fixture."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import envelope_cases as ec
+    b = ec.hifi_lattice()
+    v = ec.axis_values(b)
+    rows = np.nonzero((v[:, 0] >= -20) & (v[:, 0] <= 45) & (np.abs(v[:, 1]) <= 30) & (np.abs(v[:, 2]) <= 25))[0]
+    step = 1
+    while True:
+        keep = np.union1d(rows[rows < b.n_lattice][::step], rows[rows >= b.n_lattice])       # every edge row stays
+        g = {"seed": np.array(ec.SEED), "rows": keep, "xu": b.x[keep]}
+        for k, L in libs.items():
+            out = np.zeros((len(keep), 18))
+            for i, x in enumerate(b.x[keep]):
+                x = np.ascontiguousarray(x)
+                L.Nlplant(dptr(x), dptr(out[i]), ctypes.c_int(1))
+            g[f"xdot_hifi_xcg{k}"] = out
+        # the lofi model on its own lattice (every fourth cell) and every edge row but |beta| >= 30 deg, where the reference reads
+        # past its 7-row tables (lofi_F16_AeroData.c:141-150); beyond alpha -10 / 45 deg it extrapolates, and those rows are kept
+        lb = ec.lofi_lattice()
+        lv = ec.axis_values(lb)
+        lrows = np.nonzero(np.abs(lv[:, 1]) < 30)[0]
+        lkeep = np.union1d(lrows[lrows < lb.n_lattice][::4 * step], lrows[lrows >= lb.n_lattice])
+        g["rows_lofi"], g["xu_lofi"] = lkeep, lb.x[lkeep]
+        for k, L in libs.items():
+            out = np.zeros((len(lkeep), 18))
+            for i, x in enumerate(lb.x[lkeep]):
+                x = np.ascontiguousarray(x)
+                L.Nlplant(dptr(x), dptr(out[i]), ctypes.c_int(0))
+            g[f"xdot_lofi_xcg{k}"] = out
+        for k in libs:
+            if not clr_reads_zero(libs[k]):
+                raise SystemExit("_CLr stopped reading ~0 during the run: run the script again")
+        path = os.path.join(OUT, "g18_lattice_nlplant.npz")
+        np.savez_compressed(path, **g)
+        if os.path.getsize(path) <= limit:
+            break
+        step += 1
+    print("g18_lattice_nlplant.npz", os.path.getsize(path), len(keep), "rows, lattice step", step)
 
 
 def g17_input_schedules():
