@@ -28,6 +28,7 @@
 #include "f16_mpc.hpp"
 #include "f16_mpc_model.hpp"
 #include "f16_mpc_state.hpp"
+#include "f16_osqp_rules.hpp"
 
 namespace f16 {
 
@@ -576,7 +577,7 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
           for (int rr = 0; rr < 6; ++rr) { const double gv = G[(i - jb) * 27 + SROW[rr] * 3 + c]; s += E9[9 * i + SROW[rr]] * gv * gv; }
         tp += Pg[tri(e, e)]; ta += s;
       }
-      rho = fmin(fmax(RHO_AUTO_SCALE * sqrt(wave_sum(tp) / wave_sum(ta)), OSQP_RHO_MIN), OSQP_RHO_MAX);
+      rho = osqp_rho_start(wave_sum(tp), wave_sum(ta));
     }
     bool ok = build_minv(rho);
     for (int e = l; e < n; e += F16_WAVE) xs[e] = 0.0;
@@ -652,7 +653,7 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
         const double np_ = fmax(wave_max(nAx), wave_max(nz));
         const double nd_ = fmax(fmax(wave_max(nPx), wave_max(nAty)), wave_max(nq));
         __syncthreads();
-        if (rp < a.s.eps_abs + a.s.eps_rel * np_ && rd < a.s.eps_abs + a.s.eps_rel * nd_) { done = true; converged = true; }
+        if (osqp_converged(rp, rd, np_, nd_, a.s.eps_abs, a.s.eps_rel)) { done = true; converged = true; }
         else {
           // OSQP primal-infeasibility certificate on dy (auxil.c:is_primal_infeasible)
           double ndy = 0.0, supp = 0.0;
@@ -668,22 +669,21 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
           ndy = wave_max(ndy);
           supp = wave_sum(supp);
           __syncthreads();
-          if (ndy > a.s.eps_prim_inf && supp < -a.s.eps_prim_inf * ndy) {
+          if (osqp_infeasibility_candidate(ndy, supp, a.s.eps_prim_inf)) {
             conv_adjoint<6>(tv, G, wbuf, N, SROW);
             double nat = 0.0;
             for (int e = l; e < n; e += F16_WAVE) nat = fmax(nat, fabs(adjoint(wbuf, e)));
             nat = wave_max(nat);
-            if (nat < a.s.eps_prim_inf * ndy) { done = true; infeasible = true; }
+            if (osqp_infeasibility_certified(nat, ndy, a.s.eps_prim_inf)) { done = true; infeasible = true; }
           }
           __syncthreads();
         }
         if (done) {}
         else if (it >= a.s.max_iter) done = true;
         else if (a.s.adaptive_rho && it % a.s.rho_every == 0) {     // auxil.c:compute_rho_estimate (scaled residuals)
-          const double pr = wave_max(r1s) / (fmax(wave_max(nzs), wave_max(nAxs)) + 1e-10);
-          const double dr = wave_max(r2s) / (fmax(fmax(wave_max(nqs), wave_max(nAtys)), wave_max(nPxs)) + 1e-10);
-          const double nw = fmin(fmax(rho * sqrt(pr / (dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-          if (nw > OSQP_ADAPTIVE_RHO_TOLERANCE * rho || nw < rho / OSQP_ADAPTIVE_RHO_TOLERANCE) {
+          const double nw = osqp_rho_estimate(rho, wave_max(r1s), wave_max(nzs), wave_max(nAxs), wave_max(r2s), wave_max(nqs), wave_max(nAtys),
+                                              wave_max(nPxs));
+          if (osqp_rho_accepted(nw, rho)) {
             rho = nw;
             if (!build_minv(rho)) done = true;
           }
@@ -693,16 +693,7 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
     // res.x[0:3] (env.py:424); OSQP hands back NaN for a problem it certifies infeasible
     for (int e = l; e < 3; e += F16_WAVE) a.ucmd[e * a.ld + b] = infeasible ? NAN : xs[e];
     if (a.useq) for (int e = l; e < n; e += F16_WAVE) a.useq[e * a.ld + b] = infeasible ? NAN : xs[e];
-    if (l == 0) {
-      if (a.info) {
-        a.info[0 * a.ld + b] = (double)it;
-        a.info[1 * a.ld + b] = rp;
-        a.info[2 * a.ld + b] = rd;
-        a.info[3 * a.ld + b] = rho;
-      }
-      if (a.status && infeasible) a.status[b] |= F16_ST_QP_INFEASIBLE;
-      else if (a.status && a.s.max_iter > 0 && (!converged || !ok)) a.status[b] |= F16_ST_QP_MAXITER;
-    }
+    if (l == 0) mpc_write_result(a.info, nullptr, a.status, a.ld, b, it, rp, rd, rho, mpc_status_bits(converged, infeasible, ok, a.s.max_iter));
     __syncthreads();
   }
 }

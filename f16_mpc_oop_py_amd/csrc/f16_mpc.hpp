@@ -1,5 +1,7 @@
-// f16_mpc.hpp -- shared definitions of the MPC kernels (f16_control.hip: QP build + generic ADMM;
-// f16_mpc_solve.hip: register-resident ADMM for N <= 32).
+// f16_mpc.hpp -- shared definitions of the MPC kernels (f16_control.hip: QP build + generic ADMM, N <= 40; f16_mpc_solve.hip:
+// register-resident ADMM on 512 lanes, N <= 32; f16_mpc_big.hip: operands in HBM, 33 <= N <= 150, and the horizon sweep;
+// f16_mpc_wave.hip: one wavefront per aircraft, N <= 30, and the closed loops).  What the four solvers decide from their reduced
+// norms -- OSQP's stopping, rho and status rules -- is stated once, in f16_osqp_rules.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -106,6 +108,14 @@ __device__ __forceinline__ void mpc_write_nonfinite(double *ucmd, double *useq, 
     if (info) { info[0 * ld + b] = 0.0; info[1 * ld + b] = nan_; info[2 * ld + b] = nan_; info[3 * ld + b] = rho; }
     if (status) status[b] |= F16_ST_NONFINITE;
   }
+}
+// The lane-0 part of a finished solve: iteration count, info = it, rp, rd, rho, and the status bits of mpc_status_bits
+// (f16_osqp_rules.hpp).  The commands are stored by the lanes that own them, per solver.
+__device__ __forceinline__ void mpc_write_result(double *info, int32_t *iters_out, int32_t *status, long ld, long b, int it, double rp,
+                                                 double rd, double rho, int32_t bits) {
+  if (iters_out) iters_out[b] = it;
+  if (info) { info[0 * ld + b] = (double)it; info[1 * ld + b] = rp; info[2 * ld + b] = rd; info[3 * ld + b] = rho; }
+  if (status && bits) status[b] |= bits;
 }
 __host__ __device__ inline size_t mpc_big_doubles(int N) {      // (see k_mpc<false, true>)
   const size_t rows = (size_t)64 * ((12 * N + 63) / 64), n = (size_t)3 * N;

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "f16_mpc.hpp"
+#include "f16_osqp_rules.hpp"
 #include "f16_smallmat.hpp"
 
 namespace f16 {
@@ -774,7 +775,7 @@ __global__ __launch_bounds__(BLK) void k_mpc_big(MpcArgs a, const SweepArgs sw) 
       double tp = 0.0, ta = 0.0;
       for (int e = l; e < n; e += BLK) { tp += Pg[tri(e, e)]; ta += gram[tri(e, e)]; }
       tp = block_reduce<true>(tp, L.red); ta = block_reduce<true>(ta, L.red);
-      rho = fmin(fmax(RHO_AUTO_SCALE * sqrt(tp / ta), OSQP_RHO_MIN), OSQP_RHO_MAX);
+      rho = osqp_rho_start(tp, ta);
     }
 #ifdef F16_EXP_STAMPG
     unsigned long long tS[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -900,7 +901,7 @@ __global__ __launch_bounds__(BLK) void k_mpc_big(MpcArgs a, const SweepArgs sw) 
         const double np_ = fmax(block_reduce<false>(nAx, L.red), block_reduce<false>(nz, L.red));
         const double nd_ = fmax(fmax(block_reduce<false>(nPx, L.red), block_reduce<false>(nAty, L.red)), block_reduce<false>(nq, L.red));
         __syncthreads();
-        if (rp < a.s.eps_abs + a.s.eps_rel * np_ && rd < a.s.eps_abs + a.s.eps_rel * nd_) { done = true; converged = true; }
+        if (osqp_converged(rp, rd, np_, nd_, a.s.eps_abs, a.s.eps_rel)) { done = true; converged = true; }
         else {
           // OSQP primal-infeasibility certificate on dy (auxil.c:is_primal_infeasible)
           double ndy = 0.0, supp = 0.0;
@@ -916,24 +917,23 @@ __global__ __launch_bounds__(BLK) void k_mpc_big(MpcArgs a, const SweepArgs sw) 
           ndy = block_reduce<false>(ndy, L.red);
           supp = block_reduce<true>(supp, L.red);
           __syncthreads();
-          if (ndy > a.s.eps_prim_inf && supp < -a.s.eps_prim_inf * ndy) {
+          if (osqp_infeasibility_candidate(ndy, supp, a.s.eps_prim_inf)) {
             tp_partials<true>(part, Gc, G, wbuf, L.zpad, N);
             __syncthreads();
             double nat = 0.0;
             for (int e = l; e < n; e += BLK) nat = fmax(nat, fabs(adjoint(wbuf, e)));
             nat = block_reduce<false>(nat, L.red);
-            if (nat < a.s.eps_prim_inf * ndy) { done = true; infeasible = true; }
+            if (osqp_infeasibility_certified(nat, ndy, a.s.eps_prim_inf)) { done = true; infeasible = true; }
           }
           __syncthreads();
         }
         if (done) {}
         else if (it >= a.s.max_iter) done = true;
         else if (a.s.adaptive_rho && it % a.s.rho_every == 0) {     // auxil.c:compute_rho_estimate (scaled residuals)
-          const double pr = block_reduce<false>(r1s, L.red) / (fmax(block_reduce<false>(nzs, L.red), block_reduce<false>(nAxs, L.red)) + 1e-10);
-          const double dr = block_reduce<false>(r2s, L.red) /
-                            (fmax(fmax(block_reduce<false>(nqs, L.red), block_reduce<false>(nAtys, L.red)), block_reduce<false>(nPxs, L.red)) + 1e-10);
-          const double nw = fmin(fmax(rho * sqrt(pr / (dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-          if (nw > OSQP_ADAPTIVE_RHO_TOLERANCE * rho || nw < rho / OSQP_ADAPTIVE_RHO_TOLERANCE) {
+          const double nw = osqp_rho_estimate(rho, block_reduce<false>(r1s, L.red), block_reduce<false>(nzs, L.red), block_reduce<false>(nAxs, L.red),
+                                              block_reduce<false>(r2s, L.red), block_reduce<false>(nqs, L.red), block_reduce<false>(nAtys, L.red),
+                                              block_reduce<false>(nPxs, L.red));
+          if (osqp_rho_accepted(nw, rho)) {
             rho = nw;
             if (!build_minv(rho)) { ok = false; done = true; }
           }
@@ -948,19 +948,13 @@ __global__ __launch_bounds__(BLK) void k_mpc_big(MpcArgs a, const SweepArgs sw) 
     if (a.useq && l == 0) for (int e = 0; e < 12; ++e) a.useq[e * a.ld + b] = (double)tS[e];     // diagnostic build: cycles per phase (s_memtime)
 #endif
     if (l == 0) {
-      if (a.iters_out) a.iters_out[b] = it;
-      if (a.info) {
-        a.info[0 * a.ld + b] = (double)it;
-        a.info[1 * a.ld + b] = rp;
-        a.info[2 * a.ld + b] = rd;
-        a.info[3 * a.ld + b] = rho;
+      mpc_write_result(a.info, a.iters_out, a.status, a.ld, b, it, rp, rd, rho, mpc_status_bits(converged, infeasible, ok, a.s.max_iter));
 #ifdef F16_EXP_STAMPG
+      if (a.info) {
         a.info[1 * a.ld + b] = (double)wc0;                // diagnostic build: start / end of this solve on the 100 MHz clock
         a.info[2 * a.ld + b] = (double)wall_clock64();
-#endif
       }
-      if (a.status && infeasible) a.status[b] |= F16_ST_QP_INFEASIBLE;
-      else if (a.status && a.s.max_iter > 0 && (!converged || !ok)) a.status[b] |= F16_ST_QP_MAXITER;
+#endif
     }
     __syncthreads();
   }

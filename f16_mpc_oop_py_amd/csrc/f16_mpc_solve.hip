@@ -31,6 +31,7 @@
 #include <mutex>
 
 #include "f16_mpc.hpp"
+#include "f16_osqp_rules.hpp"
 #include "f16_smallmat.hpp"
 
 namespace f16 {
@@ -94,46 +95,6 @@ __device__ double g_it_stamp[8 * 6];    // per wave: cycles in phase A, barrier,
 __device__ double g_f_stamp[8];         // last factorisation of workgroup 0: Gram, assembly, sweep, re-layout; equilibration; iterations stamped
 #endif
 constexpr int NT = FN / 16;   // 6 tile rows / columns
-
-// 1/x to <= 1 ulp without the division sequence (v_rcp_f64 + two Newton steps); x is a positive, normal pivot minor
-__device__ __forceinline__ double rcp_nr(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return r;
-}
-
-// inverse of a 4x4 SPD block given by its lower triangle; false if a leading minor is not positive
-__device__ __forceinline__ bool inv4_spd(const double (&d)[4][4], double (&o)[4][4]) {
-  const double a = d[0][0], b = d[1][0], c = d[1][1];
-  const double detA = a * c - b * b;
-  const double ia = rcp_nr(detA);
-  const double A00 = c * ia, A10 = -b * ia, A11 = a * ia;                  // A^-1
-  const double B00 = d[2][0], B01 = d[2][1], B10 = d[3][0], B11 = d[3][1];  // rows 2,3 x cols 0,1
-  const double T00 = B00 * A00 + B01 * A10, T01 = B00 * A10 + B01 * A11;    // T = B A^-1
-  const double T10 = B10 * A00 + B11 * A10, T11 = B10 * A10 + B11 * A11;
-  const double S00 = d[2][2] - (T00 * B00 + T01 * B01);                     // S = E - T B'
-  const double S10 = d[3][2] - (T10 * B00 + T11 * B01);
-  const double S11 = d[3][3] - (T10 * B10 + T11 * B11);
-  const double detS = S00 * S11 - S10 * S10;
-  const double is = rcp_nr(detS);
-  const double I00 = S11 * is, I10 = -S10 * is, I11 = S00 * is;            // S^-1
-  const double L00 = -(I00 * T00 + I10 * T10), L01 = -(I00 * T01 + I10 * T11);   // -S^-1 T
-  const double L10 = -(I10 * T00 + I11 * T10), L11 = -(I10 * T01 + I11 * T11);
-  o[2][2] = I00; o[3][2] = o[2][3] = I10; o[3][3] = I11;
-  o[2][0] = o[0][2] = L00; o[2][1] = o[1][2] = L01; o[3][0] = o[0][3] = L10; o[3][1] = o[1][3] = L11;
-  o[0][0] = A00 - (T00 * L00 + T10 * L10);                                    // A^-1 + T' S^-1 T
-  o[1][0] = o[0][1] = A10 - (T01 * L00 + T11 * L10);
-  o[1][1] = A11 - (T01 * L01 + T11 * L11);
-  return a > 0.0 && detA > 0.0 && S00 > 0.0 && detS > 0.0;
-}
-
-// lane-dependent pick of one of four values.  Scalars BY VALUE on purpose: with an array reference the optimiser turns
-// the selects into a dynamically indexed load before inlining, and the array then lives in scratch memory.
-__device__ __forceinline__ double sel4(double v0, double v1, double v2, double v3, int k) {
-  const double lo = (k & 1) ? v1 : v0, hi = (k & 1) ? v3 : v2;
-  return (k & 2) ? hi : lo;
-}
 
 // Panel buffer of one block step: C[col][0..3] = M[pivot row][col] (FN x 4), then D^-1 (4 x 4, row-major) and a flag.
 constexpr int PAN_DI = FN * 4, PAN_OK = FN * 4 + 16, PAN_SIZE = FN * 4 + 18;
@@ -350,26 +311,17 @@ __global__ __launch_bounds__(FT) void k_dbg_inverse(const double *pk, double *ou
 // ---------------------------------------------------------------------------------------------------------------
 // Cross-lane sums over the 16 lanes of a DPP row by recursive halving: at each of the first steps a lane keeps half of
 // its values and hands the other half to its mirror partner, so V values cost about V + log steps instead of 4 V.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HMIRROR = 0x141, DPP_MIRROR = 0x140;
-
 // h,g,e = bits 3,2,1 of the lane's position in its row.  Totals land in: lanes 0-3 v0, 4-7 v1, 8-11 v2 (12-15: 0)
 __device__ __forceinline__ double reduce3(double v0, double v1, double v2, bool h, bool g) {
   const double s0 = h ? v0 : v2, s1 = h ? v1 : 0.0;
   double k0 = h ? v2 : v0, k1 = h ? 0.0 : v1;
-  k0 += dpp_f64<DPP_MIRROR>(s0);
-  k1 += dpp_f64<DPP_MIRROR>(s1);
+  k0 += dpp_all_f64<DPP_MIRROR>(s0);
+  k1 += dpp_all_f64<DPP_MIRROR>(s1);
   const double s = g ? k0 : k1;
   double k = g ? k1 : k0;
-  k += dpp_f64<DPP_HMIRROR>(s);
-  k += dpp_f64<DPP_XOR2>(k);
-  k += dpp_f64<DPP_XOR1>(k);
+  k += dpp_all_f64<DPP_HMIRROR>(s);
+  k += dpp_all_f64<DPP_XOR2>(k);
+  k += dpp_all_f64<DPP_XOR1>(k);
   return k;
 }
 // The same with the three inputs in SLOT ORDER -- a = the value this lane's half of the row keeps (h ? v2 : v0), b = v1,
@@ -377,13 +329,13 @@ __device__ __forceinline__ double reduce3(double v0, double v1, double v2, bool 
 // (stage 2: the rows of the re-laid KKT inverse), which removes the four selects of the mirror step.  v1 is summed on both
 // halves (the upper half's copy ends in lanes 12-15, which own nothing).
 __device__ __forceinline__ double reduce3_slots(double a, double b, double c, bool g) {
-  const double k0 = a + dpp_f64<DPP_MIRROR>(c);
-  const double k1 = b + dpp_f64<DPP_MIRROR>(b);
+  const double k0 = a + dpp_all_f64<DPP_MIRROR>(c);
+  const double k1 = b + dpp_all_f64<DPP_MIRROR>(b);
   const double s = g ? k0 : k1;
   double k = g ? k1 : k0;
-  k += dpp_f64<DPP_HMIRROR>(s);
-  k += dpp_f64<DPP_XOR2>(k);
-  k += dpp_f64<DPP_XOR1>(k);
+  k += dpp_all_f64<DPP_HMIRROR>(s);
+  k += dpp_all_f64<DPP_XOR2>(k);
+  k += dpp_all_f64<DPP_XOR1>(k);
   return k;
 }
 // reduce4: quad k of the row (lanes 4k..4k+3) ends up with the total of v[k] -- mirror step keeps two of the four values
@@ -397,11 +349,11 @@ __device__ __forceinline__ int slot_of(int slot, bool h, bool g) {
   return slot == 0 ? 2 * hh + gg : (slot == 1 ? 2 * hh + (1 - gg) : (slot == 2 ? 2 * (1 - hh) + (1 - gg) : 2 * (1 - hh) + gg));
 }
 __device__ __forceinline__ double reduce4_slots(d4_t p) {
-  const double k0 = p[0] + dpp_f64<DPP_MIRROR>(p[2]);
-  const double k1 = p[1] + dpp_f64<DPP_MIRROR>(p[3]);
-  double k = k0 + dpp_f64<DPP_HMIRROR>(k1);
-  k += dpp_f64<DPP_XOR2>(k);
-  k += dpp_f64<DPP_XOR1>(k);
+  const double k0 = p[0] + dpp_all_f64<DPP_MIRROR>(p[2]);
+  const double k1 = p[1] + dpp_all_f64<DPP_MIRROR>(p[3]);
+  double k = k0 + dpp_all_f64<DPP_HMIRROR>(k1);
+  k += dpp_all_f64<DPP_XOR2>(k);
+  k += dpp_all_f64<DPP_XOR1>(k);
   return k;
 }
 // totals land in: lanes 0,1 v0 | 2,3 v1 | 4-7 v2 | 8,9 v3 | 10,11 v4 | 12-15 v5.  The six inputs come in slot order:
@@ -410,18 +362,18 @@ __device__ __forceinline__ double reduce4_slots(d4_t p) {
 // removes the twelve selects of the first step.
 __device__ __forceinline__ double reduce6_slots(double p0, double p1, double p2, double p3, double p4, double p5, bool g,
                                                 bool e) {
-  const double k0 = p0 + dpp_f64<DPP_MIRROR>(p3);
-  const double k1 = p1 + dpp_f64<DPP_MIRROR>(p4);
-  const double k2 = p2 + dpp_f64<DPP_MIRROR>(p5);
+  const double k0 = p0 + dpp_all_f64<DPP_MIRROR>(p3);
+  const double k1 = p1 + dpp_all_f64<DPP_MIRROR>(p4);
+  const double k2 = p2 + dpp_all_f64<DPP_MIRROR>(p5);
   const double t0 = g ? k0 : k2, t1 = g ? k1 : 0.0;
   double n0 = g ? k2 : k0, n1 = g ? 0.0 : k1;
-  n0 += dpp_f64<DPP_HMIRROR>(t0);
-  n1 += dpp_f64<DPP_HMIRROR>(t1);
+  n0 += dpp_all_f64<DPP_HMIRROR>(t0);
+  n1 += dpp_all_f64<DPP_HMIRROR>(t1);
   const bool lo2 = !g && !e, hi2 = !g && e;
   const double u = lo2 ? n1 : n0;
   double r = hi2 ? n1 : n0;
-  r += dpp_f64<DPP_XOR2>(u);
-  r += dpp_f64<DPP_XOR1>(r);
+  r += dpp_all_f64<DPP_XOR2>(u);
+  r += dpp_all_f64<DPP_XOR1>(r);
   return r;
 }
 
@@ -470,10 +422,10 @@ constexpr int XTP = XOFF + FN + 8;
 
 // max over the 16 lanes of a DPP row, the result in every lane (values >= 0)
 __device__ __forceinline__ double row_allmax(double v) {
-  v = fmax(v, dpp_f64<DPP_XOR1>(v));
-  v = fmax(v, dpp_f64<DPP_XOR2>(v));
-  v = fmax(v, dpp_f64<DPP_HMIRROR>(v));
-  v = fmax(v, dpp_f64<DPP_MIRROR>(v));
+  v = fmax(v, dpp_all_f64<DPP_XOR1>(v));
+  v = fmax(v, dpp_all_f64<DPP_XOR2>(v));
+  v = fmax(v, dpp_all_f64<DPP_HMIRROR>(v));
+  v = fmax(v, dpp_all_f64<DPP_MIRROR>(v));
   return v;
 }
 
@@ -868,7 +820,7 @@ __device__ __noinline__ bool kkt_factorise(const double *Pg, double *gw, bool ha
       }
     const bool sums[2] = {true, true};
     block_reduce<2>(tr, sums, s_red);
-    rho = fmin(fmax(RHO_AUTO_SCALE * sqrt(tr[0] / tr[1]), OSQP_RHO_MIN), OSQP_RHO_MAX);
+    rho = osqp_rho_start(tr[0], tr[1]);
     *rho_io = rho;
   }
 #pragma unroll
@@ -926,7 +878,6 @@ struct SolveState {
   int it, to_check;
   int done, converged, infeasible;
 };
-struct IterSettings { double alpha, eps_abs, eps_rel, eps_prim_inf; int max_iter, check_every, rho_every, adaptive_rho; };
 
 // One 512-lane workgroup per aircraft, three barriers per ADMM iteration:
 //   A  stage 1 partials + row reduce -> rhs = sigma D^-2 x - c q + A' W (rho z - y)                | barrier
@@ -1073,11 +1024,11 @@ __device__ __noinline__ int admm_iterate(SolveState *st, const double *mrow_in, 
       block_reduce<9>(v, issum, s_red);
       rp = v[0]; rd = v[3];
       const double np_ = fmax(v[1], v[2]), nd_ = fmax(fmax(v[4], v[5]), v[6]);
-      if (rp < o.eps_abs + o.eps_rel * np_ && rd < o.eps_abs + o.eps_rel * nd_) { done = true; converged = true; }
+      if (osqp_converged(rp, rd, np_, nd_, o.eps_abs, o.eps_rel)) { done = true; converged = true; }
       else {
         // OSQP primal-infeasibility certificate on dy (auxil.c:is_primal_infeasible)
         const double ndy = v[7], supp = v[8];
-        if (ndy > o.eps_prim_inf && supp < -o.eps_prim_inf * ndy) {
+        if (osqp_infeasibility_candidate(ndy, supp, o.eps_prim_inf)) {
           if (kind) { const double de = Wl * dy; ydst[0] = de; ydst[dup] = de; }
           __syncthreads();
           { double wv[12]; stage1_load(ysrc, wv); stage1_fma(Gd, wv, o1); }
@@ -1085,7 +1036,7 @@ __device__ __noinline__ int admm_iterate(SolveState *st, const double *mrow_in, 
           double wv[1] = {xown ? fabs(t + s_yc[xe] + (s_yr[xe] - s_yr[xe + 3])) : 0.0};
           const bool km[1] = {false};
           block_reduce<1>(wv, km, s_red);
-          if (wv[0] < o.eps_prim_inf * ndy) { done = true; infeasible = true; }
+          if (osqp_infeasibility_certified(wv[0], ndy, o.eps_prim_inf)) { done = true; infeasible = true; }
         }
         if (!done) {
           if (it >= o.max_iter) done = true;
@@ -1097,9 +1048,8 @@ __device__ __noinline__ int admm_iterate(SolveState *st, const double *mrow_in, 
             if (xown) { sv[3] = cD * fabs(px + qu + aty); sv[4] = cD * fabs(px); sv[5] = cD * fabs(aty); sv[6] = cD * fabs(qu); }
             const bool mx[7] = {false, false, false, false, false, false, false};
             block_reduce<7>(sv, mx, s_red);
-            const double pr = sv[0] / (fmax(sv[2], sv[1]) + 1e-10), dr = sv[3] / (fmax(fmax(sv[6], sv[5]), sv[4]) + 1e-10);
-            const double nw = fmin(fmax(rho * sqrt(pr / (dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-            if (nw > OSQP_ADAPTIVE_RHO_TOLERANCE * rho || nw < rho / OSQP_ADAPTIVE_RHO_TOLERANCE) { rho = nw; refactor = true; }
+            const double nw = osqp_rho_estimate(rho, sv[0], sv[2], sv[1], sv[3], sv[6], sv[5], sv[4]);
+            if (osqp_rho_accepted(nw, rho)) { rho = nw; refactor = true; }
           }
         }
       }
@@ -1237,9 +1187,7 @@ __global__ __launch_bounds__(FT) void k_mpc_fast(MpcArgs a) {
   if (a.mode == 2 && !(exm[244] > 0.5)) ok = false;
   __syncthreads();                                            // weights / sigma D^-2 / lane constants are in place
   double *const gw = a.gramws ? a.gramws + (size_t)b * MPC_TILE_DOUBLES : nullptr;
-  IterSettings o;
-  o.alpha = a.s.alpha; o.eps_abs = a.s.eps_abs; o.eps_rel = a.s.eps_rel; o.eps_prim_inf = a.s.eps_prim_inf;
-  o.max_iter = a.s.max_iter; o.check_every = a.s.check_every; o.rho_every = a.s.rho_every; o.adaptive_rho = a.s.adaptive_rho;
+  const IterSettings o = iter_settings(a.s);
   bool have_inverse = a.mode == 2, have_gram = false;
   bool done = a.s.max_iter < 0;                               // (max_iter == 0: factor only, used for timing)
   while (!done) {
@@ -1267,17 +1215,8 @@ __global__ __launch_bounds__(FT) void k_mpc_fast(MpcArgs a) {
     if (xe < 3) a.ucmd[xe * a.ld + b] = infeasible ? NAN : st.xs;
     if (a.useq) a.useq[xe * a.ld + b] = infeasible ? NAN : st.xs;
   }
-  if (tid == 0) {
-    if (a.iters_out) a.iters_out[b] = st.it;
-    if (a.info) {
-      a.info[0 * a.ld + b] = (double)st.it;
-      a.info[1 * a.ld + b] = st.rp;
-      a.info[2 * a.ld + b] = st.rd;
-      a.info[3 * a.ld + b] = st.rho;
-    }
-    if (a.status && infeasible) a.status[b] |= F16_ST_QP_INFEASIBLE;
-    else if (a.status && a.s.max_iter > 0 && (!converged || !ok)) a.status[b] |= F16_ST_QP_MAXITER;
-  }
+  if (tid == 0)
+    mpc_write_result(a.info, a.iters_out, a.status, a.ld, b, st.it, st.rp, st.rd, st.rho, mpc_status_bits(converged, infeasible, ok, a.s.max_iter));
 #ifdef F16_EXP_STAMPM
   __syncthreads();      // diagnostic build: the u_seq column of the aircraft solved by workgroup 0 is replaced by the stamps
   if (blockIdx.x == 0 && a.useq) {

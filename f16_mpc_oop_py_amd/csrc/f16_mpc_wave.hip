@@ -37,6 +37,7 @@
 #include "f16_mpc.hpp"
 #include "f16_mpc_model.hpp"
 #include "f16_mpc_state.hpp"
+#include "f16_osqp_rules.hpp"
 #include "f16_plant.hpp"
 #include "f16_smallmat.hpp"
 #include "f16_wave_tables.inc"
@@ -102,14 +103,6 @@ __device__ __forceinline__ int tile_idx(int w, int J) { return w * (w + 1) / 2 +
 typedef const double __attribute__((address_space(1))) *gptr_t;
 __device__ __forceinline__ gptr_t as_global(const double *p) { return (gptr_t)p; }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HMIRROR = 0x141;
 __device__ __forceinline__ double bperm(double v, int src_lane) {
   const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v));
   const int hi = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2hiint(v));
@@ -156,7 +149,6 @@ struct SolveState {
   double rho, rp, rd;
   int it, to_check, done, converged, infeasible;
 };
-struct IterSettings { double alpha, eps_abs, eps_rel, eps_prim_inf; int max_iter, check_every, rho_every, adaptive_rho; };
 
 // ----------------------------------------------------------------------------------------------------------------
 // The two block-Toeplitz stages (utils.py:171-197: CC[i,j] = A^(i-j) B, never formed; stage 3 = CCs x~, stage 1 = CCs' w) with
@@ -306,7 +298,7 @@ __device__ __forceinline__ void stage1_totals(const int (&a1)[9], double (&out)[
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double t = (((v[0][c] + v[1][c]) + (v[2][c] + v[3][c])) + ((v[4][c] + v[5][c]) + (v[6][c] + v[7][c]))) + v[8][c];
-    out[c] = t + dpp<DPP_XOR1>(t);
+    out[c] = t + dpp_all_f64<DPP_XOR1>(t);
   }
 }
 // LDS addresses of the records a lane consumes: its step istep = 5 I + e, kept rows 3h..3h+2 (stage 3); its pair's half of the
@@ -371,8 +363,8 @@ __device__ __forceinline__ void sym_matvec_core(const double (&A)[6][6], const d
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       double sm = yd[j] + qa[j] + (R.s < 3 ? qb[j] : 0.0);
-      sm += dpp<DPP_XOR1>(sm);
-      sm += dpp<DPP_XOR2>(sm);
+      sm += dpp_all_f64<DPP_XOR1>(sm);
+      sm += dpp_all_f64<DPP_XOR2>(sm);
       y[j] = sm;
     }
     return;
@@ -381,8 +373,8 @@ __device__ __forceinline__ void sym_matvec_core(const double (&A)[6][6], const d
   for (int j = 0; j < 6; ++j) {
     const double pa = bperm(ytA[j], srcA), pb = bperm(ytB[j], srcB);
     double sm = yd[j] + pa + (R.s < 3 ? pb : 0.0);
-    sm += dpp<DPP_XOR1>(sm);
-    sm += dpp<DPP_XOR2>(sm);
+    sm += dpp_all_f64<DPP_XOR1>(sm);
+    sm += dpp_all_f64<DPP_XOR2>(sm);
     y[j] = sm;
   }
 }
@@ -515,39 +507,6 @@ __device__ __noinline__ void gram_tiles(double *gw, int N) {
 }
 
 // ---- the blocked symmetric sweep (f16_mpc_solve.hip: inverse_step) on all 21 lower-triangular tiles in ONE wavefront.
-__device__ __forceinline__ double rcp_nr(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return r;
-}
-__device__ __forceinline__ bool inv4_spd(const double (&d)[4][4], double (&o)[4][4]) {
-  const double a = d[0][0], b = d[1][0], c = d[1][1];
-  const double detA = a * c - b * b;
-  const double ia = rcp_nr(detA);
-  const double A00 = c * ia, A10 = -b * ia, A11 = a * ia;
-  const double B00 = d[2][0], B01 = d[2][1], B10 = d[3][0], B11 = d[3][1];
-  const double T00 = B00 * A00 + B01 * A10, T01 = B00 * A10 + B01 * A11;
-  const double T10 = B10 * A00 + B11 * A10, T11 = B10 * A10 + B11 * A11;
-  const double S00 = d[2][2] - (T00 * B00 + T01 * B01);
-  const double S10 = d[3][2] - (T10 * B00 + T11 * B01);
-  const double S11 = d[3][3] - (T10 * B10 + T11 * B11);
-  const double detS = S00 * S11 - S10 * S10;
-  const double is = rcp_nr(detS);
-  const double I00 = S11 * is, I10 = -S10 * is, I11 = S00 * is;
-  const double L00 = -(I00 * T00 + I10 * T10), L01 = -(I00 * T01 + I10 * T11);
-  const double L10 = -(I10 * T00 + I11 * T10), L11 = -(I10 * T01 + I11 * T11);
-  o[2][2] = I00; o[3][2] = o[2][3] = I10; o[3][3] = I11;
-  o[2][0] = o[0][2] = L00; o[2][1] = o[1][2] = L01; o[3][0] = o[0][3] = L10; o[3][1] = o[1][3] = L11;
-  o[0][0] = A00 - (T00 * L00 + T10 * L10);
-  o[1][0] = o[0][1] = A10 - (T01 * L00 + T11 * L10);
-  o[1][1] = A11 - (T01 * L01 + T11 * L11);
-  return a > 0.0 && detA > 0.0 && S00 > 0.0 && detS > 0.0;
-}
-__device__ __forceinline__ double sel4(double v0, double v1, double v2, double v3, int k) {
-  const double lo = (k & 1) ? v1 : v0, hi = (k & 1) ? v3 : v2;
-  return (k & 2) ? hi : lo;
-}
 // pan: C[col][0..3] = M[pivot row][col] (FN x 4).  Publish pivots 16 Kt + 4 KQ .. + 3 from the tiles; the pivot block's inverse: P.
 struct PivInv { double2 a0, a1; double dpiv; };      // row l / 16 of the pivot block's inverse, and its element (l / 16, l % 4)
 template <int Kt, int KQ>
@@ -919,8 +878,8 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
     v0 = wave_reduce_dpp<false>(v0); v12 = wave_reduce_dpp<false>(v12);
     v7 = wave_reduce_dpp<false>(v7); v8 = wave_reduce_dpp<true>(v8);
     rp = v0;
-    const bool prim_ok = rp < o.eps_abs + o.eps_rel * v12;
-    const bool cert = v7 > o.eps_prim_inf && v8 < -o.eps_prim_inf * v7;
+    const bool prim_ok = osqp_residual_small(rp, v12, o.eps_abs, o.eps_rel);
+    const bool cert = osqp_infeasibility_candidate(v7, v8, o.eps_prim_inf);
     const bool full = prim_ok || cert || it >= o.max_iter || (o.adaptive_rho && it % o.rho_every == 0);
     WSTAMP(7)
     if (__builtin_amdgcn_readfirstlane((int)full)) break;   // (wave-uniform: the reductions leave the same value on every lane)
@@ -1050,11 +1009,11 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
   TSTAMP(3)
   const double rp = v[0], rd = v[3];
   const double np_ = fmax(v[1], v[2]), nd_ = fmax(fmax(v[4], v[5]), v[6]);
-  if (rp < o.eps_abs + o.eps_rel * np_ && rd < o.eps_abs + o.eps_rel * nd_) { done = true; converged = true; }
+  if (osqp_converged(rp, rd, np_, nd_, o.eps_abs, o.eps_rel)) { done = true; converged = true; }
   else {
     // OSQP primal-infeasibility certificate on dy (auxil.c:is_primal_infeasible)
     const double ndy = v[7], supp = v[8];
-    if (ndy > o.eps_prim_inf && supp < -o.eps_prim_inf * ndy) {
+    if (osqp_infeasibility_candidate(ndy, supp, o.eps_prim_inf)) {
       {
         double eA[3], eB[3];
 #pragma unroll
@@ -1072,7 +1031,7 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
         for (int c = 0; c < 3; ++c) wmax = fmax(wmax, fabs(t3[c] + wc[kx + c] + (wr[kx + c] - wr[kx + c + 3])));
       }
       wmax = wave_reduce_dpp<false>(wmax);
-      if (wmax < o.eps_prim_inf * ndy) { done = true; infeasible = true; }
+      if (osqp_infeasibility_certified(wmax, ndy, o.eps_prim_inf)) { done = true; infeasible = true; }
     }
     if (!done) {
       if (it >= o.max_iter) done = true;
@@ -1093,9 +1052,8 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
         }
 #pragma unroll
         for (int i = 0; i < 7; ++i) sv[i] = wave_reduce_dpp<false>(sv[i]);
-        const double pr = sv[0] / (fmax(sv[2], sv[1]) + 1e-10), dr = sv[3] / (fmax(fmax(sv[6], sv[5]), sv[4]) + 1e-10);
-        const double nw = fmin(fmax(rho * sqrt(pr / (dr + 1e-10)), OSQP_RHO_MIN), OSQP_RHO_MAX);
-        if (nw > OSQP_ADAPTIVE_RHO_TOLERANCE * rho || nw < rho / OSQP_ADAPTIVE_RHO_TOLERANCE) { rho = nw; refactor = true; }
+        const double nw = osqp_rho_estimate(rho, sv[0], sv[2], sv[1], sv[3], sv[6], sv[5], sv[4]);
+        if (osqp_rho_accepted(nw, rho)) { rho = nw; refactor = true; }
       }
     }
   }
@@ -1166,9 +1124,9 @@ struct RuizOut { double De[3], EA[3], EB[3], cs; };
 template <bool IS_MAX>
 __device__ __forceinline__ double octet_allreduce(double v) {
   auto op = [](double a, double b) { return IS_MAX ? fmax(a, b) : a + b; };
-  v = op(v, dpp<DPP_XOR1>(v));
-  v = op(v, dpp<DPP_XOR2>(v));
-  v = op(v, dpp<DPP_HMIRROR>(v));
+  v = op(v, dpp_all_f64<DPP_XOR1>(v));
+  v = op(v, dpp_all_f64<DPP_XOR2>(v));
+  v = op(v, dpp_all_f64<DPP_HMIRROR>(v));
   return v;
 }
 
@@ -1211,8 +1169,8 @@ __device__ __forceinline__ void p_row_norms(const double (&A)[6][6], const doubl
   for (int j = 0; j < 6; ++j) {
     const double pa = bperm(mtA[j], srcA), pb_ = bperm(mtB[j], srcB);
     double m = fmax(md[j], fmax(pa, R.s < 3 ? pb_ : 0.0));
-    m = fmax(m, dpp<DPP_XOR1>(m));
-    m = fmax(m, dpp<DPP_XOR2>(m));
+    m = fmax(m, dpp_all_f64<DPP_XOR1>(m));
+    m = fmax(m, dpp_all_f64<DPP_XOR2>(m));
     if (R.s == 0 && R.r < NB) npm[6 * R.r + j] = dr[j] * m;
   }
 }
@@ -1489,9 +1447,7 @@ __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long jo
   if (job == 0 && l < 8) g_tstamp[l] = 0;
   tK0 = __builtin_amdgcn_s_memtime();
 #endif
-  IterSettings o;
-  o.alpha = a.s.alpha; o.eps_abs = a.s.eps_abs; o.eps_rel = a.s.eps_rel; o.eps_prim_inf = a.s.eps_prim_inf;
-  o.max_iter = a.s.max_iter; o.check_every = a.s.check_every; o.rho_every = a.s.rho_every; o.adaptive_rho = a.s.adaptive_rho;
+  const IterSettings o = iter_settings(a.s);
   const bool anyeq = __ballot((C.eqA | C.eqB) != 0) != 0;      // (wave-uniform)
   const bool ok = anyeq ? solve_loop<true>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R)
                         : solve_loop<false>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R);
@@ -1560,20 +1516,14 @@ __global__ __launch_bounds__(64, 1) void k_mpc_wave(MpcArgs a) {
   }
 #endif
   if (l == 0) {
-    if (a.iters_out) a.iters_out[b] = st.it;
-    if (a.info) {
-      a.info[0 * a.ld + b] = (double)st.it;
-      a.info[1 * a.ld + b] = st.rp;
-      a.info[2 * a.ld + b] = st.rd;
-      a.info[3 * a.ld + b] = st.rho;
+    mpc_write_result(a.info, a.iters_out, a.status, a.ld, b, st.it, st.rp, st.rd, st.rho, mpc_status_bits(converged, infeasible, ok, a.s.max_iter));
 #ifdef F16_EXP_STAMPW
+    if (a.info) {
       a.info[1 * a.ld + b] = (double)wc0_;                 // diagnostic build: start / end of this solve on the 100 MHz clock
       a.info[2 * a.ld + b] = (double)wall_clock64();
       a.info[3 * a.ld + b] = (double)((__builtin_amdgcn_s_getreg(63508) & 15) * 65536 + (__builtin_amdgcn_s_getreg(63492) & 0xFFFF));    // XCC_ID | HW_ID: which SIMD
-#endif
     }
-    if (a.status && infeasible) a.status[b] |= F16_ST_QP_INFEASIBLE;
-    else if (a.status && (!converged || !ok)) a.status[b] |= F16_ST_QP_MAXITER;
+#endif
   }
 #ifdef F16_EXP_STAMPW
   if (job == 0 && l == 0) g_stamp_wg = -1;
@@ -1966,8 +1916,7 @@ __global__ __launch_bounds__(64, 1) void k_rollout_mpc(typename std::conditional
       const double c0 = bcast0_f64(st.x[0]), c1 = bcast0_f64(st.x[1]), c2 = bcast0_f64(st.x[2]);      // res.x[0:3], env.py:424 (lane 0 owns step 0)
       io.iters = __builtin_amdgcn_readfirstlane(st.it);
       io.cmd[0] = infeasible ? NAN : c0; io.cmd[1] = infeasible ? NAN : c1; io.cmd[2] = infeasible ? NAN : c2;
-      if (infeasible) io.stw |= F16_ST_QP_INFEASIBLE;         // OSQP hands back NaN for a problem it certifies infeasible
-      else if (!converged || !uniform_flag(ok)) io.stw |= F16_ST_QP_MAXITER;
+      io.stw |= mpc_status_bits(converged, infeasible, uniform_flag(ok), a.s.max_iter);      // (OSQP hands back NaN for a problem it certifies infeasible)
       wave_lds_sync();
     }
     DBGM(3, 4000 + io.iters)

@@ -969,6 +969,37 @@ def test_horizons_beyond_the_on_chip_solvers_vs_same_algorithm_oracle(mode):
             assert np.abs(u[b].cpu().numpy() - ref["x"][:3]).max() < 1e-8
 
 
+@pytest.mark.parametrize("solver,mode,N,max_iter", [("k_mpc_fast<2>", "builder", 2, 25), ("k_mpc_wave", "osqp", 10, 25),
+                                                    ("k_mpc_big", "builder", 33, 25), ("k_mpc<false>", "builder", 2, -25)])
+def test_max_iter_branch_of_every_solver_vs_same_algorithm_oracle(solver, mode, N, max_iter):
+    """The one branch of the stopping rules (csrc/f16_osqp_rules.hpp) that the horizon tests above leave to a single solver: the
+    solve that ends at max_iter.  Each solver once, at its smallest horizon, with max_iter = the first termination test: on
+    these eight aircraft the CPU twin converges AT that test for some (status 0: convergence is asked before the iteration
+    limit) and not for the others (status 64, the last iterate handed back); the wavefront solver's QPs (OSQP's defaults,
+    which need hundreds of iterations) all stop at the limit.  Iteration counts and status words equal the twin's, the input
+    sequence to the 1e-6 of the horizon tests.  (A negative max_iter selects the generic solver.)"""
+    from f16_mpc_oop_py_amd.workload import config4_states
+    x0, u0 = config4_states(8, seed=21)
+    env = make_env(x0, u0, xcg=0.35)
+    env.build_ssr()
+    Ad, Bd, Cd = _model_np(env)
+    dem = (0.02, -0.01, 0.01)
+    u, info = env._calc_MPC_action(*dem, N, settings=mode_settings(mode, max_iter=max_iter), return_info=True)
+    torch.cuda.synchronize()
+    st, it = info["status"].cpu().numpy(), info["iters"].cpu().numpy()
+    hit = 0
+    for b in range(8):
+        P, q, A, l, uu = mo.mpc_qp(x0[b], Ad[b], Bd[b], Cd[b], N, 0.001, *dem)
+        ref = MODES[mode][1](P, q, A, l, uu, max_iter=abs(max_iter))
+        assert not ref["infeasible"]
+        assert int(it[b]) == ref["iters"], (solver, b)
+        assert int(st[b]) == (0 if ref["converged"] else 64), (solver, b, int(st[b]))
+        assert np.abs(info["u_seq"][b].cpu().numpy() - ref["x"]).max() < 1e-6, (solver, b)
+        assert np.abs(u[b].cpu().numpy() - ref["x"][:3]).max() < 1e-6, (solver, b)
+        hit += not ref["converged"]
+    assert hit >= 2                                             # the case does reach the branch
+
+
 def test_constraint_checking_horizon_sweep_surface(tmp_path):
     """F16._calc_constr_checking_hzn (env.py:426-436): first moves for N = 1..max_hzn, here for a batch, as ONE library call
     (f16_mpc_hzn_sweep: the long horizons solved by a single launch over every (horizon, aircraft) pair, taken from a work
