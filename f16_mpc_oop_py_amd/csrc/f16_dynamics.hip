@@ -670,8 +670,12 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 //                     navigation equations, Euler on x[0..5]; the trajectory sample
 //   wave 3  x[12..17] atmosphere; the four actuators on sub-lanes 0..3; flap model, Euler;  | --
 //                     the LQR law and the input schedule
-// Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached).  GROUPS = 2 keeps
-// the full lookup on every step and psi on wave 2 (sub-lane 2, beta in a second round): the cache's registers spill there.
+// Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached), and with the cells the
+// TABLE VALUES read then (LongCorners / LatCorners, f16_plant_quad.hpp: the four / eight corner sets, the 1-D rows, the 45-degree
+// node): on such a step -- 93 % of the workload's -- a table wave forms no table address and reads nothing from LDS but the
+// published state; the values are re-read on a step on which a lane has left its cell, at launch start and for every group of
+// aircraft.  GROUPS = 2 keeps the full lookup and fresh values on every step and psi on wave 2 (sub-lane 2, beta in a second
+// round): the cache's registers spill there.
 // Owned states are replicated over the sub-lanes of their wave; two barriers per step as in k_rollout_4w.
 // GROUPS = 1: EVERY ROLE HAS A STEP LOOP OF ITS OWN (f16_quad_steps.inc, included once per role): the role index is wave-uniform
 // (readfirstlane), one scalar switch behind the common prologue picks the loop, and a loop holds that role's statements alone.  In one shared loop a wave reached
@@ -684,8 +688,9 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // GROUPS = 2 (4096 < B <= 8192): two independent 16-aircraft groups per workgroup share the LDS table image, one role
 // wave of each on every SIMD -- the two dependency chains interleave.
 // GROUPS = 1 takes the constants of its sin/cos pair and of the atmosphere's exp / log from SCALAR registers: each role loads
-// its own from QUAD_K (constant memory, f16_plant.hpp) at the top of its part of a step -- a few scalar loads that land while the
-// role waits for its LDS reads anyway -- and uses them as the scalar operand of its FMAs.  As literals they cost the
+// its own from QUAD_K (constant memory, f16_plant.hpp) at the top of its part of a step and uses them as the scalar operand of
+// its FMAs.  (The loads were meant to land while the role waits for its LDS reads; in the ISA they are issued BEHIND that wait --
+// wave 2: behind the sample block, wave 3 and wave 0's psi: with the wait for them on the next instruction.  DESIGN.md.)  As literals they cost the
 // trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28 vector registers for
 // the sin/cos table; kept in scalar registers for the whole loop (43 doubles) they push loop masks out into lane moves.
 // Same operations, same operands, same order.
@@ -697,12 +702,18 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
   __shared__ double xs[18][NA], xt[11][NA];                // published state; Cx Cz Cm | Cy Cn Cl static | qbar ps | Cy Cn Cl damping
   __shared__ int xenv[3][NA], xst[2][NA];
   __shared__ double xpsi[3][NA];                           // psi after the step (wave 2 -> wave 0), its sin / cos (wave 0 -> wave 2)
+#ifdef F16_EXP_STAMPQ
+  const unsigned long long tstage0 = __builtin_amdgcn_s_memtime();
+#endif
   {
     const double2 *src = reinterpret_cast<const double2 *>(a.tab);
     double2 *dst = reinterpret_cast<double2 *>(tab);
     for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += 256 * GROUPS) dst[i] = src[i];
     __syncthreads();
   }
+#ifdef F16_EXP_STAMPQ
+  const unsigned long long tstage = __builtin_amdgcn_s_memtime() - tstage0;     // kernel entry to the first barrier: the table staging
+#endif
   // GROUPS = 1: the role index from a scalar register (wave-uniform), so that the role dispatch is a scalar branch
   const int role = G1 ? __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3) : (threadIdx.x >> 6) & 3;
   const int grp = threadIdx.x >> 8, lane = threadIdx.x & 63, ac = 16 * grp + (lane >> 2), s = lane & 3;
@@ -726,6 +737,8 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
     double *tr = a.traj ? a.traj + b : nullptr;            // next sample (written by wave 2 from the published state)
     int until_store = a.traj_every;
     QuadCell qc = quad_cell_none();                        // waves 0 / 1: cells of the last full lookup (none at launch start)
+    LongCorners klong = {};                                // GROUPS = 1, wave 0: the table values of that lookup (a role's loop keeps its own alone)
+    LatCorners klat = {};                                  //             wave 1
     // SCHED: wave 3 owns the inputs and re-loads them right after their last use in a step -- sub-lane s its own command of the
     // new row; under the LQR law sub-lane j = 0..2 demand j (dmq), handed round the quad at the point of use: one 8-byte load
     // per lane and row either way, and four registers fewer than three demands on every sub-lane (GROUPS = 2 has none to spare)
@@ -753,8 +766,14 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
 #define QSTAMP_WAIT 0
 #endif
 #define QSTAMP(acc) { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); unsigned long long t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
+    // the wait for a role's QUAD_K loads: QK_BEGIN in front of reloaded() (LDS reads and earlier scalar loads have landed), QK_END behind it
+    unsigned long long tK = 0, tk0 = 0;
+#define QK_BEGIN { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); tk0 = __builtin_amdgcn_s_memtime(); }
+#define QK_END { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); tK += __builtin_amdgcn_s_memtime() - tk0; }
 #else
 #define QSTAMP(acc)
+#define QK_BEGIN
+#define QK_END
 #endif
     // The step loop (f16_quad_steps.inc).  GROUPS = 1: one copy per role behind a scalar switch; GROUPS = 2: one shared loop, as
     // before (four loops spill more there).
@@ -785,6 +804,8 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
     if (lane == 0 && blockIdx.x == 0 && a.traj) {   // diagnostic build: cycles per segment, per wave, into trajectory row 2
       double *d = a.traj + 18 * a.ld * 2 + role * 4;
       d[0] = (double)tD; d[1] = (double)tA; d[2] = (double)tB; d[3] = (double)tC;
+      a.traj[18 * a.ld * 2 + a.ld + role] = (double)tstage;   // (state row 1 of the same sample; once per launch, not per step)
+      a.traj[18 * a.ld * 2 + a.ld + 4 + role] = (double)tK;
     }
 #endif
     // ---- write the final state back (owners), flags

@@ -63,14 +63,17 @@ F16_DEV QuadBr quad_br_cells(const BrRaw &r, int nX, double vX) {
 // inside its cell (x0 <= v < x1 -- NaN, off-grid values and a value on the last node all fail it) the wave skips the
 // breakpoint reads, the fix-up and the broadcasts; br_axis then sees the same v, x0, x1 and lambda has the same bits.  The
 // cell is unique for an on-grid v < x1, so the full path could not have picked another one.  x0 = NaN: no cell yet.
+// `hit` tells the caller which path was taken (the same for the whole wave): on a hit the cell indices are last step's, so
+// every table address is last step's too, and the role keeps the values it read then (LongCorners / LatCorners below).
 struct QuadCell { int ja, jb, jd; double x0, x1; };
 F16_DEV QuadCell quad_cell_none() { QuadCell c; c.ja = c.jb = c.jd = 0; c.x0 = c.x1 = __builtin_nan(""); return c; }
 template <bool USE_D2, bool CACHE, typename TP>
-F16_DEV QuadBr quad_br_cached(TP T, double alpha, double beta, double el, int s, unsigned flags, QuadCell &cc) {
+F16_DEV QuadBr quad_br_cached(TP T, double alpha, double beta, double el, int s, unsigned flags, QuadCell &cc, bool &hit) {
   const double v = s == 0 ? alpha : (s == 1 ? beta : el);
   const bool in = cc.x0 <= v && v < cc.x1;
   QuadBr q;
-  if (CACHE && !(flags & FLAG_NO_CELL_CACHE) && __builtin_amdgcn_ballot_w64(!in) == 0) {   // wave-uniform branch
+  hit = CACHE && !(flags & FLAG_NO_CELL_CACHE) && __builtin_amdgcn_ballot_w64(!in) == 0;   // wave-uniform
+  if (hit) {
     q.c.j = 0; q.c.v = v; q.c.x0 = cc.x0; q.c.x1 = cc.x1;                          // (br_axis's j is not used by the quads)
     q.ja = cc.ja; q.jb = cc.jb; q.jd = cc.jd;
     q.offa = q.offb = q.offd = false;
@@ -88,6 +91,29 @@ F16_DEV void quad_br_axes(const QuadBr &q, Axis &a, Axis &b, Axis &d) {
   a.j = q.ja; a.l = quad_bcast<0>(own.l); a.m = quad_bcast<0>(own.m);
   b.j = q.jb; b.l = quad_bcast<1>(own.l); b.m = quad_bcast<1>(own.m);
   d.j = q.jd; d.l = quad_bcast<2>(own.l); d.m = quad_bcast<2>(own.m);
+}
+
+// Table values a role read at its last full lookup, carried across steps beside its QuadCell (CACHE only): while the wave
+// stays in its cells it neither forms the table addresses nor reads LDS -- phase (2) of quad_long / quad_lat runs on a
+// miss alone, phase (3) reads these.  Zero until the first lookup, which is always a miss (QuadCell starts with x0 = NaN).
+struct LongCorners {
+  Q4 qlo, qhi, q0, qlef;
+  double g0, g1, m0, m1, h0, h1, e0, e1, r0, r1, p0, p1, b0, b1, hr0, hr1, hp0, hp1, a45;
+};
+struct LatCorners {
+  Q4 qlo, qhi, q0, qy, qr, qa, ql, qal;
+  double a45;
+};
+
+// lerp() across the elevator axis of a 3-D table, both of whose operands are sums of products themselves: `l f2 + m f1` may be
+// contracted from either side, and with the corners held in registers the compiler picks the other one.  PIN states the
+// choice it made while they were loaded in front of the arithmetic (l f2 fused, m f1 rounded on its own), so that no bit moves.
+// Every other lerp / bil4w of phase (3) is still left to -ffp-contract=fast and can flip the same way under another compiler:
+// fixture G16 (tests/test_gpu_rollout_cell_cache.py, test_quad_rollout_matches_the_recorded_kernel_bit_for_bit) is the guard.
+template <bool PIN>
+F16_DEV double lerp_d(double f1, double f2, const Axis &a) {
+  if constexpr (PIN) return __builtin_fma(a.l, f2, a.m * f1);
+  else return lerp(f1, f2, a);
 }
 
 struct QuadIn {            // what both aerodynamic waves derive from the published state (C/nlplant.c:84-125)
@@ -124,7 +150,8 @@ __device__ unsigned long long g_qstamp[8];
 #define Q2STAMP(i)
 #endif
 template <bool CACHE, typename TP>
-F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned flags, QuadCell &cc, double &latd, int &status) {
+F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned flags, QuadCell &cc, LongCorners &kept, double &latd,
+                         int &status) {
 #ifdef F16_EXP_STAMPQ2
   unsigned long long tq_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -132,29 +159,34 @@ F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned fla
   Q2STAMP(0)
   const int k = s < 2 ? s : 2;
   // (1) breakpoints and cells: one axis per sub-lane (re-used from the last step while every lane stays in its cell)
-  const QuadBr qb = quad_br_cached<false, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc);
+  bool hit;
+  const QuadBr qb = quad_br_cached<false, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc, hit);
   Q2STAMP(1)
-  const double a45 = T[OFF_BP_A1 + N_A2 - 1];
+  LongCorners fresh;
+  LongCorners &c = CACHE ? kept : fresh;
+  const bool hi_a = qb.ja > N_A2 - 2;                            // ALPHA2 ends at 45 deg: last cell, lambda = 1
+  if (!CACHE || !hit) {
+    c.a45 = T[OFF_BP_A1 + N_A2 - 1];
+    const int j2 = hi_a ? N_A2 - 2 : qb.ja;
+    const int n1 = qb.jb * N_A1 + qb.ja, n2 = qb.jb * N_A2 + j2;
+    struct { int j; } ca = {qb.ja}, cd = {qb.jd};
+    // (2) every table corner this role needs
+    constexpr int SA = S_G3A, SB = S_G3A * N_A1, SD = S_G3A * N_A1 * N_B1;
+    TP p = T + OFF_G3A + n1 * SA + k;
+    c.qlo = ld4(p + cd.j * SD, SA, SB); c.qhi = ld4(p + (cd.j + 1) * SD, SA, SB); c.q0 = ld4(p + D1_ZERO_NODE * SD, SA, SB);
+    c.qlef = ld4(T + OFF_G2B + n2 * S_G2B + k, S_G2B, S_G2B * N_A2);
+    TP g = T + OFF_G1A + ca.j * S_G1A, h = T + OFF_G1B + j2 * S_G1B;
+    c.g0 = g[3 * k]; c.g1 = g[S_G1A + 3 * k]; c.m0 = g[11]; c.m1 = g[S_G1A + 11];
+    c.h0 = h[3 * k]; c.h1 = h[S_G1B + 3 * k];
+    c.e0 = T[OFF_ETA + cd.j]; c.e1 = T[OFF_ETA + cd.j + 1];
+    const int ir = k == 0 ? 1 : (k == 1 ? 7 : 4), ib = k == 1 ? 9 : 10;     // CYr CYp | CNr CNp | CLr CLp; dCNbeta, dCLbeta
+    c.r0 = g[ir]; c.r1 = g[S_G1A + ir]; c.p0 = g[ir + 1]; c.p1 = g[S_G1A + ir + 1]; c.b0 = g[ib]; c.b1 = g[S_G1A + ib];
+    c.hr0 = h[ir]; c.hr1 = h[S_G1B + ir]; c.hp0 = h[ir + 1]; c.hp1 = h[S_G1B + ir + 1];
+  }
   if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
   if (qb.offb) status |= ST_BETA;
   if (qb.offd) status |= ST_EL;
-  const bool hi_a = qb.ja > N_A2 - 2;                            // ALPHA2 ends at 45 deg: last cell, lambda = 1
-  if (hi_a && in.alpha > a45) status |= ST_ALPHA2;
-  const int j2 = hi_a ? N_A2 - 2 : qb.ja;
-  const int n1 = qb.jb * N_A1 + qb.ja, n2 = qb.jb * N_A2 + j2;
-  struct { int j; } ca = {qb.ja}, cd = {qb.jd};
-  // (2) every table corner this role needs
-  constexpr int SA = S_G3A, SB = S_G3A * N_A1, SD = S_G3A * N_A1 * N_B1;
-  TP p = T + OFF_G3A + n1 * SA + k;
-  const Q4 qlo = ld4(p + cd.j * SD, SA, SB), qhi = ld4(p + (cd.j + 1) * SD, SA, SB), q0 = ld4(p + D1_ZERO_NODE * SD, SA, SB);
-  const Q4 qlef = ld4(T + OFF_G2B + n2 * S_G2B + k, S_G2B, S_G2B * N_A2);
-  TP g = T + OFF_G1A + ca.j * S_G1A, h = T + OFF_G1B + j2 * S_G1B;
-  const double g0 = g[3 * k], g1 = g[S_G1A + 3 * k], m0 = g[11], m1 = g[S_G1A + 11];
-  const double h0 = h[3 * k], h1 = h[S_G1B + 3 * k];
-  const double e0 = T[OFF_ETA + cd.j], e1 = T[OFF_ETA + cd.j + 1];
-  const int ir = k == 0 ? 1 : (k == 1 ? 7 : 4), ib = k == 1 ? 9 : 10;     // CYr CYp | CNr CNp | CLr CLp; dCNbeta, dCLbeta
-  const double r0 = g[ir], r1 = g[S_G1A + ir], p0 = g[ir + 1], p1 = g[S_G1A + ir + 1], b0 = g[ib], b1 = g[S_G1A + ib];
-  const double hr0 = h[ir], hr1 = h[S_G1B + ir], hp0 = h[ir + 1], hp1 = h[S_G1B + ir + 1];
+  if (hi_a && in.alpha > c.a45) status |= ST_ALPHA2;
   Q2STAMP(2)
   F16_PHASE();
   // (3) arithmetic
@@ -163,18 +195,18 @@ F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned fla
   Axis a2 = a1;
   if (hi_a) { a2.j = N_A2 - 2; a2.l = 1.0; a2.m = 0.0; }
   const W4 W1 = bil_weights(a1, b), W2 = bil_weights(a2, b);
-  const double Cf = lerp(bil4w(qlo, a1, b, W1), bil4w(qhi, a1, b, W1), d1);
-  const double C0 = bil4w(q0, a1, b, W1);
-  const double dC = bil4w(qlef, a2, b, W2) - C0;                       // hifi_C_lef :1892-1899
-  const double Cq = lerp(g0, g1, a1), dCm = lerp(m0, m1, a1), dq = lerp(h0, h1, a2), eta = lerp(e0, e1, d1);
+  const double Cf = lerp_d<CACHE>(bil4w(c.qlo, a1, b, W1), bil4w(c.qhi, a1, b, W1), d1);
+  const double C0 = bil4w(c.q0, a1, b, W1);
+  const double dC = bil4w(c.qlef, a2, b, W2) - C0;                     // hifi_C_lef :1892-1899
+  const double Cq = lerp(c.g0, c.g1, a1), dCm = lerp(c.m0, c.m1, a1), dq = lerp(c.h0, c.h1, a2), eta = lerp(c.e0, c.e1, d1);
   const double dql = k == 1 ? dC : dq;                            // reference quirk: dZdQ uses delta_Cz_lef
   double tot = Cf * (k == 2 ? eta : 1.0) + dC * in.dlef + in.kq * (Cq + dql * in.dlef) * in.Q + (k == 2 ? dCm : 0.0);
   const double Cz_tot = quad_bcast<1>(tot);
   if (k == 2) tot += Cz_tot * (0.35 - xcg);                       // :347
-  double Cr = lerp(r0, r1, a1);
+  double Cr = lerp(c.r0, c.r1, a1);
   if (k == 2 && !(flags & FLAG_FIX_CLR)) Cr = 0.0;                // reference defect: _CLr is never loaded
-  const double Cp = lerp(p0, p1, a1), Cb = lerp(b0, b1, a1);
-  const double dCr = lerp(hr0, hr1, a2), dCp = lerp(hp0, hp1, a2);
+  const double Cp = lerp(c.p0, c.p1, a1), Cb = lerp(c.b0, c.b1, a1);
+  const double dCr = lerp(c.hr0, c.hr1, a2), dCp = lerp(c.hp0, c.hp1, a2);
   latd = in.kb * (Cr + dCr * in.dlef) * in.R + in.kb * (Cp + dCp * in.dlef) * in.P + (k == 0 ? 0.0 : Cb * in.beta);
   Q2STAMP(3)
   return tot;
@@ -184,30 +216,35 @@ F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned fla
 // hifi_C_lef, hifi_rudder, hifi_ailerons); the damping part comes from quad_long, the cg coupling of Cn (:367) is
 // applied by the consumer once both parts of Cy_tot are known.
 template <bool CACHE, typename TP>
-F16_DEV double quad_lat(TP T, const double *xu, int s, unsigned flags, QuadCell &cc, int &status) {
+F16_DEV double quad_lat(TP T, const double *xu, int s, unsigned flags, QuadCell &cc, LatCorners &kept, int &status) {
   const QuadIn in = quad_inputs(xu);
   const int k = s < 2 ? s : 2;
   // (1) breakpoints and cells: one axis per sub-lane (re-used from the last step while every lane stays in its cell)
-  const QuadBr qb = quad_br_cached<true, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc);
-  const double a45 = T[OFF_BP_A1 + N_A2 - 1];
+  bool hit;
+  const QuadBr qb = quad_br_cached<true, CACHE>(T, in.alpha, in.beta, in.el, s, flags, cc, hit);
+  LatCorners fresh;
+  LatCorners &c = CACHE ? kept : fresh;
+  const bool hi_a = qb.ja > N_A2 - 2;
+  if (!CACHE || !hit) {
+    c.a45 = T[OFF_BP_A1 + N_A2 - 1];
+    const int j2 = hi_a ? N_A2 - 2 : qb.ja;
+    const int n1 = qb.jb * N_A1 + qb.ja, n2 = qb.jb * N_A2 + j2;
+    struct { int j; } cd = {qb.jd};
+    // (2) every table corner this role needs
+    constexpr int SA3 = S_G3B, SB3 = S_G3B * N_A1, SD3 = S_G3B * N_A1 * N_B1;
+    TP p3 = T + OFF_G3B + n1 * SA3 + (k > 0 ? k - 1 : 0);          // sub-lane 0 shadows Cn; its base is Cy
+    c.qlo = ld4(p3 + cd.j * SD3, SA3, SB3); c.qhi = ld4(p3 + (cd.j + 1) * SD3, SA3, SB3); c.q0 = ld4(p3 + D2_ZERO_NODE * SD3, SA3, SB3);
+    constexpr int SA2 = S_G2A, SB2 = S_G2A * N_A1;
+    TP pa = T + OFF_G2A + n1 * SA2;
+    c.qy = ld4(pa, SA2, SB2); c.qr = ld4(pa + 1 + k, SA2, SB2); c.qa = ld4(pa + 4 + k, SA2, SB2);
+    constexpr int SAB = S_G2B, SBB = S_G2B * N_A2;
+    TP pb = T + OFF_G2B + n2 * SAB;
+    c.ql = ld4(pb + 3 + k, SAB, SBB); c.qal = ld4(pb + 6 + k, SAB, SBB);
+  }
   if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
   if (qb.offb) status |= ST_BETA;
   if (qb.offd) status |= ST_EL;
-  const bool hi_a = qb.ja > N_A2 - 2;
-  if (hi_a && in.alpha > a45) status |= ST_ALPHA2;
-  const int j2 = hi_a ? N_A2 - 2 : qb.ja;
-  const int n1 = qb.jb * N_A1 + qb.ja, n2 = qb.jb * N_A2 + j2;
-  struct { int j; } cd = {qb.jd};
-  // (2) every table corner this role needs
-  constexpr int SA3 = S_G3B, SB3 = S_G3B * N_A1, SD3 = S_G3B * N_A1 * N_B1;
-  TP p3 = T + OFF_G3B + n1 * SA3 + (k > 0 ? k - 1 : 0);          // sub-lane 0 shadows Cn; its base is Cy
-  const Q4 qlo = ld4(p3 + cd.j * SD3, SA3, SB3), qhi = ld4(p3 + (cd.j + 1) * SD3, SA3, SB3), q0 = ld4(p3 + D2_ZERO_NODE * SD3, SA3, SB3);
-  constexpr int SA2 = S_G2A, SB2 = S_G2A * N_A1;
-  TP pa = T + OFF_G2A + n1 * SA2;
-  const Q4 qy = ld4(pa, SA2, SB2), qr = ld4(pa + 1 + k, SA2, SB2), qa = ld4(pa + 4 + k, SA2, SB2);
-  constexpr int SAB = S_G2B, SBB = S_G2B * N_A2;
-  TP pb = T + OFF_G2B + n2 * SAB;
-  const Q4 ql = ld4(pb + 3 + k, SAB, SBB), qal = ld4(pb + 6 + k, SAB, SBB);
+  if (hi_a && in.alpha > c.a45) status |= ST_ALPHA2;
   F16_PHASE();
   // (3) arithmetic
   Axis a1, b, d2;
@@ -215,9 +252,9 @@ F16_DEV double quad_lat(TP T, const double *xu, int s, unsigned flags, QuadCell 
   Axis a2 = a1;
   if (hi_a) { a2.j = N_A2 - 2; a2.l = 1.0; a2.m = 0.0; }
   const W4 W1 = bil_weights(a1, b), W2 = bil_weights(a2, b);
-  const double C3 = lerp(bil4w(qlo, a1, b, W1), bil4w(qhi, a1, b, W1), d2), C30 = bil4w(q0, a1, b, W1);
-  const double Cy = bil4w(qy, a1, b, W1), Cr30 = bil4w(qr, a1, b, W1), Ca20 = bil4w(qa, a1, b, W1);
-  const double Clef = bil4w(ql, a2, b, W2), Ca20lef = bil4w(qal, a2, b, W2);
+  const double C3 = lerp_d<CACHE>(bil4w(c.qlo, a1, b, W1), bil4w(c.qhi, a1, b, W1), d2), C30 = bil4w(c.q0, a1, b, W1);
+  const double Cy = bil4w(c.qy, a1, b, W1), Cr30 = bil4w(c.qr, a1, b, W1), Ca20 = bil4w(c.qa, a1, b, W1);
+  const double Clef = bil4w(c.ql, a2, b, W2), Ca20lef = bil4w(c.qal, a2, b, W2);
   const double base = k == 0 ? Cy : C3, base0 = k == 0 ? Cy : C30;
   const double dlefC = Clef - base0;                             // hifi_C_lef
   const double dr30 = Cr30 - base0;                              // hifi_rudder

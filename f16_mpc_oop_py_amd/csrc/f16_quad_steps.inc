@@ -82,12 +82,12 @@
       if (wave == 0) {
         int sa_ = 0;
         double latd;
-        const double tot = quad_long<G1>((const double *)tab, xa, s, a.xcg, a.flags, qc, latd, sa_);
+        const double tot = quad_long<G1>((const double *)tab, xa, s, a.xcg, a.flags, qc, klong, latd, sa_);
         if (s < 3) { xt[s][ac] = tot; xt[8 + s][ac] = latd; }
         xst[0][ac] = sa_;
       } else if (wave == 1) {
         int sa_ = 0;
-        const double tot = quad_lat<G1>((const double *)tab, xa, s, a.flags, qc, sa_);
+        const double tot = quad_lat<G1>((const double *)tab, xa, s, a.flags, qc, klat, sa_);
         if (s < 3) xt[3 + s][ac] = tot;
         xst[1][ac] = sa_;
         {   // the rate-product terms of the moment equations (C/nlplant.c:413-436, Heng = 0) do not need the totals: first half
@@ -104,7 +104,12 @@
         // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
         const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
         double sn, cs, sb, s_psi, c_psi;
-        if constexpr (G1) F16_SINCOS_K(reloaded(QUAD_K.sc), ang, &sn, &cs); else F16_SINCOS(ang, &sn, &cs);
+        if constexpr (G1) {
+          QK_BEGIN
+          const auto ksc = reloaded(QUAD_K.sc);
+          QK_END
+          F16_SINCOS_K(ksc, ang, &sn, &cs);
+        } else F16_SINCOS(ang, &sn, &cs);
         // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
         //  changes x[1] in the last place)
         if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
@@ -159,7 +164,9 @@
         double mach, qbar, ps;
         double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
         if constexpr (G1) {
+          QK_BEGIN
           const PowK pk = reloaded(QUAD_K.pw);
+          QK_END
           atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(pk, 0.14 * log_k(pk, tfac)); });
         } else
           atmos_dev(xa[2], vt, mach, qbar, ps);
@@ -239,7 +246,10 @@
         }
       } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
         double sp, cp;
-        F16_SINCOS_K(reloaded(QUAD_K.sc), xpsi[0][ac], &sp, &cp);
+        QK_BEGIN
+        const auto ksc = reloaded(QUAD_K.sc);
+        QK_END
+        F16_SINCOS_K(ksc, xpsi[0][ac], &sp, &cp);
         xpsi[1][ac] = sp; xpsi[2][ac] = cp;
       }
     }

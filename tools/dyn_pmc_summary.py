@@ -46,7 +46,7 @@ try:
     rec = json.load(open(ip))
 except Exception:
     rec = {}
-for key, pat, meta in (("k_rollout_q", "k_rollout_q<1, false>", dict(batch=4096, euler_steps=1000)),
+for key, pat, meta in (("k_rollout_q", "k_rollout_q<1, false, false>", dict(batch=4096, euler_steps=1000)),
                        ("k_rollout_i", "k_rollout_i<512, false>", dict(batch=262144, euler_steps=200))):
     ks = [k for k in kern if pat in k and (k, "SQ_INSTS_VALU") in acc]
     if ks:
