@@ -6,6 +6,8 @@
 //   k_xdot_na   env.py:152-193                                         (f16_xdot_na_batch)
 //   k_rollout_exact       the same step x nsteps through the out-of-line euler_step_exact: one kernel for every batch size
 //                         (F16_FLAG_ONE_LANE; the step the closed MPC loop f16_rollout_mpc takes)
+//   k_rollout / k_rollout_i / k_rollout_exact <..., STAGES = 4>  the scheduled rollouts with the classical Runge-Kutta step instead of
+//                         the Euler step (f16_rollout_rk, f16_rollout_lqr_rk, f16_rollout_cost_rk with F16_INT_RK4)
 //   k_rollout_lqr_linear  test_env_mk2.py:46-62 / test_env.py:501-576: the linear-model LQR loops (f16_rollout_lqr_linear)
 //
 // Mapping: one lane = one aircraft; state-major [k][ld] arrays so a wave's 64 lanes read 512 contiguous
@@ -205,10 +207,16 @@ constexpr bool INC_TRIG = false;
 // COST (f16_rollout_cost; SCHED && !LQR only): the lane's cost J is accumulated in a register pair in step order; the nine x_ref
 // entries of the lane sit in lane-indexed LDS slots xr like the inputs (XRL), or -- where those do not fit beside the fp64 image,
 // the 512-lane workgroups -- are re-read from global memory (L2) at every step.
-template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false, bool COST = false, bool XRL = false>
+// STAGES (f16_rollout_rk / _lqr_rk / _cost_rk; SCHED only): 1 = the explicit Euler step of env.py:126, 4 = the classical Runge-Kutta
+// step (rk4_step, f16_plant.hpp) with the command -- under the LQR law the action formed from the state at the start of the step --
+// held over its four stages.  INCT is false then: every stage evaluates its sin / cos pairs exactly, so nothing but the state is
+// carried from step to step and a rollout of n + m steps equals one of n followed by one of m bit for bit.
+template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false, bool COST = false, bool XRL = false,
+          int STAGES = 1>
 __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
                                               double (*tgs)[BLOCK] = nullptr, double (*xr)[BLOCK] = nullptr) {
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
+  static_assert(STAGES == 1 || (STAGES == 4 && SCHED && !INCT), "the Runge-Kutta step: scheduled variants, exact sin / cos");
   for (long b = (long)blockIdx.x * BLOCK + threadIdx.x; b < a.B; b += (long)gridDim.x * BLOCK) {
     double x[18];
     long b0 = b;                                         // (COST) the aircraft of this lane: the column of x0 / x_ref / u_ref
@@ -268,6 +276,9 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
           for (int i = 0; i < 3; ++i)
             ul[i] = u[1 + i] = lqr_action(kq[3 * i][threadIdx.x], kq[3 * i + 1][threadIdx.x], kq[3 * i + 2][threadIdx.x], e0, e1, e2, u[1 + i]);
         }
+        if constexpr (STAGES == 4) {
+          rk4_step<FI>(T, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, st);
+        } else
         if (INCT) {
           const TrigSlots ts{&tgs[0][threadIdx.x], BLOCK};
           if (stale || ((ROW_TRIG ? t - t0 : t) & 31) == 0) { Trig5 g; trig_exact(x, g); trig_store(ts, g); }
@@ -330,9 +341,11 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
 // from global memory: no LDS staging) -- ONE instruction sequence for every batch size, the one the closed MPC loop (f16_rollout_mpc)
 // steps with.  Same rules as rollout_lanes (envelope freeze, status bits, trajectory samples, u_out); a reproducibility path, not a
 // fast one.
-template <bool LQR, bool SCHED = false, bool COST = false>
+// STAGES = 4: the Runge-Kutta step through the out-of-line rk4_step_exact instead.
+template <bool LQR, bool SCHED = false, bool COST = false, int STAGES = 1>
 __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a) {
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
+  static_assert(STAGES == 1 || (STAGES == 4 && SCHED), "the Runge-Kutta step: scheduled variants");
   for (long b = (long)blockIdx.x * 64 + threadIdx.x; b < a.B; b += (long)gridDim.x * 64) {
     double x[18], u[4];
     long b0 = b;                                         // (COST: as in rollout_lanes; the reference in registers)
@@ -376,6 +389,8 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a
 #pragma unroll
           for (int i = 0; i < 3; ++i) u[1 + i] = lqr_action(kq[3 * i], kq[3 * i + 1], kq[3 * i + 2], e0, e1, e2, u0[i]);
         }
+        if constexpr (STAGES == 4) rk4_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &st);
+        else
         euler_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &st);
         if constexpr (COST) J = cost_state_term(J + ju, x, a.w.q, ref);
       } else if constexpr (COST) {
@@ -416,20 +431,20 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a
   }
 }
 
-template <int BLOCK, int FI, bool LQR = false, bool SCHED = false, bool COST = false>
+template <int BLOCK, int FI, bool LQR = false, bool SCHED = false, bool COST = false, int STAGES = 1>
 __global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED, COST> a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   // the four inputs of a lane are constant over the rollout and used once per step: kept in lane-indexed (conflict-free) LDS
   // slots rather than in eight registers that the 512-lane instantiation (256 registers per lane) spilled and reloaded per step
   __shared__ double us[4][BLOCK];
   __shared__ double kq[LQR ? 12 : 1][LQR ? BLOCK : 1];
-  constexpr bool INCT = INC_TRIG && BLOCK <= 256 && !(LQR && BLOCK == 256);      // (the ten slots must fit beside the fp64 table image and, closed loop, the gain slots)
+  constexpr bool INCT = INC_TRIG && STAGES == 1 && BLOCK <= 256 && !(LQR && BLOCK == 256);      // (the ten slots must fit beside the fp64 table image and, closed loop, the gain slots)
   __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
   constexpr bool XRL = COST && BLOCK <= 256;           // (nine more slots of 512 lanes do not fit beside the fp64 image)
   __shared__ double xr[XRL ? 9 : 1][XRL ? BLOCK : 1];
   static_assert(sizeof(tab) + sizeof(us) + sizeof(kq) + sizeof(tgs) + sizeof(xr) <= 163840, "static LDS of a CU");
   if (a.fi == 1) stage_tables(tab, a.tab);
-  rollout_lanes<BLOCK, FI, const double *, LQR, INCT, SCHED, COST, XRL>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
+  rollout_lanes<BLOCK, FI, const double *, LQR, INCT, SCHED, COST, XRL, STAGES>(a, (const double *)tab, us, reinterpret_cast<double (*)[BLOCK]>(kq),
                                                                         reinterpret_cast<double (*)[BLOCK]>(tgs),
                                                                         reinterpret_cast<double (*)[BLOCK]>(xr));
 }
@@ -437,12 +452,12 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(RolloutArgs<SCHED, COST> a) {
 // The same rollout on the scaled-integer table image (hifi, default numerics; large batches: the LDS pipe -- 1.5 KB of
 // table vertices per aircraft-step as doubles, more than half of its cycles bank-conflict replays of the per-lane gathers --
 // is one of the two ceilings of k_rollout there).
-template <int BLOCK, bool LQR = false, bool SCHED = false, bool COST = false>
+template <int BLOCK, bool LQR = false, bool SCHED = false, bool COST = false, int STAGES = 1>
 __global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED, COST> a) {
   __shared__ __attribute__((aligned(16))) int tab[i32::IMAGE_INTS];
   __shared__ double us[4][BLOCK];
   __shared__ double kq[LQR ? 12 : 1][LQR ? BLOCK : 1];
-  constexpr bool INCT = INC_TRIG && !LQR;              // (closed loop: the gain slots take the room)
+  constexpr bool INCT = INC_TRIG && STAGES == 1 && !LQR;      // (closed loop: the gain slots take the room)
   __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
   __shared__ double xr[COST ? 9 : 1][COST ? BLOCK : 1];
   static_assert(sizeof(tab) + sizeof(us) + sizeof(kq) + sizeof(tgs) + sizeof(xr) <= 163840, "static LDS of a CU");
@@ -452,7 +467,7 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED, COST> a)
     for (int i = threadIdx.x; i < i32::IMAGE_INTS / 4; i += BLOCK) dst[i] = src[i];
     __syncthreads();
   }
-  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED, COST, COST>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq),
+  rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED, COST, COST, STAGES>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq),
                                                                 reinterpret_cast<double (*)[BLOCK]>(tgs), reinterpret_cast<double (*)[BLOCK]>(xr));
 }
 
@@ -1020,7 +1035,17 @@ extern "C" int f16_nlplant_batch(f16_ctx *ctx, const double *xu, double *xdot, i
 // never moves a batch to another kernel family.
 // COST = true: f16_rollout_cost takes the same rules without the quad and four-wave branches (those kernels split the state
 // over four role waves and have no scored twin), so a scored batch of B <= 16,384 hifi lanes runs the 64-lane one-lane kernel.
-template <bool LQR, bool SCHED, bool COST>
+// STAGES = 4 (f16_rollout_rk / _lqr_rk / _cost_rk with F16_INT_RK4): the same rules without the quad and four-wave branches, as for
+// COST (an RK4 twin of the role-wave kernels is out of scope), and with a 256-lane ceiling: the Runge-Kutta step keeps 54 doubles
+// more than the Euler step live across a plant evaluation, which the 256 registers per lane of a 512-lane workgroup do not hold
+// (profiles/rollout_rk4_resources.txt: the 512-lane instantiations, built with -DF16_RK4_512 for that table alone, have scratch
+// traffic inside the step loop), so from 131,072 aircraft on an RK4 rollout stays at one wave per SIMD.
+#ifdef F16_RK4_512
+constexpr bool RK4_512 = true;      // (resource table only: instantiate and route the 512-lane RK4 kernels)
+#else
+constexpr bool RK4_512 = false;
+#endif
+template <bool LQR, bool SCHED, bool COST, int STAGES = 1>
 static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *stream) {
   const hipStream_t st = (hipStream_t)stream;
   const long B = a.B;
@@ -1031,10 +1056,10 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *str
   if (a.flags & F16_FLAG_ONE_LANE) {
     // results independent of the batch size: ONE kernel for every B, its step an out-of-line function (k_rollout_exact)
     const long blocks = (B + 63) / 64;
-    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST, STAGES>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
     return hip_check(hipGetLastError(), what);
   }
-  if constexpr (!COST) {
+  if constexpr (!COST && STAGES == 1) {
     if (hifi && B <= 2 * maxq) {
       // four lanes per aircraft.  At most 16 aircraft per CU: one 16-aircraft workgroup per CU; at most 32: two 16-aircraft
       // groups per workgroup
@@ -1050,21 +1075,27 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *str
     }
   }
   Geometry g = geometry(B, a.fi);
+  constexpr bool WIDE = STAGES == 1 || RK4_512;      // 512-lane workgroups
+  if (!WIDE && g.block == 512) {                     // the RK4 ceiling: 256 lanes, the grid that goes with them
+    g.block = 256;
+    const long blocks = (B + 255) / 256;
+    g.grid = (int)(blocks < 256 ? blocks : 256);
+  }
 #ifdef F16_FAST_DIV
   // throughput regime, default numerics: lookups on the scaled-integer image
   static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
-  if (hifi && use_i32 && g.block == 512) {
+  if constexpr (WIDE) if (hifi && use_i32 && g.block == 512) {
     a.tab32 = ctx->d_tab32;
-    hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED, COST>), dim3(g.grid), dim3(512), 0, st, a);
+    hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(512), 0, st, a);
     return hip_check(hipGetLastError(), what);
   }
 #endif
   if (LQR && g.block == 512) g.block = 256;  // (fp64 image + 16 slots of 512 lanes would not fit the 160 KB of a CU)
   by_block(g, [&](auto block) {
     constexpr int BLOCK = decltype(block)::value;
-    if constexpr (!(LQR && BLOCK == 512)) {    // (never reached, and not instantiated)
-      if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED, COST>), dim3(g.grid), dim3(BLOCK), 0, st, a);
-      else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED, COST>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+    if constexpr (!((LQR || !WIDE) && BLOCK == 512)) {    // (never reached, and not instantiated)
+      if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+      else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
     }
   });
   return hip_check(hipGetLastError(), what);
@@ -1102,6 +1133,7 @@ struct PlantRollout {
   const double *x_ref = nullptr, *u_ref = nullptr;
   double *x_end = nullptr;
   const f16_cost_weights *w = nullptr;
+  int method = F16_INT_EULER;          // the step rule: F16_INT_EULER, or (SCHED entry points f16_rollout*_rk) F16_INT_RK4
 };
 
 template <bool LQR, bool SCHED, bool COST>
@@ -1117,6 +1149,8 @@ static int plant_rollout(f16_ctx *ctx, const PlantRollout &d, void *stream) {
     for (int k = 0; k < 22; ++k)
       if (!(w[k] >= 0.0) || !__builtin_isfinite(w[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
   }
+  if (d.method != F16_INT_EULER && !(SCHED && d.method == F16_INT_RK4))
+    return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
   // nothing to step; the scored call still launches for nsteps = 0: its cost is then the terminal term
   if (d.B == 0 || (!COST && d.nsteps == 0)) return F16_OK;
   auto a = base_args<RolloutArgs<SCHED, COST>>(ctx, d.B, d.ld, d.xcg, d.fi, d.flags, d.status);
@@ -1125,6 +1159,7 @@ static int plant_rollout(f16_ctx *ctx, const PlantRollout &d, void *stream) {
   a.K = d.K; a.dem = d.dem; a.u_out = d.u_out;
   if constexpr (SCHED) { a.seq = d.seq; a.hold = d.hold; a.nrows = d.nsteps > 0 ? (d.nsteps - 1) / d.hold + 1 : 0; }
   if constexpr (COST) { a.x0 = d.x; a.x_ref = d.x_ref; a.u_ref = d.u_ref; a.x_end = d.x_end; a.B0 = d.B0; a.ld0 = d.ld0; a.w = *d.w; }
+  if constexpr (SCHED) if (d.method == F16_INT_RK4) return rollout_dispatch<LQR, SCHED, COST, 4>(ctx, a, stream);
   return rollout_dispatch<LQR, SCHED, COST>(ctx, a, stream);
 }
 
@@ -1168,6 +1203,40 @@ extern "C" int f16_rollout_lqr_sched(f16_ctx *ctx, double *x, const double *u0, 
   PlantRollout d{"K / dem_seq is NULL", x, u0, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
   d.seq = dem_seq; d.hold = hold; d.K = K; d.dem = dem_seq; d.u_out = u_out;
   return plant_rollout<true, true, false>(ctx, d, stream);
+}
+
+// The same three scheduled rollouts with the step rule as an argument (include/f16_hip.h).  F16_INT_EULER forwards to the call above
+// it stands for, so it gives that call's bits on that call's kernel; F16_INT_RK4 takes the same checks in the same order.
+extern "C" int f16_rollout_rk(f16_ctx *ctx, double *x, const double *u_seq, double *traj, int32_t *status, long B, long ld,
+                              int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags,
+                              void *stream) {
+  if (method == F16_INT_EULER) return f16_rollout_sched(ctx, x, u_seq, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, flags, stream);
+  PlantRollout d{"u_seq is NULL", x, u_seq, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = u_seq; d.hold = hold; d.method = method;
+  return plant_rollout<false, true, false>(ctx, d, stream);
+}
+
+extern "C" int f16_rollout_lqr_rk(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, double *traj,
+                                  double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
+                                  double xcg, int fi_flag, int method, unsigned flags, void *stream) {
+  if (method == F16_INT_EULER)
+    return f16_rollout_lqr_sched(ctx, x, u0, K, dem_seq, traj, u_out, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, flags, stream);
+  PlantRollout d{"K / dem_seq is NULL", x, u0, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = dem_seq; d.hold = hold; d.K = K; d.dem = dem_seq; d.u_out = u_out; d.method = method;
+  return plant_rollout<true, true, false>(ctx, d, stream);
+}
+
+extern "C" int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long ld0, const double *u_seq, const double *x_ref,
+                                   const double *u_ref, const f16_cost_weights *h_w, double *cost, double *x_end, double *traj,
+                                   int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt, double xcg,
+                                   int fi_flag, int method, unsigned flags, void *stream) {
+  if (method == F16_INT_EULER)
+    return f16_rollout_cost(ctx, x0, B0, ld0, u_seq, x_ref, u_ref, h_w, cost, x_end, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg,
+                            fi_flag, flags, stream);
+  PlantRollout d{"u_seq / x_ref / h_w / cost is NULL", x0, u_seq, cost, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = u_seq; d.hold = hold; d.method = method;
+  d.B0 = B0; d.ld0 = ld0; d.x_ref = x_ref; d.u_ref = u_ref; d.x_end = x_end; d.w = h_w;
+  return plant_rollout<false, true, true>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr_linear(f16_ctx *ctx, double *x9, const double *Ad, const double *Bd, const double *K, const double *x_ref,

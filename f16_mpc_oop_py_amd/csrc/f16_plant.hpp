@@ -1108,6 +1108,54 @@ static __device__ __noinline__ void euler_step_exact(const double *tab, const do
   *stio |= st;
 }
 
+// ONE classical fourth-order Runge-Kutta step of ONE aircraft (include/f16_hip.h: F16_INT_RK4), f = calc_xdot with the command u held
+// over the four stages:
+//   k1 = f(x)   k2 = f(x + (dt/2) k1)   k3 = f(x + (dt/2) k2)   k4 = f(x + dt k3)      x <- x + (dt/6) ((k1 + 2 k2) + (2 k3 + k4))
+// The grid bits of all four evaluations are ORed into status; the stage states are not box-tested.  The four evaluations are ONE
+// copy of the plant in a loop that is not unrolled (a step is ~1,500 wave-instructions: four copies would not stay in the instruction
+// cache); the stage weights are selected by the uniform stage index, and x, the stage state and the two partial sums (72 doubles)
+// stay in registers across an evaluation.  The products by 2 are exact, so the sums round as written whether contracted or not.
+template <int FI = -1, typename TP>
+F16_DEV void rk4_step(TP T, const double *__restrict__ LT, double *x, const double *u, double dt, double xcg, int fi_flag,
+                      unsigned flags, int &status) {
+  const double h2 = 0.5 * dt, h6 = dt / 6.0;
+  double xs[18], s1[18], s2[18];
+#pragma unroll
+  for (int k = 0; k < 18; ++k) { xs[k] = x[k]; s1[k] = 0; s2[k] = 0; }
+#pragma unroll 1
+  for (int s = 0; s < 4; ++s) {
+    double xd[18];
+    calc_xdot<FI>(T, LT, xs, u, xd, xcg, fi_flag, flags, status);
+    const double c = s == 2 ? dt : h2;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+      if (s == 0) s1[k] = xd[k];
+      else if (s == 1) s1[k] += 2.0 * xd[k];
+      else if (s == 2) s2[k] = 2.0 * xd[k];
+      else s2[k] += xd[k];
+      xs[k] = x[k] + c * xd[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 18; ++k) x[k] += h6 * (s1[k] + s2[k]);
+}
+
+// The same step compiled OUT OF LINE, for the reason euler_step_exact is: the F16_FLAG_ONE_LANE rollouts (k_rollout_exact, open loop,
+// LQR law and scored alike) take an RK4 step through this one instruction sequence, so their results do not depend on the batch size.
+static __device__ __noinline__ void rk4_step_exact(const double *tab, const double *lofi, double *xio, const double *uin, double dt,
+                                                   double xcg, int fi, unsigned flags, int *stio) {
+  double x[18], u[4];
+#pragma unroll
+  for (int k = 0; k < 18; ++k) x[k] = xio[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) u[k] = uin[k];
+  int st = 0;
+  rk4_step<-1>(tab, lofi, x, u, dt, xcg, fi, flags, st);
+#pragma unroll
+  for (int k = 0; k < 18; ++k) xio[k] = x[k];
+  *stio |= st;
+}
+
 // env.py:152-193 _calc_xdot_na at ONE point (sv[18]: the full state with the three MPC inputs already in sv[13..15]) -> xdot9[9],
 // compiled out of line for the same reason as euler_step_exact: the per-step re-linearised LQR loop (f16_control.hip:
 // k_rollout_lqr_relin) evaluates every column of its forward differences through this one instruction sequence.  tab: the fp64

@@ -209,33 +209,41 @@ class F16Batch:
             self.status[done] = 0
         return self.get_obs(), reward, done, info
 
-    def rollout(self, nsteps, action=None, traj_every=None):
+    def rollout(self, nsteps, action=None, traj_every=None, method="euler"):
         """nsteps Euler steps in ONE launch with the state held in registers (the reference's
         `for ...: self.step(u)` loops, test_env.py:456-462).  traj_every=k stores the state after every k-th
-        step and returns it as [nsteps//k, 18, B] (state-major)."""
-        return self._rollout_call(self._u if action is None else self._soa(action, 4), nsteps, traj_every)
+        step and returns it as [nsteps//k, 18, B] (state-major).
+        method="rk4": classical fourth-order Runge-Kutta steps of self.dt instead (C-ABI f16_rollout_rk, the action held over the
+        four stages of a step) -- for a step coarser than the reference's 1 ms, where Euler is no longer accurate."""
+        return self._rollout_call(self._u if action is None else self._soa(action, 4), nsteps, traj_every, method=_lib.integrator(method))
 
-    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None):
+    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER):
         """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
         into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
-        around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values."""
+        around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values.  method F16_INT_RK4:
+        the _rk entry points, which are scheduled ones -- a constant input is one row held for every step."""
         traj = self._samples(nsteps, traj_every)
         # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
         name, law, u_out = ("f16_rollout", (), ()) if K is None else ("f16_rollout_lqr", (_vp(K), _vp(dem)), (_vp(self._u),))
-        name, held = (name, ()) if hold is None else (name + "_sched", (hold,))
+        rule = ()
+        if method != _lib.F16_INT_EULER:
+            name, held, rule = name + "_rk", (max(int(nsteps), 1) if hold is None else hold,), (int(method),)
+        else:
+            name, held = (name, ()) if hold is None else (name + "_sched", (hold,))
         self._check(getattr(self.lib, name)(self.ctx.handle, _vp(self._x), _vp(u), *law, _vp(traj), *u_out, _vp(self.status), self.B,
-                                            self.B, int(nsteps), *held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag,
+                                            self.B, int(nsteps), *held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag, *rule,
                                             self.flags, self._stream))
         return traj
 
-    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None):
+    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler"):
         """The reference's call pattern `u.values = action; step(u.values)` with an action that changes during the run
         (env.py:105-130; the doublets of Nguyen_m/runF16Sim.m) in ONE launch (C-ABI f16_rollout_sched): step t takes
         actions[t // hold], a zero-order hold.  actions: [S, B, 4] (numpy or torch), or a state-major [S, 4, B] fp64 tensor
         already on the device, which is taken as it is, without a copy (for B == 4 a 3-D device tensor is read as [S, B, 4];
         pass a host array or a non-contiguous view to say otherwise).  nsteps defaults to S * hold and needs
         S >= ceil(nsteps / hold) rows.  Returns what `rollout` returns; u.values ends up holding the last row used, as the
-        reference's caller leaves it."""
+        reference's caller leaves it.  method="rk4": Runge-Kutta steps, each row held over the stages of its steps (f16_rollout_rk)."""
+        method = _lib.integrator(method)
         t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
         if t.dim() != 3:
             raise ValueError(f"actions must be [S, B, 4] or a state-major [S, 4, B] device tensor, not {tuple(t.shape)}")
@@ -247,7 +255,7 @@ class F16Batch:
             raise ValueError(f"actions must be [S, {self.B}, 4] or a contiguous fp64 [S, 4, {self.B}] tensor on {self.device}, "
                              f"not {tuple(t.shape)} ({t.dtype}, {t.device})")
         hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
-        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold)
+        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold, method=method)
         self._u.copy_(seq[(nsteps - 1) // hold])
         return traj
 
@@ -261,18 +269,20 @@ class F16Batch:
         S, K = t.shape[0], t.shape[1]
         return t.to(device=self.device, dtype=torch.float64).permute(0, 3, 1, 2).reshape(S, width, K * self.B).contiguous(), K
 
-    def _score(self, seq, K, hold, nsteps, x_ref, u_ref, w, traj_every, want_final):
+    def _score(self, seq, K, hold, nsteps, x_ref, u_ref, w, traj_every, want_final, method=_lib.F16_INT_EULER):
         """f16_rollout_cost on seq [S, 4, K * B] from the resident state -> cost [K * B], status [K * B], x_end [18, K * B] or None,
-        traj [n, 18, K * B] or None.  x_ref [9, B], u_ref [3, B] or None (state-major, contiguous)."""
+        traj [n, 18, K * B] or None.  x_ref [9, B], u_ref [3, B] or None (state-major, contiguous).  method F16_INT_RK4:
+        f16_rollout_cost_rk."""
         lanes = K * self.B
         hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
         traj = self._samples(nsteps, traj_every, lanes=lanes)
         cost = torch.empty(lanes, dtype=torch.float64, device=self.device)
         st = torch.empty(lanes, dtype=torch.int32, device=self.device)
         x_end = torch.empty((18, lanes), dtype=torch.float64, device=self.device) if want_final else None
-        self._check(self.lib.f16_rollout_cost(self.ctx.handle, _vp(self._x), self.B, self.B, _vp(seq), _vp(x_ref), _vp(u_ref),
-                                              ctypes.byref(w), _vp(cost), _vp(x_end), _vp(traj), _vp(st), lanes, lanes, nsteps, hold,
-                                              int(traj_every or 1), self.dt, self.xcg, self.fi_flag, self.flags, self._stream))
+        call, rule = (self.lib.f16_rollout_cost, ()) if method == _lib.F16_INT_EULER else (self.lib.f16_rollout_cost_rk, (int(method),))
+        self._check(call(self.ctx.handle, _vp(self._x), self.B, self.B, _vp(seq), _vp(x_ref), _vp(u_ref),
+                         ctypes.byref(w), _vp(cost), _vp(x_end), _vp(traj), _vp(st), lanes, lanes, nsteps, hold,
+                         int(traj_every or 1), self.dt, self.xcg, self.fi_flag, *rule, self.flags, self._stream))
         return cost, st, x_end, traj
 
     def _blend(self, cost, seq, K, lam):
@@ -289,7 +299,7 @@ class F16Batch:
         return out, wts, stats
 
     def score_schedules(self, actions, hold=1, nsteps=None, x_ref=None, u_ref=None, q=None, qf=None, r=None, penalty=0.0,
-                        traj_every=None, return_final=False):
+                        traj_every=None, return_final=False, method="euler"):
         """K sampled command schedules per aircraft through the nonlinear plant, each scored, in ONE launch (C-ABI
         f16_rollout_cost): actions [S, K, B, 4] (numpy or torch, host or device), step t of sample k takes actions[t // hold, k] as
         rollout_schedule does; every sample starts from the current x.values.  The cost of a sample is
@@ -300,12 +310,14 @@ class F16Batch:
         defaults to S * hold.  Returns cost [K, B]; with return_final also the final states [18, K, B]; with traj_every = k also the
         samples [nsteps // k, 18, K, B] -- (cost, final), (cost, traj) or (cost, final, traj).  x.values, u.values and status are
         not touched; the status words of the samples [K, B] (an output: every sample starts from 0) are kept in
-        `last_score_status`."""
+        `last_score_status`.  method="rk4": the samples are integrated with Runge-Kutta steps of self.dt (f16_rollout_cost_rk); the
+        cost formula is the same, on the states after each whole step."""
+        method = _lib.integrator(method)
         seq, K = self._sample_lanes(actions)
         xr = self._x[P.mpc_x_idx].contiguous() if x_ref is None else self._soa(x_ref, 9)
         ur = None if u_ref is None else self._soa(u_ref, 3)
         w = _lib.make_cost_weights(q, qf, r, penalty)
-        cost, st, x_end, traj = self._score(seq, K, hold, nsteps, xr, ur, w, traj_every, return_final)
+        cost, st, x_end, traj = self._score(seq, K, hold, nsteps, xr, ur, w, traj_every, return_final, method)
         self.last_score_status = st.view(K, self.B)
         out = (cost.view(K, self.B),)
         if return_final:
@@ -328,7 +340,7 @@ class F16Batch:
         u = out.permute(0, 2, 1)
         return (u, dict(weights=wts.view(K, self.B), min_cost=stats[0], ess=stats[1])) if return_info else u
 
-    def calc_MPPI_action(self, p_dem, q_dem, r_dem, nominal, noise, hold=1, lam=1.0, **weights):
+    def calc_MPPI_action(self, p_dem, q_dem, r_dem, nominal, noise, hold=1, lam=1.0, method="euler", **weights):
         """One step of sampling-based nonlinear MPC (MPPI, model-predictive path integral control) on the plant itself -- for the
         states from which the linear MPC's QP has no feasible point: K command sequences per aircraft, nominal
         [S, B, 4] plus noise [S, K, B, 3] on the three surface commands (the caller's, e.g. sigma * torch.randn(..., generator=g)),
@@ -336,7 +348,9 @@ class F16Batch:
         steps, scored against x_ref = the current x9 with x_ref[4:7] = (p, q, r)_dem (the convention of _calc_LQR_action,
         env.py:365-367) and blended by softmin weights of temperature lam: one score_schedules plus one blend_schedules.  weights:
         q, qf, r, penalty, u_ref as score_schedules takes them.  Returns (the blended schedule [S, B, 4], dict(cost [K, B],
-        min_cost [B], ess [B], status [K, B])); nothing resident is touched."""
+        min_cost [B], ess [B], status [K, B])); nothing resident is touched.  method="rk4": the samples are scored with
+        Runge-Kutta steps (score_schedules' keyword)."""
+        method = _lib.integrator(method)
         nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal, dtype=np.float64))
         eps = noise if isinstance(noise, torch.Tensor) else torch.as_tensor(np.asarray(noise, dtype=np.float64))
         if nom.dim() != 3 or tuple(nom.shape[1:]) != (self.B, 4):
@@ -360,19 +374,20 @@ class F16Batch:
         xr[4:7] = self._demands(p_dem, q_dem, r_dem)
         ur = None if weights.get("u_ref") is None else self._soa(weights["u_ref"], 3)
         w = _lib.make_cost_weights(weights.get("q"), weights.get("qf"), weights.get("r"), weights.get("penalty", 0.0))
-        cost, st, _, _ = self._score(seq, K, hold, None, xr, ur, w, None, False)
+        cost, st, _, _ = self._score(seq, K, hold, None, xr, ur, w, None, False, method)
         out, _, stats = self._blend(cost, seq, K, lam)
         return out.permute(0, 2, 1), dict(cost=cost.view(K, self.B), min_cost=stats[0], ess=stats[1], status=st.view(K, self.B))
 
     def rollout_MPPI(self, nsteps, p_dem, q_dem, r_dem, horizon, hold, samples, sigma, lam, seed=0, traj_every=None,
-                     return_info=False, **weights):
+                     return_info=False, method="euler", **weights):
         """The closed MPPI loop as a host loop (fusing it into one launch is future work).  Per control period of `hold` plant steps:
         noise = sigma * randn([horizon, samples, B, 3]) from a device torch.Generator seeded once with `seed`; calc_MPPI_action on
         the nominal schedule [horizon, B, 4] (at first the current u.values in every row); u.values = row 0 of the blend and
         `rollout(hold)`; the nominal becomes the blend shifted one row, its last row repeated.  nsteps must be a multiple of hold,
         hold of traj_every.  sigma: a scalar or the three surface deviations (deg).  x.values, u.values and status advance as under
         `rollout`.  Returns the samples [nsteps // traj_every, 18, B] (None without traj_every); with return_info also
-        dict(min_cost [periods, B], ess [periods, B])."""
+        dict(min_cost [periods, B], ess [periods, B]).  method="rk4": Runge-Kutta steps both in the scoring and in the plant advance."""
+        _lib.integrator(method)
         nsteps, horizon, hold, samples = int(nsteps), int(horizon), int(hold), int(samples)
         if hold < 1 or horizon < 1 or samples < 1:
             raise ValueError("horizon, hold and samples must be >= 1")
@@ -391,9 +406,9 @@ class F16Batch:
         trajs, mins, ess = [], [], []
         for _ in range(nsteps // hold):
             noise = sig * torch.randn((horizon, samples, self.B, 3), generator=g, device=self.device, dtype=torch.float64)
-            u, info = self.calc_MPPI_action(p_dem, q_dem, r_dem, nominal, noise, hold=hold, lam=lam, **weights)
+            u, info = self.calc_MPPI_action(p_dem, q_dem, r_dem, nominal, noise, hold=hold, lam=lam, method=method, **weights)
             self.set_input(u[0])
-            trajs.append(self.rollout(hold, traj_every=traj_every))
+            trajs.append(self.rollout(hold, traj_every=traj_every, method=method))
             nominal = torch.cat((u[1:], u[-1:]), 0)
             mins.append(info["min_cost"])
             ess.append(info["ess"])
@@ -588,7 +603,7 @@ class F16Batch:
         return seq.contiguous(), k
 
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
-                    R=None, hold=None):
+                    R=None, hold=None, method="euler"):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -604,7 +619,11 @@ class F16Batch:
         Demand histories: when any of p_dem, q_dem, r_dem is [S] or [S, B] (the pilot loop of flight_sim.py:141-182, whose demands
         change from frame to frame under one gain) the loop runs as one launch of f16_rollout_lqr_sched: step t takes row
         t // hold (hold defaults to 1; scalars are broadcast; S >= ceil(nsteps / hold)).  Not combined with linear=True or
-        relinearise=True (ValueError).  Scalar / [B] demands call f16_rollout_lqr exactly as before; hold is then not taken."""
+        relinearise=True (ValueError).  Scalar / [B] demands call f16_rollout_lqr exactly as before; hold is then not taken.
+        method="rk4" (the frozen-gain nonlinear loop only; ValueError with linear=True or relinearise=True, whose kernels step with
+        the Euler step): Runge-Kutta steps, the action formed from the state at the start of a step and held over its four stages
+        (f16_rollout_lqr_rk; constant demands are one row held for every step)."""
+        method = _lib.integrator(method, rk4=not (linear or relinearise))
         dem_seq = self._demand_schedule(p_dem, q_dem, r_dem)
         if dem_seq is not None:
             if linear or relinearise:
@@ -641,7 +660,7 @@ class F16Batch:
             u0s = torch.cat((self._u[0:1], self._u_init[1:4]), 0).contiguous()
         else:
             u0s = self._soa(u0, 4)
-        return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq)
+        return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq, method=method)
 
     def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
                           hold=None):
@@ -851,7 +870,7 @@ class F16Batch:
     calc_MPC_action = _calc_MPC_action
 
     def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False,
-                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None, dem_every=None):
+                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None, dem_every=None, method="euler"):
         """The reference's closed MPC loop (test_env.py:480-495; BASELINE config 5) as ONE launch (C-ABI f16_rollout_mpc): per step
         `cmd = _calc_MPC_action(p_dem, q_dem, r_dem, hzn); u.values[1:] = cmd; step(u.values)` from the frozen reduced model
         (env.py:49-60) with OSQP's default settings (every solve cold, as the reference's -- or warm from the step before when the plan was
@@ -878,7 +897,8 @@ class F16Batch:
         c // dem_every (default 1; S >= ceil(control steps / dem_every)), with relinearise and ctrl_every alike.  The demand of a control
         step is held over that step's whole horizon, so the call equals one call per row.  A 2-D p_dem with q_dem is None and
         r_dem is None stays a ready [3, B] block of constant demands.  dem_every without a history, too few rows and
-        dem_every < 1 raise ValueError."""
+        dem_every < 1 raise ValueError.  method: "euler" only -- the loop's plant step is the Euler step; "rk4" raises ValueError."""
+        _lib.integrator(method, rk4=False)
         nsteps, hold = int(nsteps), int(ctrl_every)
         if hold < 1 or nsteps % hold:      # (argument checks first: they need no GPU)
             raise ValueError(f"nsteps ({nsteps}) must be a multiple of ctrl_every ({hold}) >= 1")

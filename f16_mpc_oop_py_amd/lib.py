@@ -34,6 +34,18 @@ F16_FLAG_NO_ENVELOPE = 2
 F16_FLAG_ONE_LANE = 4          # rollouts: the one-lane-per-aircraft kernel whatever the batch size (results independent of B)
 F16_FLAG_HOLD_COMMAND = 8      # closed MPC loops: a step without a command (infeasible QP, state not finite) keeps the previous one
 F16_FLAG_NO_CELL_CACHE = 16    # diagnostic: quad rollout re-brackets every step (no cell re-use); results bit-identical either way
+F16_INT_EULER, F16_INT_RK4 = 1, 4      # the step rule of f16_rollout_rk / f16_rollout_lqr_rk / f16_rollout_cost_rk
+INTEGRATORS = {"euler": F16_INT_EULER, "rk4": F16_INT_RK4}
+
+
+def integrator(method, rk4=True):
+    """The `method` keyword of the rollouts ("euler" | "rk4") -> F16_INT_*; ValueError for anything else, and for "rk4" where the
+    loop behind the call steps with the Euler step only (rk4=False)."""
+    if not isinstance(method, str) or method not in INTEGRATORS:
+        raise ValueError(f'method must be "euler" or "rk4", not {method!r}')
+    if method == "rk4" and not rk4:
+        raise ValueError('method="rk4" is not available here: this loop steps with the explicit Euler step')
+    return INTEGRATORS[method]
 
 
 class F16HipError(RuntimeError):
@@ -244,6 +256,10 @@ def load():
         L.f16_rollout_lqr_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
     if hasattr(L, "f16_rollout_cost"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
         L.f16_rollout_cost.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
+    if hasattr(L, "f16_rollout_rk"):         # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        L.f16_rollout_rk.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
+        L.f16_rollout_lqr_rk.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
+        L.f16_rollout_cost_rk.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
     if hasattr(L, "f16_mppi_blend"):         # (not part of the strict build, which holds the plant sources alone)
         L.f16_mppi_blend.argtypes = [vp, vp, vp, d, vp, vp, vp, l, l, l, l, i, vp]
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]

@@ -212,6 +212,48 @@ int f16_rollout_cost(f16_ctx *ctx, const double *x0, long B0, long ld0, const do
                      double *cost, double *x_end, double *traj, int32_t *status,
                      long B, long ld, int nsteps, int hold, int traj_every,
                      double dt, double xcg, int fi_flag, unsigned flags, void *stream);
+/* The three scheduled rollouts above with the STEP RULE as an argument: explicit Euler (the reference's step, env.py:126) or the
+ * classical fourth-order Runge-Kutta step, still ONE launch.  Euler at the reference's dt = 1 ms reproduces the reference; at 10 ms it
+ * is outside the tolerance of the reference's Simulink time histories (fixture G10), where RK4 at 10 ms is inside it with 0.4 x the
+ * plant evaluations per simulated second.
+ *   method = F16_INT_EULER  forwards to f16_rollout_sched / f16_rollout_lqr_sched / f16_rollout_cost: that call's kernel, its bits.
+ *   method = F16_INT_RK4    with f = env.py:65-103 `_calc_xdot` (all 18 states, the actuator and leading-edge-flap models inside)
+ *     and u the command of the step -- under the LQR law the action of env.py:360-371 formed from the state at the START of the step
+ *     -- held over the four stages:
+ *         if the box test of env.py:117-124 fails on x: the aircraft is frozen (F16_ST_ENVELOPE), x untouched; else
+ *         k1 = f(x, u)   k2 = f(x + (dt/2) k1, u)   k3 = f(x + (dt/2) k2, u)   k4 = f(x + dt k3, u)
+ *         x <- x + (dt/6) ((k1 + 2 k2) + (2 k3 + k4))
+ *     The grid bits (F16_ST_ALPHA1 .. F16_ST_EL) of all four evaluations are ORed into the sticky status word; the stage states are
+ *     not box-tested; NaN and infinite commands or states propagate by ordinary arithmetic; F16_ST_NONFINITE and F16_ST_ENV_STATE
+ *     are formed at write-back; trajectory samples, u_out and the scored cost (f16_rollout_cost's formula, unchanged) use the state
+ *     after the whole step.
+ *   Any other method: F16_EINVAL ("method must be ...").
+ * Arguments, layouts, the zero-order hold, the no-op rules and the F16_EINVAL rules are those of the call each stands for, checked
+ * in the same order, the method last.  A constant input is one row with hold >= nsteps.
+ * Contracts (RK4).  Nothing but the state is carried from step to step (every stage evaluates its sin / cos pairs exactly), so a
+ * rollout of n steps followed by one of m steps equals one of n + m steps BIT FOR BIT, and a schedule equals the chain of one call
+ * per segment bit for bit, for EVERY batch size and EVERY hold -- a stronger statement than the Euler kernels make.  Under
+ * F16_FLAG_ONE_LANE every variant steps through one out-of-line function, so an aircraft's result does not depend on the batch
+ * size.  f16_rollout_cost_rk's x_end / traj / status equal f16_rollout_rk's on the K-fold replicated states bit for bit at every
+ * size (both run the same kernel family); cost has the same bits with and without x_end / traj.
+ * Launch rules (RK4): the one-lane-per-aircraft kernels at every size, 64 / 128 / 256 lanes per workgroup -- never the
+ * four-lanes-per-aircraft and four-wavefront kernels, and never 512-lane workgroups (the step's registers do not fit there).
+ * OUT OF SCOPE: an RK4 twin of those role-wave kernels.  For hifi batches of at most 16,384 aircraft the Euler call at dt = 1 ms on
+ * them remains the fastest way to fly a second of simulated time; RK4 pays where the one-lane kernels run anyway (scored rollouts,
+ * batches above 16,384) and wherever a coarser step is wanted.  The closed MPC loops and the per-step re-linearised LQR loop keep
+ * the Euler step.  Nothing is allocated: the calls can be captured into a graph. */
+#define F16_INT_EULER 1
+#define F16_INT_RK4 4
+int f16_rollout_rk(f16_ctx *ctx, double *x, const double *u_seq, double *traj, int32_t *status, long B, long ld, int nsteps,
+                   int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
+int f16_rollout_lqr_rk(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, double *traj,
+                       double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
+                       double xcg, int fi_flag, int method, unsigned flags, void *stream);
+int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long ld0, const double *u_seq,
+                        const double *x_ref, const double *u_ref, const f16_cost_weights *h_w,
+                        double *cost, double *x_end, double *traj, int32_t *status,
+                        long B, long ld, int nsteps, int hold, int traj_every,
+                        double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
 /* The softmin blend of an MPPI step over the costs f16_rollout_cost wrote.  For aircraft a and its samples k = 0..K-1 (K = B / B0) at
  * lanes k * B0 + a:  m = the minimum over the FINITE cost,  w_k = exp(-(J_k - m) / lambda) for finite J_k and 0 otherwise,
  *     u_blend[nrows][4][ld0] = sum_k w_k u_seq[row][c][k * B0 + a] / sum_k w_k        (all four commands; u_seq[nrows][4][ld])

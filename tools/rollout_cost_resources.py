@@ -41,10 +41,11 @@ def main():
         if not m:
             continue
         args = [a.strip() for a in m.group(2).split(",")]
-        # k_rollout<BLOCK, FI, LQR, SCHED, COST>, k_rollout_i<BLOCK, LQR, SCHED, COST>, k_rollout_exact<LQR, SCHED, COST>
-        lqr, sched, cost = args[-3:]
-        if lqr == "false" and sched == "true":
-            rows.append((m.group(1), ", ".join(args[:-3]), "scored" if cost == "true" else "scheduled", k))
+        # k_rollout<BLOCK, FI, LQR, SCHED, COST, STAGES>, k_rollout_i<BLOCK, LQR, SCHED, COST, STAGES>, k_rollout_exact<LQR, SCHED, COST, STAGES>
+        # (STAGES 1: the Euler step; the Runge-Kutta twins have a table of their own, tools/rollout_rk4_resources.py)
+        lqr, sched, cost, stages = args[-4:]
+        if lqr == "false" and sched == "true" and stages == "1":
+            rows.append((m.group(1), ", ".join(args[:-4]), "scored" if cost == "true" else "scheduled", k))
     rows.sort(key=lambda r: (r[0], [int(v) for v in r[1].split(",") if v.strip()], r[2]))
     out = os.path.join(REPO, "profiles", "rollout_cost_resources.txt")
     with open(out, "w") as f:
