@@ -939,34 +939,41 @@ static int mpc_lds_opt_in() {
   return F16_OK;
 }
 
-// Per-call QP workspace, stream-ordered (see f16_ctx.h): [B][np] P | [B][ext] extras | [B][tiles] A'WA of the fast solver.
-static int mpc_work_alloc(f16_ctx *ctx, MpcArgs &a, bool with_ext, void *stream, void **block, bool with_gram = false,
-                          bool with_pblk = false) {
-  const size_t np = (size_t)(3 * a.N) * (3 * a.N + 1) / 2;
-  const bool big = a.N > FAST_MAXN;                    // long horizons: operands in HBM (the workgroup solver; beyond MAXN also the one-wave slow path)
-  const size_t bigd = big ? (mpc_big_ws_doubles(a.N) > mpc_big_doubles(a.N) ? mpc_big_ws_doubles(a.N) : mpc_big_doubles(a.N)) : 0;
-  const size_t need = (np + (with_ext ? mpc_ext_doubles(a.N) : 0) + (with_gram ? MPC_TILE_DOUBLES : 0) + bigd +
-                       (with_pblk ? WAVE_PBLK_DOUBLES : 0)) * (size_t)a.B * sizeof(double);
-  *block = nullptr;
-  // Not under stream capture.  What round 3 established (profiles/r03_capture_pool.log, r03_capture_probe.log): on ROCm 7.2 a
-  // plain-HIP graph with mem-alloc / mem-free nodes (tools/micro/capture_pool.hip, none of this library's kernels) replays
-  // WRONGLY beside eager allocations from the same pool (302,520 wrong elements at replay 11 of 12); the mechanism is not
-  // established -- the logged eager blocks never overlap the graph's block.  tools/gpu_capture_probe.py replays the one-shot call
-  // with no host state in the capture (F16_MPC_DISPATCH_ORDER=0): every replay is bit-identical to the eager call EXCEPT the
-  // ones with an eager call of the same context enqueued behind them (NaN in 20-200 of 256 aircraft), with either solver.
-  // The fault is the runtime's, not in what the capture bakes in; the refusal stays.  A prepared plan owns its workspace for
-  // its lifetime and IS capturable (f16_mpc_plan_solve; tests).
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  static const bool allow_capture = [] { const char *e = getenv("F16_MPC_ALLOW_CAPTURE"); return e && e[0] == '1'; }();   // (diagnosis only: tools/gpu_capture_probe.py)
-  if (!allow_capture && stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return set_error(F16_EINVAL, "one-shot MPC calls cannot be captured into a HIP graph (per-call workspace): use f16_mpc_plan_solve");
-  if (int rc = hip_check(hipMallocFromPoolAsync(block, need, ctx->pool, (hipStream_t)stream), "hipMallocFromPoolAsync QP workspace")) return rc;
-  a.Ppk = (double *)*block;
-  a.ext = with_ext ? a.Ppk + np * (size_t)a.B : nullptr;
-  a.gramws = with_gram ? a.Ppk + (np + mpc_ext_doubles(a.N)) * (size_t)a.B : nullptr;
-  a.bigws = big ? a.Ppk + (np + (with_ext ? mpc_ext_doubles(a.N) : 0) + (with_gram ? MPC_TILE_DOUBLES : 0)) * (size_t)a.B : nullptr;
-  a.pblk = with_pblk ? a.Ppk + (np + (with_ext ? mpc_ext_doubles(a.N) : 0) + (with_gram ? MPC_TILE_DOUBLES : 0) + bigd) * (size_t)a.B : nullptr;
+// The QP settings of every MPC solve, checked in one place.  need_iterations: prepared plans (max_iter >= 1); the one-shot call and
+// the sweep take any max_iter (negative: the generic kernel for |max_iter| iterations; 0: no iteration at all).
+static int mpc_check_settings(const f16_qp_settings &s, bool need_iterations, const char *entry) {
+  if (s.check_every < 1 || s.rho_every < 1) return einval("%s: check_every and rho_every must be >= 1", entry);
+  if (!(s.rho >= 0) || !(s.sigma > 0)) return einval("%s: rho must be >= 0 and sigma > 0", entry);
+  if (s.scaling < 0 || s.scaling > 100) return einval("%s: scaling must be 0..100", entry);
+  if (s.scaling > 0 && !(s.rho > 0)) return einval("%s: the automatic start value of rho (rho = 0) needs scaling = 0", entry);
+  // the rho estimate is formed from the residuals of a termination test, so it can only run on an iteration that has one
+  // (osqp.c adapts independently of check_termination; here an interval that is not a multiple would silently become the
+  // least common multiple)
+  if (s.adaptive_rho && s.rho_every % s.check_every != 0) return einval("%s: with adaptive_rho, rho_every must be a multiple of check_every", entry);
+  if (need_iterations && s.max_iter < 1) return einval("%s: max_iter must be >= 1", entry);
   return F16_OK;
+}
+
+static bool stream_capturing(void *stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// Per-call workspace of `entry`, stream-ordered (see f16_ctx.h) -- and therefore refused under stream capture, here and nowhere
+// else.  What round 3 established (profiles/r03_capture_pool.log, r03_capture_probe.log): on ROCm 7.2 a plain-HIP graph with mem-alloc / mem-free nodes (tools/micro/capture_pool.hip, none of this library's kernels) replays
+// WRONGLY beside eager allocations from the same pool (302,520 wrong elements at replay 11 of 12); the mechanism is not
+// established -- the logged eager blocks never overlap the graph's block.  tools/gpu_capture_probe.py replays the one-shot call
+// with no host state in the capture (F16_MPC_DISPATCH_ORDER=0): every replay is bit-identical to the eager call EXCEPT the
+// ones with an eager call of the same context enqueued behind them (NaN in 20-200 of 256 aircraft), with either solver.
+// The fault is the runtime's, not in what the capture bakes in; the refusal stays.  A prepared plan owns its workspace for
+// its lifetime and IS capturable (f16_mpc_plan_solve; tests).  escape: F16_MPC_ALLOW_CAPTURE=1 lifts the refusal (the one-shot
+// call only; diagnosis only: tools/gpu_capture_probe.py).
+static int mpc_work_alloc(f16_ctx *ctx, size_t bytes, void *stream, const char *entry, bool escape, void **block) {
+  static const bool allow_capture = [] { const char *e = getenv("F16_MPC_ALLOW_CAPTURE"); return e && e[0] == '1'; }();
+  *block = nullptr;
+  if (!(escape && allow_capture) && stream_capturing(stream))
+    return einval("%s cannot be captured into a HIP graph (per-call workspace; a prepared plan owns its own: f16_mpc_plan_solve)", entry);
+  return hip_check(hipMallocFromPoolAsync(block, bytes, ctx->pool, (hipStream_t)stream), "hipMallocFromPoolAsync QP workspace");
 }
 static int mpc_work_free(void *block, void *stream) {
   return block ? hip_check(hipFreeAsync(block, (hipStream_t)stream), "hipFreeAsync QP workspace") : F16_OK;
@@ -978,8 +985,7 @@ static f16_ctx::sched_entry *mpc_sched_entry(f16_ctx *ctx, void *stream, long B,
   std::lock_guard<std::mutex> lk(mu);
   for (int i = 0; i < ctx->n_sched; ++i)
     if (ctx->sched[i].stream == stream && ctx->sched[i].B == B && ctx->sched[i].tag == tag) return &ctx->sched[i];
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return nullptr;
+  if (stream_capturing(stream)) return nullptr;
   int32_t *buf = nullptr;
   if (hipMalloc(&buf, 2 * (size_t)B * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   int slot = ctx->n_sched;
@@ -1015,58 +1021,60 @@ static int mpc_solve_dispatch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
   return mpc_fast_solve_launch(ctx, a, stream);
 }
 
+// The one launch of k_mpc: the QP build alone (setup_only; a solver follows), or build + generic ADMM, one wavefront per aircraft.
+// Needs mpc_lds_opt_in() once per device before it -- by the caller, for a plan at its creation: a solve may be under capture.
+static int mpc_build_launch(const MpcArgs &a, bool setup_only, void *stream, const char *what) {
+  const bool big = a.N > MAXN;
+  const size_t lds = mpc_lds_doubles(a.N, setup_only, big) * sizeof(double);
+  if (lds > 160 * 1024) return set_error(F16_EINVAL, "horizon too large for LDS");
+  void (*const k)(MpcArgs) = setup_only ? (big ? k_mpc<true, true> : k_mpc<true, false>) : (big ? k_mpc<false, true> : k_mpc<false, false>);
+  hipLaunchKernelGGL(k, dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
+  return hip_check(hipGetLastError(), what);
+}
+
+// The solve behind a build, in dispatch order (see k_plan_order): the reference's closed loops call calc_MPC_action once per step on
+// states that move little, so the iteration counts of the previous solve of the same batch predict this one's; any order is valid, a
+// stale one only loses the gain.  hist: [2][B] the iteration counts of this solve (written here) | the order made of them for the next
+// one; null: the caller's order, nothing recorded.  ordered: hist holds the order of a previous solve.  Without one, and with
+// first_order (the solvers up to FAST_MAXN), a batch beyond 1024 is ordered by the QPs themselves (mpc_first_order_launch: by ||q||_inf).
+static int mpc_ordered_solve(f16_ctx *ctx, MpcArgs a, int32_t *hist, bool ordered, bool first_order, void *stream) {
+  const bool big = a.N > FAST_MAXN;          // the workgroup solver with its operands in HBM: it starts cold
+  a.iters_out = hist;
+  a.order = hist && ordered ? hist + a.B : nullptr;
+  if (hist && !a.order && first_order && a.B > 1024) {
+    if (int rc = mpc_first_order_launch(a, hist, hist + a.B, stream)) return rc;
+    a.order = hist + a.B;
+  }
+  if (big) a.warm = nullptr;
+  if (int rc = big ? mpc_big_solve_launch(ctx, a, stream) : mpc_solve_dispatch(ctx, a, stream)) return rc;
+  return hist ? mpc_plan_order_launch(hist, hist + a.B, a.B, a.s.check_every, stream) : F16_OK;
+}
+
 // mode 0: generic one-wave kernel (build + ADMM); 1: build only (workspace P, A'A, q|G|pred; *keep receives the block,
 // the caller frees it); 2: build, then the register-resident 512-thread solver (N <= 32); 3: build, then the 512-lane workgroup
 // solver for long horizons (N > 32, f16_mpc_big.hip).
 static int mpc_launch(f16_ctx *ctx, MpcArgs &a, void *stream, int mode, void **keep = nullptr) {
   const int N = a.N;
-  const bool big = N > MAXN;
   if (N < 1 || N > BIG_MAXN || (N > FAST_MAXN && mode == 2)) return set_error(F16_EINVAL, "horizon must be 1..150 (plans: 1..40)");
-  const size_t lds = mpc_lds_doubles(N, mode != 0, big) * sizeof(double);
-  if (lds > 160 * 1024) return set_error(F16_EINVAL, "horizon too large for LDS");
   if (int rc = mpc_lds_opt_in()) return rc;
-  void *block = nullptr;
   // the wavefront solver (f16_mpc_wave.hip: N <= 30, equilibrated solves) keeps its per-aircraft workspace in the Gram block
   const bool wave_ok = mode == 2 && N <= WAVE_MAXN && a.s.scaling > 0 && a.s.max_iter > 0;
-  if (int rc = mpc_work_alloc(ctx, a, mode != 0, stream, &block, mode == 2 && (a.s.adaptive_rho || wave_ok), wave_ok)) return rc;
-  int rc = F16_OK;
-  if (mode == 0) {
-    if (big) hipLaunchKernelGGL((k_mpc<false, true>), dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_mpc<false>, dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
-    rc = hip_check(hipGetLastError(), "f16_mpc_batch launch");
-  } else {
-    if (big) hipLaunchKernelGGL((k_mpc<true, true>), dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_mpc<true>, dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
-    rc = hip_check(hipGetLastError(), "f16_mpc_batch setup launch");
+  // (long horizons: the workgroup solver's operands, or beyond MAXN the generic kernel's -- the block holds either)
+  const MpcWork w = mpc_work_one_shot(N, mode, a.s.adaptive_rho, wave_ok, mpc_ext_doubles(N), std::max(mpc_big_ws_doubles(N), mpc_big_doubles(N)));
+  void *block = nullptr;
+  if (int rc = mpc_work_alloc(ctx, w.total() * (size_t)a.B * sizeof(double), stream, "f16_mpc_batch", true, &block)) return rc;
+  w.place(a, (double *)block);
+  int rc = mpc_build_launch(a, mode != 0, stream, mode ? "f16_mpc_batch setup launch" : "f16_mpc_batch launch");
 #ifdef F16_EXP_STAMPB
-    mode = 1;
+  mode = 1;
 #endif
-    if (!rc && mode == 3) {
-      MpcArgs w = a;
-      w.mode = 0;
-      rc = mpc_big_solve_launch(ctx, w, stream);
-    }
-    if (!rc && mode == 2) {
-      // Dispatch order (see k_plan_order): the reference's closed loops call calc_MPC_action once per step on states that
-      // move little, so the iteration counts of the previous call of the same batch size ON THE SAME STREAM predict this
-      // one's; any order is valid, a stale one only loses the gain.  F16_MPC_DISPATCH_ORDER=0 keeps the caller's order.
-      // A first call has no such counts: its order comes from the QPs themselves (mpc_first_order_launch: by ||q||_inf).
-      // F16_MPC_DISPATCH_ORDER=first treats every call as a first one (benchmarks: what BASELINE config 4, one call on an unseen
-      // batch, costs); =0 switches every ordering off.
-      const char *ev = getenv("F16_MPC_DISPATCH_ORDER");
-      const bool always_first = ev && ev[0] == 'f';
-      f16_ctx::sched_entry *se = (ev && ev[0] == '0') ? nullptr : mpc_sched_entry(ctx, stream, a.B);
-      if (se) { a.iters_out = se->buf; a.order = (se->valid && !always_first) ? se->buf + a.B : nullptr; }
-      if (se && !a.order && a.B > 1024) {
-        rc = mpc_first_order_launch(a, se->buf, se->buf + a.B, stream);
-        if (!rc) a.order = se->buf + a.B;
-      }
-      if (!rc) rc = mpc_solve_dispatch(ctx, a, stream);
-      if (!rc && se) {
-        rc = mpc_plan_order_launch(se->buf, se->buf + a.B, a.B, a.s.check_every, stream);
-        if (!rc) se->valid = 1;
-      }
-    }
+  if (!rc && mode >= 2) {
+    // The history of a one-shot call is per (stream, batch size); N > 32 keeps none.  F16_MPC_DISPATCH_ORDER=0 keeps the caller's
+    // order; =first treats every call as a first one (benchmarks: what BASELINE config 4, one call on an unseen batch, costs).
+    const char *ev = getenv("F16_MPC_DISPATCH_ORDER");
+    f16_ctx::sched_entry *se = mode == 3 || (ev && ev[0] == '0') ? nullptr : mpc_sched_entry(ctx, stream, a.B);
+    rc = mpc_ordered_solve(ctx, a, se ? se->buf : nullptr, se && se->valid && !(ev && ev[0] == 'f'), mode == 2, stream);
+    if (!rc && se) se->valid = 1;
   }
   if (keep && !rc) { *keep = block; return F16_OK; }
   const int rf = mpc_work_free(block, stream);
@@ -1090,14 +1098,7 @@ extern "C" int f16_mpc_batch_w(f16_ctx *ctx, const double *Ad, const double *Bd,
   a.B = B; a.ld = ld; a.N = hzn; a.dt = dt;
   if (int rc = mpc_fill_prob(&a.pb, h_w)) return rc;
   if (s) a.s = *s; else f16_qp_default_settings(&a.s);
-  if (a.s.check_every < 1 || a.s.rho_every < 1 || !(a.s.rho >= 0) || !(a.s.sigma > 0) || a.s.scaling < 0 || a.s.scaling > 100 ||
-      (a.s.scaling > 0 && !(a.s.rho > 0)))
-    return set_error(F16_EINVAL, "bad QP settings (the automatic start value of rho, rho = 0, needs scaling = 0)");
-  // the rho estimate is formed from the residuals of a termination test, so it can only run on an iteration that has one
-  // (osqp.c adapts independently of check_termination; here an interval that is not a multiple would silently become the
-  // least common multiple)
-  if (a.s.adaptive_rho && a.s.rho_every % a.s.check_every != 0)
-    return set_error(F16_EINVAL, "bad QP settings: rho_every must be a multiple of check_every");
+  if (int rc = mpc_check_settings(a.s, false, "f16_mpc_batch")) return rc;
   // solver selection: N <= 32 the register-resident / one-wavefront solvers, longer horizons the workgroup solver with its
   // operands in HBM; a negative max_iter forces the generic one-wave kernel (tests: the cross-check of every other solver)
   const bool generic = a.s.max_iter < 0;
@@ -1119,6 +1120,7 @@ extern "C" int f16_mpc_hzn_sweep(f16_ctx *ctx, const double *Ad, const double *B
   if (B == 0) return F16_OK;
   f16_qp_settings st;
   if (s) st = *s; else f16_qp_default_settings(&st);
+  if (int rc = mpc_check_settings(st, false, "f16_mpc_hzn_sweep")) return rc;
   int N = hzn_lo;
   for (; N <= hzn_hi && (N <= FAST_MAXN || st.max_iter < 0); ++N) {
     const size_t k = (size_t)(N - hzn_lo);
@@ -1129,13 +1131,7 @@ extern "C" int f16_mpc_hzn_sweep(f16_ctx *ctx, const double *Ad, const double *B
   MpcArgs a{};
   mpc_default_prob(&a.pb);
   a.Ad = Ad; a.Bd = Bd; a.Cd = Cd; a.x = x; a.dem = dem; a.B = B; a.ld = ld; a.dt = dt; a.s = st;
-  if (a.s.check_every < 1 || a.s.rho_every < 1 || !(a.s.rho >= 0) || !(a.s.sigma > 0) || a.s.scaling < 0 || a.s.scaling > 100 ||
-      (a.s.scaling > 0 && !(a.s.rho > 0)) || (a.s.adaptive_rho && a.s.rho_every % a.s.check_every != 0))
-    return set_error(F16_EINVAL, "bad QP settings");
   if (int rc = mpc_lds_opt_in()) return rc;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return set_error(F16_EINVAL, "f16_mpc_hzn_sweep cannot be captured into a HIP graph (per-call workspace)");
   // groups of horizons, longest first, each within the workspace budget (N = 150: 4.45 MB per aircraft = mpc_big_sweep_job_doubles(150) x 8)
   static const size_t budget = [] { const char *e = getenv("F16_SWEEP_WS_GB"); const double g = e ? atof(e) : 0; return (size_t)((g > 0 ? g : 32.0) * (1ull << 30)); }();
   int hi = hzn_hi;
@@ -1145,25 +1141,18 @@ extern "C" int f16_mpc_hzn_sweep(f16_ctx *ctx, const double *Ad, const double *B
     while (lo - 1 >= N && (doubles + mpc_big_sweep_job_doubles(lo - 1)) * (size_t)B * sizeof(double) <= budget) doubles += mpc_big_sweep_job_doubles(--lo);
     void *block = nullptr;
     const size_t wbytes = doubles * (size_t)B * sizeof(double);
-    if (int rc = hip_check(hipMallocFromPoolAsync(&block, wbytes + 256, ctx->pool, (hipStream_t)stream),
-                           "hipMallocFromPoolAsync sweep workspace")) return rc;
+    if (int rc = mpc_work_alloc(ctx, wbytes + 256, stream, "f16_mpc_hzn_sweep", false, &block)) return rc;
     unsigned int *next = (unsigned int *)((char *)block + wbytes);      // work-queue counter of the solve launch
     int rc = hip_check(hipMemsetAsync(next, 0, 256, (hipStream_t)stream), "hipMemsetAsync sweep queue");
     size_t off = 0;
     for (int Nn = hi; Nn >= lo && !rc; --Nn) {           // the builds (one wavefront per aircraft each)
       MpcArgs b = a;
-      const size_t np = (size_t)(3 * Nn) * (3 * Nn + 1) / 2, k = (size_t)(Nn - hzn_lo);
+      const size_t k = (size_t)(Nn - hzn_lo);
       b.N = Nn;
-      b.Ppk = (double *)block + off * (size_t)B;
-      b.ext = b.Ppk + np * (size_t)B;
-      b.bigws = b.ext + mpc_ext_doubles(Nn) * (size_t)B;
+      mpc_work_sweep(Nn, mpc_ext_doubles(Nn), mpc_big_ws_doubles(Nn)).place(b, (double *)block + off * (size_t)B);
       b.ucmd = u_cmd + k * 3 * ld;
       b.status = status ? status + k * ld : nullptr;
-      const bool big = Nn > MAXN;
-      const size_t lds = mpc_lds_doubles(Nn, true, big) * sizeof(double);
-      if (big) hipLaunchKernelGGL((k_mpc<true, true>), dim3(wave_grid(B)), dim3(64), lds, (hipStream_t)stream, b);
-      else hipLaunchKernelGGL(k_mpc<true>, dim3(wave_grid(B)), dim3(64), lds, (hipStream_t)stream, b);
-      rc = hip_check(hipGetLastError(), "f16_mpc_hzn_sweep build launch");
+      rc = mpc_build_launch(b, true, stream, "f16_mpc_hzn_sweep build launch");
       off += mpc_big_sweep_job_doubles(Nn);
     }
     // Queue order: the pairs of a previous sweep of the same horizons on this stream, costliest first (iterations x N^2) -- a
@@ -1210,15 +1199,6 @@ struct f16_mpc_plan {
   MpcArgs a;
 };
 
-static int plan_launch_build(f16_mpc_plan *p, MpcArgs &a, void *stream) {
-  const size_t lds = mpc_lds_doubles(p->N, true) * sizeof(double);
-  if (a.mode == 1) {      // once per device (the solve path may run under stream capture)
-    if (int rc = mpc_lds_opt_in()) return rc;
-  }
-  hipLaunchKernelGGL(k_mpc<true>, dim3(wave_grid(a.B)), dim3(64), lds, (hipStream_t)stream, a);
-  return hip_check(hipGetLastError(), "f16_mpc_plan build launch");
-}
-
 extern "C" int f16_mpc_plan_create(f16_ctx *ctx, f16_mpc_plan **plan, const double *Ad, const double *Bd, const double *Cd,
                                    long B, long ld, int hzn, double dt, const f16_qp_settings *s, void *stream) {
   return f16_mpc_plan_create_w(ctx, plan, Ad, Bd, Cd, nullptr, B, ld, hzn, dt, s, stream);
@@ -1231,35 +1211,27 @@ extern "C" int f16_mpc_plan_create_w(f16_ctx *ctx, f16_mpc_plan **plan, const do
   MpcProb pb;
   if (int rc = mpc_fill_prob(&pb, h_w)) return rc;
   if (hzn < 1 || hzn > MAXN) return set_error(F16_EINVAL, "prepared plans need 1 <= hzn <= 40");
+  f16_qp_settings st;
+  if (s) st = *s; else f16_qp_default_settings(&st);
+  if (int rc = mpc_check_settings(st, true, "f16_mpc_plan_create")) return rc;      // (before anything is allocated)
+  const bool wide = hzn > FAST_MAXN;                   // horizons 33..40: the model part is kept, every solve runs the workgroup solver
+  if (int rc = mpc_lds_opt_in()) return rc;            // the LDS opt-ins now: the first solve of the plan may already be under capture
+  if (int rc = wide ? mpc_big_opt_in() : F16_OK) return rc;
   f16_mpc_plan *p = new f16_mpc_plan();
   p->ctx = ctx; p->B = B; p->ld = ld; p->N = hzn; p->dt = dt;
   p->warm = nullptr; p->warm_on = false; p->have_prev = false; p->sched = nullptr; p->have_order = false; p->last_stream = stream;
   p->roll_sync = nullptr; p->relin_w = nullptr; p->relin_model = false;
-  if (s) p->s = *s; else f16_qp_default_settings(&p->s);
-  if (p->s.check_every < 1 || p->s.rho_every < 1 || !(p->s.rho >= 0) || !(p->s.sigma > 0) || p->s.max_iter < 1 || p->s.scaling < 0 ||
-      p->s.scaling > 100 || (p->s.scaling > 0 && !(p->s.rho > 0)) || (p->s.adaptive_rho && p->s.rho_every % p->s.check_every != 0)) {
-    delete p;
-    return set_error(F16_EINVAL, "bad QP settings (rho_every must be a multiple of check_every)");
-  }
-  const size_t np = (size_t)(3 * hzn) * (3 * hzn + 1) / 2;
-  const bool wide = hzn > FAST_MAXN;                   // horizons 33..40: the model part is kept, every solve runs the workgroup solver
-  if (wide) {                                          // its LDS opt-in now: the first solve of the plan may already be under capture
-    if (int rc = mpc_big_opt_in()) { delete p; return rc; }
-  }
-  const size_t per = np + mpc_ext_doubles(hzn) + 2 * MPC_TILE_DOUBLES + (wide ? mpc_big_ws_doubles(hzn) : 0);      // P | extras | inverse (scaling = 0) | A'WA | long-horizon operands
-  if (int rc = hip_check(hipMalloc(&p->buf, per * (size_t)B * sizeof(double)), "hipMalloc MPC plan")) { delete p; return rc; }
+  p->s = st;
+  const MpcWork w = mpc_work_plan(hzn, mpc_ext_doubles(hzn), mpc_big_ws_doubles(hzn));
+  if (int rc = hip_check(hipMalloc(&p->buf, w.total() * (size_t)B * sizeof(double)), "hipMalloc MPC plan")) { delete p; return rc; }
   if (int rc = hip_check(hipMalloc(&p->sched, 2 * (size_t)B * sizeof(int32_t)), "hipMalloc MPC plan")) { (void)hipFree(p->buf); delete p; return rc; }
   MpcArgs &a = p->a;
   a = MpcArgs{};
   a.pb = pb;
   a.Ad = Ad; a.Bd = Bd; a.Cd = Cd; a.B = B; a.ld = ld; a.N = hzn; a.dt = dt; a.s = p->s;
-  a.Ppk = p->buf; a.ext = a.Ppk + np * (size_t)B;
-  a.tiles = a.ext + mpc_ext_doubles(hzn) * (size_t)B;
-  a.gramws = a.tiles + MPC_TILE_DOUBLES * (size_t)B;
-  a.pblk = a.tiles;                                    // (equilibrated plans keep no inverse: the block is the wavefront solver's)
-  a.bigws = wide ? a.gramws + MPC_TILE_DOUBLES * (size_t)B : nullptr;
+  w.place(a, p->buf);
   a.mode = 1;
-  int rc = plan_launch_build(p, a, stream);
+  int rc = mpc_build_launch(a, true, stream, "f16_mpc_plan build launch");
   // Without equilibration the start value of rho and the KKT factorisation depend on the model only and are cached too.
   // OSQP's equilibration depends on q (the cost scaling c looks at ||q||, and D, E at c), i.e. on the state of the call:
   // a plan with scaling > 0 keeps the model part (DARE, G_k, P) and redoes equilibration + factorisation per solve.
@@ -1285,19 +1257,10 @@ extern "C" int f16_mpc_plan_solve_w(f16_mpc_plan *p, const double *x, const doub
   a.mode = 2;
   a.warm = p->warm_on ? p->warm : nullptr;
   a.warm_load = p->warm_on && p->have_prev;
-  a.iters_out = p->sched;
-  a.order = p->have_order ? p->sched + p->B : nullptr;
-  if (int rc = plan_launch_build(p, a, stream)) return rc;
-  if (!a.order && p->B > 1024 && p->N <= FAST_MAXN) {      // first solve of the plan: longest-first by ||q||_inf of the QPs just built
-    if (int rc = mpc_first_order_launch(a, p->sched, p->sched + p->B, stream)) return rc;
-    a.order = p->sched + p->B;
-  }
+  if (int rc = mpc_build_launch(a, true, stream, "f16_mpc_plan build launch")) return rc;
   if (p->s.scaling > 0 || p->N > FAST_MAXN) a.mode = 0;   // nothing cached beyond the model part: full solver prologue
-  if (p->N > FAST_MAXN) {
-    a.warm = nullptr;
-    if (int rc = mpc_big_solve_launch(p->ctx, a, stream)) return rc;
-  } else if (int rc = mpc_solve_dispatch(p->ctx, a, stream)) return rc;
-  if (int rc = mpc_plan_order_launch(p->sched, p->sched + p->B, p->B, p->s.check_every, stream)) return rc;
+  // the history is the plan's own; a first solve is ordered by the QPs just built (F16_MPC_DISPATCH_ORDER steers one-shot calls only)
+  if (int rc = mpc_ordered_solve(p->ctx, a, p->sched, p->have_order, p->N <= FAST_MAXN, stream)) return rc;
   p->have_order = true;
   p->have_prev = p->warm_on;
   return F16_OK;

@@ -54,15 +54,16 @@ struct MpcArgs {
   MpcProb pb;
   double *ucmd, *useq, *info;
   int32_t *status;
-  double *Ppk;                // workspace [B][np] packed P (A'A is never stored: the solvers form the weighted Gram themselves)
-  double *ext;                // workspace [B][mpc_ext_doubles(N)]: q | G | pred | A | Q | Qbar | rho, ok | scaling (setup kernel -> solver / debug)
-  double *tiles;              // prepared plans without equilibration: [B][MPC_TILE_DOUBLES] the re-laid KKT inverse
-  double *bigws;              // horizons beyond MAXN: [B][mpc_big_doubles(N)] seven per-row vectors | packed KKT inverse
+  // The workspace blocks, each [B][per-aircraft size]: which of them a call has, and in which order they lie, is MpcWork's (below).
+  double *Ppk;                // [B][mpc_np(N)] packed P (A'A is never stored: the solvers form the weighted Gram themselves)
+  double *ext;                // [B][mpc_ext_doubles(N)]: q | G | pred | A | Q | Qbar | rho, ok | scaling (setup kernel -> solver / debug); null: mode 0
+  double *tiles;              // prepared plans without equilibration: [B][MPC_TILE_DOUBLES] the re-laid KKT inverse; null in one-shot calls
+  double *bigws;              // N > FAST_MAXN: the workgroup solver's operands [B][mpc_big_ws_doubles(N)]; in one-shot calls the larger of
+                              // that and [B][mpc_big_doubles(N)], the generic kernel's seven per-row vectors | packed KKT inverse (N > MAXN)
   double *gramws;             // [B][MPC_TILE_DOUBLES] A'WA as matrix-core tiles, written by a solve's first factorisation and
                               // re-read by its rho updates (the Gram product does not depend on rho); may be null (recomputed)
   double *pblk;               // wavefront solver: [B][WAVE_PBLK_DOUBLES] P as the symmetric block image (termination test) | the lanes'
-                              // Toeplitz operands [36][64] double2; plans: the
-                              // `tiles` block (unused with equilibration)
+                              // Toeplitz operands [36][64] double2; plans: the `tiles` block (unused with equilibration)
   int wave_ruiz;              // wavefront solver: equilibrate in the solver itself (else: k_mpc_fast mode 3 went before it)
   unsigned wave_stride;       // wavefront solver without a dispatch order: workgroup w solves aircraft (w * wave_stride) % B, a
                               // stride coprime to B (0: the identity)
@@ -172,5 +173,64 @@ constexpr int FAST_MAXN = 32;
 int mpc_fast_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream);
 int mpc_plan_order_launch(const int32_t *iters, int32_t *order, long B, int check_every, void *stream);
 int mpc_first_order_launch(const MpcArgs &a, int32_t *scratch, int32_t *order, void *stream);      // first call: longest-first by ||q||_inf
+
+// ---- The per-aircraft workspace of a solve call, stated once (host).  A call says which blocks it has and how many doubles each
+// takes per aircraft; the blocks lie in the order of `size`, each [B][size], so a block starts (the sizes before it) x B doubles
+// behind the base.  The three rules below are the callers' whole say; place() sets the six MpcArgs pointers from them.
+constexpr size_t mpc_np(int N) { return (size_t)(3 * N) * (3 * N + 1) / 2; }      // packed P of the condensed QP (n = 3N)
+struct MpcWork {
+  enum { P, EXT, TILES, GRAM, BIG, PBLK, NBLOCKS, NONE = -1 };
+  size_t size[NBLOCKS] = {};
+  constexpr long at(int blk) const {      // per-aircraft offset of a block (NBLOCKS: the total); NONE: no such block, its pointer is null
+    if (blk == PBLK && !size[PBLK]) blk = TILES;      // a plan's wavefront block IS its tiles block (unused with equilibration)
+    if (blk < NBLOCKS && !size[blk]) return NONE;
+    long o = 0;
+    for (int i = 0; i < blk; ++i) o += (long)size[i];
+    return o;
+  }
+  constexpr size_t total() const { return (size_t)at(NBLOCKS); }
+  void place(MpcArgs &a, double *base) const {
+    auto ptr = [&](int blk) { return at(blk) == NONE ? nullptr : base + (size_t)at(blk) * (size_t)a.B; };
+    a.Ppk = ptr(P); a.ext = ptr(EXT); a.tiles = ptr(TILES); a.gramws = ptr(GRAM); a.bigws = ptr(BIG); a.pblk = ptr(PBLK);
+  }
+};
+// ext = mpc_ext_doubles(N); big = what the long-horizon solvers keep in HBM (taken only when N > FAST_MAXN).  Both are arguments
+// because their size functions are shared with device code and not constexpr; the rules themselves are, and are pinned below.
+// One-shot call (mode as in mpc_launch; wave: the wavefront solver applies): P | ext | A'WA | long-horizon operands | wavefront block.
+constexpr MpcWork mpc_work_one_shot(int N, int mode, bool adaptive_rho, bool wave, size_t ext, size_t big) {
+  MpcWork w;
+  w.size[MpcWork::P] = mpc_np(N);
+  if (mode != 0) w.size[MpcWork::EXT] = ext;
+  if (mode == 2 && (adaptive_rho || wave)) w.size[MpcWork::GRAM] = MPC_TILE_DOUBLES;
+  if (N > FAST_MAXN) w.size[MpcWork::BIG] = big;
+  if (wave) w.size[MpcWork::PBLK] = WAVE_PBLK_DOUBLES;
+  return w;
+}
+// Prepared plan: P | ext | inverse (scaling = 0) or wavefront block (equilibrated) | A'WA | long-horizon operands.
+constexpr MpcWork mpc_work_plan(int N, size_t ext, size_t big) {
+  MpcWork w = mpc_work_one_shot(N, 1, false, false, ext, big);
+  w.size[MpcWork::TILES] = w.size[MpcWork::GRAM] = MPC_TILE_DOUBLES;
+  return w;
+}
+// One horizon of a sweep group: the build-only layout P | ext | long-horizon operands -- mpc_big_sweep_job_doubles(N) in all, as
+// k_mpc_big recomputes it.
+constexpr MpcWork mpc_work_sweep(int N, size_t ext, size_t big) { return mpc_work_one_shot(N, 1, false, false, ext, big); }
+
+// The layouts written out as per-aircraft offsets: ext, tiles, gram, big, pblk, total.  (ext = 39 N + 247; big = mpc_big_ws_doubles(N)
+// evaluated once.  The two size functions themselves are left to the GPU tests, which run every one of these cases.)
+constexpr bool mpc_work_is(const MpcWork &w, long ext, long tiles, long gram, long big, long pblk, long total) {
+  return w.at(MpcWork::P) == 0 && w.at(MpcWork::EXT) == ext && w.at(MpcWork::TILES) == tiles && w.at(MpcWork::GRAM) == gram &&
+         w.at(MpcWork::BIG) == big && w.at(MpcWork::PBLK) == pblk && (long)w.total() == total;
+}
+static_assert(mpc_work_is(mpc_work_one_shot(10, 0, true, false, 637, 0), -1, -1, -1, -1, -1, 465), "one-shot N = 10, generic kernel");
+static_assert(mpc_work_is(mpc_work_one_shot(30, 2, true, true, 1417, 0), 4095, -1, 5512, -1, 14728, 23944), "one-shot N = 30, wavefront solver");
+static_assert(mpc_work_is(mpc_work_one_shot(32, 2, true, false, 1495, 0), 4656, -1, 6151, -1, -1, 15367), "one-shot N = 32, adaptive rho");
+static_assert(mpc_work_is(mpc_work_one_shot(33, 3, true, false, 1534, 30870), 4950, -1, -1, 6484, -1, 37354), "one-shot N = 33");
+static_assert(mpc_work_is(mpc_work_one_shot(40, 3, true, false, 1807, 41244), 7260, -1, -1, 9067, -1, 50311), "one-shot N = 40");
+static_assert(mpc_work_is(mpc_work_one_shot(40, 0, true, false, 1807, 41244), -1, -1, -1, 7260, -1, 48504), "one-shot N = 40, generic kernel");
+static_assert(mpc_work_is(mpc_work_one_shot(150, 3, true, false, 6097, 448803), 101475, -1, -1, 107572, -1, 556375), "one-shot N = 150");
+static_assert(mpc_work_is(mpc_work_plan(30, 1417, 0), 4095, 5512, 14728, -1, 5512, 23944), "plan N = 30: pblk = tiles");
+static_assert(mpc_work_is(mpc_work_plan(40, 1807, 41244), 7260, 9067, 18283, 27499, 9067, 68743), "plan N = 40");
+static_assert(mpc_work_is(mpc_work_sweep(150, 6097, 448803), 101475, -1, -1, 107572, -1, 556375), "sweep N = 150");
 
 }  // namespace f16

@@ -1053,6 +1053,39 @@ np.savez(sys.argv[1], u=sw.cpu().numpy(), iters=inf["iters"].cpu().numpy(), stat
     assert np.array_equal(g["iters"], inf["iters"].cpu().numpy()) and np.array_equal(g["status"], inf["status"].cpu().numpy())
 
 
+def test_one_table_of_qp_settings_through_the_one_shot_call_the_plan_and_the_sweep():
+    """The QP settings are checked by one rule (mpc_check_settings) behind the three calls that take them: the one-shot call
+    (f16_mpc_batch_w), prepare_MPC (f16_mpc_plan_create_w) and the horizon sweep (f16_mpc_hzn_sweep; horizons 1..3: its one-shot
+    part).  One table through all three: what is refused is refused everywhere with the library's error, what is accepted runs
+    everywhere, and max_iter <= 0 (negative: the generic kernel) is the one setting on which they differ -- a plan needs
+    iterations.  A refusal leaves nothing behind: the default call on the same environment returns finite commands after each."""
+    from f16_mpc_oop_py_amd import lib
+    from f16_mpc_oop_py_amd.workload import config4_states
+    x0, u0 = config4_states(2, seed=9)
+    env = make_env(x0, u0, xcg=0.35)
+    env.build_ssr()
+    dem, N = (0.01, 0.0, -0.01), 4
+
+    def plan(st):
+        env.prepare_MPC(N, settings=st)
+        return env._calc_MPC_action(*dem, N, use_plan=True)
+
+    calls = {"one_shot": lambda st: env._calc_MPC_action(*dem, N, settings=st), "plan": plan,
+             "sweep": lambda st: env._calc_constr_checking_hzn(max_hzn=3, settings=st)}
+    refused = [dict(check_every=0), dict(rho_every=0), dict(rho=-1.0), dict(rho=float("nan")), dict(sigma=0.0), dict(scaling=-1),
+               dict(scaling=101), dict(scaling=10, rho=0.0), dict(adaptive_rho=1, rho_every=30, check_every=25)]
+    accepted = [dict(adaptive_rho=0, rho_every=30, check_every=25), dict(scaling=0, rho=0.0)]
+    no_iterations = [dict(max_iter=-50), dict(max_iter=0)]
+    for name, call in calls.items():
+        for st in refused + (no_iterations if name == "plan" else []):
+            with pytest.raises(lib.F16HipError):
+                call(st)
+            assert bool(torch.isfinite(call(None)).all()), (name, st)
+        for st in accepted + (no_iterations if name != "plan" else []):
+            call(st)
+            torch.cuda.synchronize()
+
+
 def test_wavefront_solver_vs_the_512_lane_solver_and_its_equilibration(tmp_path):
     """The one-wavefront-per-aircraft solver (k_mpc_wave, the default for equilibrated solves up to N = 30) against the
     512-lane solver (F16_MPC_WAVE=0) on the same QPs: same iteration counts, status words and final rho, input sequences to
