@@ -8,6 +8,8 @@
 //                         (F16_FLAG_ONE_LANE; the step the closed MPC loop f16_rollout_mpc takes)
 //   k_rollout / k_rollout_i / k_rollout_exact <..., STAGES = 4>  the scheduled rollouts with the classical Runge-Kutta step instead of
 //                         the Euler step (f16_rollout_rk, f16_rollout_lqr_rk, f16_rollout_cost_rk with F16_INT_RK4)
+//   k_rollout_mppi / k_rollout_mppi_exact  the closed MPPI loop -- sample, score, blend, advance, shift per control period -- as one
+//                         launch, one workgroup per aircraft, on the lane bodies of the scored and scheduled rollouts (f16_rollout_mppi)
 //   k_rollout_lqr_linear  test_env_mk2.py:46-62 / test_env.py:501-576: the linear-model LQR loops (f16_rollout_lqr_linear)
 //
 // Mapping: one lane = one aircraft; state-major [k][ld] arrays so a wave's 64 lanes read 512 contiguous
@@ -25,6 +27,7 @@
 #include "f16_ctx.h"
 #include "f16_plant.hpp"
 #include "f16_plant_quad.hpp"
+#include "f16_mppi.hpp"
 
 namespace f16 {
 
@@ -211,23 +214,42 @@ constexpr bool INC_TRIG = false;
 // step (rk4_step, f16_plant.hpp) with the command -- under the LQR law the action formed from the state at the start of the step --
 // held over its four stages.  INCT is false then: every stage evaluates its sin / cos pairs exactly, so nothing but the state is
 // carried from step to step and a rollout of n + m steps equals one of n followed by one of m bit for bit.
+// LANES: which lanes the calling thread rolls out, and where a scored lane finds its aircraft and its reference.  GridLanes: the
+// grid-stride loop of every k_rollout* kernel.  The fused MPPI loop (k_rollout_mppi) hands over the ONE lane of its thread instead
+// (MppiLane), whose reference is formed from the initial state and the demands rather than read from a.x_ref.
+struct GridLanes {
+  F16_DEV long first(int block) const { return (long)blockIdx.x * block + threadIdx.x; }
+  template <typename ARGS> F16_DEV long end(const ARGS &a) const { return a.B; }
+  F16_DEV long stride(int block) const { return (long)gridDim.x * block; }
+  F16_DEV long aircraft(const CostArgs &a, long b) const { return b % a.B0; }
+  F16_DEV double reference(const CostArgs &a, int k, const double *, long b0) const { return a.x_ref[k * a.ld0 + b0]; }
+};
+struct MppiLane {
+  long b, b0;
+  F16_DEV long first(int) const { return b; }
+  template <typename ARGS> F16_DEV long end(const ARGS &) const { return b + 1; }
+  F16_DEV long stride(int) const { return 1; }
+  F16_DEV long aircraft(const CostArgs &, long) const { return b0; }
+  // calc_MPPI_action: the lane's initial x9 with entries 4..6 = the demands
+  F16_DEV double reference(const CostArgs &a, int k, const double *x, long c) const { return k >= 4 && k < 7 ? a.dem[(k - 4) * a.ld0 + c] : mpc_state(x, k); }
+};
 template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false, bool COST = false, bool XRL = false,
-          int STAGES = 1>
+          int STAGES = 1, typename LANES = GridLanes>
 __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
-                                              double (*tgs)[BLOCK] = nullptr, double (*xr)[BLOCK] = nullptr) {
+                                              double (*tgs)[BLOCK] = nullptr, double (*xr)[BLOCK] = nullptr, const LANES lanes = {}) {
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   static_assert(STAGES == 1 || (STAGES == 4 && SCHED && !INCT), "the Runge-Kutta step: scheduled variants, exact sin / cos");
-  for (long b = (long)blockIdx.x * BLOCK + threadIdx.x; b < a.B; b += (long)gridDim.x * BLOCK) {
+  for (long b = lanes.first(BLOCK); b < lanes.end(a); b += lanes.stride(BLOCK)) {
     double x[18];
     long b0 = b;                                         // (COST) the aircraft of this lane: the column of x0 / x_ref / u_ref
     double J = 0, ju = 0;                                // (COST) the cost so far; the command term of the row in use
     if constexpr (COST) {
-      b0 = b % a.B0;
+      b0 = lanes.aircraft(a, b);
 #pragma unroll
       for (int k = 0; k < 18; ++k) x[k] = a.x0[k * a.ld0 + b0];
       if (XRL) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) xr[k][threadIdx.x] = a.x_ref[k * a.ld0 + b0];
+        for (int k = 0; k < 9; ++k) xr[k][threadIdx.x] = lanes.reference(a, k, x, b0);
       }
     } else {
 #pragma unroll
@@ -342,93 +364,17 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
 // steps with.  Same rules as rollout_lanes (envelope freeze, status bits, trajectory samples, u_out); a reproducibility path, not a
 // fast one.
 // STAGES = 4: the Runge-Kutta step through the out-of-line rk4_step_exact instead.
+// The lane loop itself is f16_rollout_exact.inc: included here, and in rollout_exact_lanes for the fused MPPI loop under the flag.
 template <bool LQR, bool SCHED = false, bool COST = false, int STAGES = 1>
 __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a) {
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   static_assert(STAGES == 1 || (STAGES == 4 && SCHED), "the Runge-Kutta step: scheduled variants");
-  for (long b = (long)blockIdx.x * 64 + threadIdx.x; b < a.B; b += (long)gridDim.x * 64) {
-    double x[18], u[4];
-    long b0 = b;                                         // (COST: as in rollout_lanes; the reference in registers)
-    double J = 0, ju = 0, xr[COST ? 9 : 1];
-    if constexpr (COST) {
-      b0 = b % a.B0;
-#pragma unroll
-      for (int k = 0; k < 18; ++k) x[k] = a.x0[k * a.ld0 + b0];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) xr[k] = a.x_ref[k * a.ld0 + b0];
-    } else {
-#pragma unroll
-    for (int k = 0; k < 18; ++k) x[k] = a.out[k * a.ld + b];
-    }
-    [[maybe_unused]] const auto ref = [&](int k) { return xr[COST ? k : 0]; };
-    if (!COST || a.nsteps > 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) u[k] = a.u[k * a.ld + b];
-    }
-    if constexpr (COST) if (a.nsteps > 0) ju = cost_command_term(a, b0, u[1], u[2], u[3]);
-    double kq[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, u0[3] = {u[1], u[2], u[3]};
-    if (LQR) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) kq[3 * i + j] = a.K[(9 * i + 4 + j) * a.ld + b];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) kq[9 + j] = a.dem[j * a.ld + b];
-    }
-    int st = !COST && a.status ? a.status[b] : 0;
-    double *tr = a.traj ? a.traj + b : nullptr;
-    int until_store = a.traj_every;
-    constexpr int NR = LQR ? 3 : 4;
-    RowAhead<NR> ra;
-    if constexpr (SCHED) { ra.init(a, NR, a.out + b); ra.settle(); }
-    for (int t = 0; t < a.nsteps; ++t) {
-      if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;      // env.py:117-124
-      if (!(st & ST_ENVELOPE)) {
-        if (LQR) {
-          const double e0 = kq[9] - x[9], e1 = kq[10] - x[10], e2 = kq[11] - x[11];
-#pragma unroll
-          for (int i = 0; i < 3; ++i) u[1 + i] = lqr_action(kq[3 * i], kq[3 * i + 1], kq[3 * i + 2], e0, e1, e2, u0[i]);
-        }
-        if constexpr (STAGES == 4) rk4_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &st);
-        else
-        euler_step_exact(a.tab, a.lofi, x, u, a.dt, a.xcg, a.fi, a.flags, &st);
-        if constexpr (COST) J = cost_state_term(J + ju, x, a.w.q, ref);
-      } else if constexpr (COST) {
-        J += a.w.pen;
-      }
-      if (tr && --until_store == 0) {
-        until_store = a.traj_every;
-#pragma unroll
-        for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
-        tr += 18 * a.ld;
-      }
-      if constexpr (SCHED) if (ra.due(a, NR)) {
-        ra.take(a, NR, LQR ? kq + 9 : u, a.out + b);
-        if (LQR) { u[1] = u0[0]; u[2] = u0[1]; u[3] = u0[2]; }      // (as a new launch: u0 until it steps)
-        if constexpr (COST) ju = cost_command_term(a, b0, u[1], u[2], u[3]);
-      }
-    }
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 18; ++k) finite = finite && isfinite(x[k]);
-    if (!finite) st |= ST_NONFINITE;
-    if (st & ST_ENVELOPE) st |= envelope_state_bits(x);
-    if constexpr (COST) {
-      a.out[b] = cost_state_term(J, x, a.w.qf, ref);
-      if (a.x_end) {
-#pragma unroll
-        for (int k = 0; k < 18; ++k) a.x_end[k * a.ld + b] = x[k];
-      }
-    } else {
-#pragma unroll
-    for (int k = 0; k < 18; ++k) a.out[k * a.ld + b] = x[k];
-    }
-    if (a.status) a.status[b] = st;
-    if (LQR && a.u_out) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a.u_out[i * a.ld + b] = u[i];
-    }
-  }
+  const GridLanes lanes;
+#include "f16_rollout_exact.inc"
+}
+template <bool LQR, bool SCHED, bool COST, int STAGES, typename LANES>
+__device__ __forceinline__ void rollout_exact_lanes(const RolloutArgs<SCHED, COST> &a, const LANES lanes) {
+#include "f16_rollout_exact.inc"
 }
 
 template <int BLOCK, int FI, bool LQR = false, bool SCHED = false, bool COST = false, int STAGES = 1>
@@ -469,6 +415,119 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED, COST> a)
   }
   rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED, COST, COST, STAGES>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq),
                                                                 reinterpret_cast<double (*)[BLOCK]>(tgs), reinterpret_cast<double (*)[BLOCK]>(xr));
+}
+
+// The closed MPPI loop as ONE launch (f16_rollout_mppi): one workgroup = one aircraft, its lanes = that aircraft's K samples
+// (K <= 256; lanes >= K idle but take part in the barriers and in the table staging).  Per control period, between workgroup barriers:
+//   lanes < K        write their rows of the sample set (mppi_write_row: the statement of f16_mppi_sample) into u_seq, in the host
+//                    loop's layout, and score them -- the lane body of the scored rollout (rollout_lane / rollout_exact_lane with
+//                    COST), which reads back the lane's own column of u_seq and writes cost[lane];
+//   -- fence + barrier: the columns and costs are published to the workgroup
+//   lanes < 4 S      one (row, command) entry of the softmin blend each, k ascending (blend_walk: the arithmetic of k_mppi_blend);
+//                    row 0 goes to u, row r >= 1 to row r - 1 of u_nom, the last row also to the last row of u_nom (the shift);
+//   -- fence + barrier
+//   lane 0           advances the aircraft `hold` steps under u: the lane body of the scheduled rollout, one row held;
+//   -- fence + barrier: the next period's lanes read the new x and u_nom.
+// No spin-wait, no ticket, no state shared between workgroups; aircraft are drawn grid-stride.  The table image is staged once per
+// launch; the plant advance costs hold steps of ONE lane per period (the other lanes wait at the barrier) against S * hold scored
+// steps of all of them: a fraction 1 / (S + 1) of a period's step time.
+struct MppiArgs {
+  const double *tab, *lofi;
+  double *x, *u, *u_nom;           // [18][ld0], [4][ld0], [S][4][ld0]
+  const double *dem, *u_ref;       // [3][ld0]; [3][ld0] or null
+  double *u_seq, *cost;            // [S][4][ld], [ld]
+  double *stats, *traj;            // [nperiods][2][ld0] or null; [nperiods * hold / traj_every][18][ld0] or null
+  int32_t *status;                 // [ld0] or null
+  long B0, ld0, K, ld;
+  int nperiods, S, hold, traj_every;      // (traj_every = hold + 1 without traj)
+  double dt, xcg, lambda, sg[3];
+  int fi;
+  unsigned flags;
+  uint32_t key0, key1, period0;
+  f16_cost_weights w;
+};
+// score(CostArgs, lane, aircraft): one sample; advance(SchedArgs, aircraft): the plant under the blended command
+template <typename SCORE, typename ADVANCE>
+F16_DEV void mppi_periods(const MppiArgs &m, SCORE score, ADVANCE advance) {
+  const int tid = threadIdx.x;
+  for (long ac = blockIdx.x; ac < m.B0; ac += gridDim.x) {
+    const long b = tid * m.B0 + ac;                      // sample tid of this aircraft: its lane in u_seq / cost
+    for (int p = 0; p < m.nperiods; ++p) {
+      if (tid < m.K) {
+        for (int row = 0; row < m.S; ++row)
+          mppi_write_row(m.u_nom + (long)row * 4 * m.ld0 + ac, m.ld0, m.u_seq + (long)row * 4 * m.ld + b, m.ld, m.period0 + (uint32_t)p,
+                         (uint32_t)row, (uint32_t)tid, (uint32_t)ac, m.key0, m.key1, m.sg[0], m.sg[1], m.sg[2]);
+        CostArgs c{};                                    // what f16_rollout_cost fills for the host loop's call
+        c.tab = m.tab; c.lofi = m.lofi; c.B = m.K * m.B0; c.ld = m.ld; c.xcg = m.xcg; c.fi = m.fi; c.flags = m.flags;
+        c.u = c.seq = m.u_seq; c.out = m.cost; c.nsteps = m.S * m.hold; c.traj_every = c.nsteps + 1; c.dt = m.dt; c.dem = m.dem;
+        c.hold = m.hold; c.nrows = m.S; c.x0 = m.x; c.u_ref = m.u_ref; c.B0 = m.B0; c.ld0 = m.ld0; c.w = m.w;
+        score(c, b, ac);
+      }
+      __threadfence_block();
+      __syncthreads();
+      if (tid < 4 * m.S) {
+        const double *cost = m.cost + ac;
+        const double mn = blend_min(cost, m.K, m.B0);
+        const bool any = mn < INFINITY;
+        for (int e = tid; e < 4 * m.S; e += blockDim.x) {
+          const int row = e >> 2, cm = e & 3;
+          const double *u = m.u_seq + ((long)row * 4 + cm) * m.ld + ac;
+          double sw = 0, sw2 = 0, acc[1] = {0};
+          blend_walk<1>(cost, u, m.K, m.B0, m.ld, mn, m.lambda, true, sw, sw2, acc);
+          const double v = any ? acc[0] / sw : u[0];
+          if (row == 0) m.u[cm * m.ld0 + ac] = v;
+          else m.u_nom[((long)(row - 1) * 4 + cm) * m.ld0 + ac] = v;
+          if (row == m.S - 1) m.u_nom[((long)row * 4 + cm) * m.ld0 + ac] = v;
+          if (e == 0 && m.stats) {
+            double *st = m.stats + (long)p * 2 * m.ld0 + ac;
+            st[0] = any ? mn : 0.0; st[m.ld0] = any ? sw * sw / sw2 : 0.0;
+          }
+        }
+      }
+      __threadfence_block();
+      __syncthreads();
+      if (tid == 0) {
+        SchedArgs s{};                                   // f16_rollout(_rk) of `hold` steps under the one row u
+        s.tab = m.tab; s.lofi = m.lofi; s.status = m.status; s.B = m.B0; s.ld = m.ld0; s.xcg = m.xcg; s.fi = m.fi; s.flags = m.flags;
+        s.u = s.seq = m.u; s.out = m.x; s.nsteps = m.hold; s.traj_every = m.traj_every; s.dt = m.dt; s.hold = m.hold; s.nrows = 1;
+        s.traj = m.traj ? m.traj + (long)p * (m.hold / m.traj_every) * 18 * m.ld0 : nullptr;
+        advance(s, ac);
+      }
+      __threadfence_block();
+      __syncthreads();
+    }
+  }
+}
+
+// the twin of k_rollout<BLOCK, FI, false, true, true, STAGES>: the same LDS slots, the same lane body
+template <int BLOCK, int FI, int STAGES>
+__global__ __launch_bounds__(BLOCK) void k_rollout_mppi(MppiArgs m) {
+  __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
+  __shared__ double us[4][BLOCK];
+  constexpr bool INCT = INC_TRIG && STAGES == 1;
+  __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
+  __shared__ double xr[9][BLOCK];
+  static_assert(BLOCK <= 256 && sizeof(tab) + sizeof(us) + sizeof(tgs) + sizeof(xr) <= 163840, "static LDS of a CU");
+  if (m.fi == 1) stage_tables(tab, m.tab);
+  double (*const tg)[BLOCK] = reinterpret_cast<double (*)[BLOCK]>(tgs);
+  mppi_periods(m,
+               [&](const CostArgs &c, long b, long ac) {
+                 rollout_lanes<BLOCK, FI, const double *, false, INCT, true, true, true, STAGES>(c, (const double *)tab, us, nullptr, tg, xr,
+                                                                                                 MppiLane{b, ac});
+               },
+               [&](const SchedArgs &s, long ac) {
+                 rollout_lanes<BLOCK, FI, const double *, false, INCT, true, false, false, STAGES>(s, (const double *)tab, us, nullptr, tg, nullptr,
+                                                                                                   MppiLane{ac, ac});
+               });
+}
+
+// F16_FLAG_ONE_LANE: the lane bodies of k_rollout_exact (out-of-line steps, tables from global memory), which is what makes the call
+// equal the host loop bit for bit; 64, 128 or 256 lanes by K.
+template <int STAGES>
+__global__ __launch_bounds__(256) void k_rollout_mppi_exact(MppiArgs m) {
+  mppi_periods(m,
+               [&](const CostArgs &c, long b, long ac) { rollout_exact_lanes<false, true, true, STAGES>(c, MppiLane{b, ac}); },
+               [&](const SchedArgs &s, long ac) { rollout_exact_lanes<false, true, false, STAGES>(s, MppiLane{ac, ac}); });
 }
 
 // Four-wavefront rollout (latency regime, hifi): one workgroup = 64 aircraft on the four SIMDs of a CU; the state is
@@ -1237,6 +1296,56 @@ extern "C" int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long
   d.seq = u_seq; d.hold = hold; d.method = method;
   d.B0 = B0; d.ld0 = ld0; d.x_ref = x_ref; d.u_ref = u_ref; d.x_end = x_end; d.w = h_w;
   return plant_rollout<false, true, true>(ctx, d, stream);
+}
+
+// The closed MPPI loop as one launch (k_rollout_mppi): one workgroup per aircraft, K rounded up to 64, 128 or 256 lanes.
+extern "C" int f16_rollout_mppi(f16_ctx *ctx, double *x, double *u, double *u_nom, const double *dem, const double *u_ref,
+                                const f16_cost_weights *h_w, const double *h_sigma, double lambda, uint64_t seed, uint32_t period0,
+                                double *u_seq, double *cost, double *stats, double *traj, int32_t *status, long B0, long ld0, long K,
+                                long ld, int nperiods, int S, int hold, int traj_every, double dt, double xcg, int fi_flag, int method,
+                                unsigned flags, void *stream) {
+  if (!ctx || !x || !u || !u_nom || !dem || !h_w || !h_sigma || !u_seq || !cost)
+    return set_error(F16_EINVAL, "ctx / x / u / u_nom / dem / h_w / h_sigma / u_seq / cost is NULL");
+  if (K < 1 || K > 256) return set_error(F16_EINVAL, "K must be in 1..256: one workgroup holds an aircraft's samples");
+  if (B0 < 0 || ld0 < B0 || ld / K < B0) return set_error(F16_EINVAL, "bad argument (B0 < 0, ld0 < B0 or ld < K * B0)");
+  if (S < 1 || hold < 1 || nperiods < 0 || (long)S * hold > 0x7fffffffL) return set_error(F16_EINVAL, "S and hold must be >= 1, nperiods >= 0");
+  if (traj && (traj_every < 1 || hold % traj_every != 0)) return set_error(F16_EINVAL, "hold must be a multiple of traj_every >= 1 when traj is given");
+  if (!(lambda > 0.0) || !__builtin_isfinite(lambda)) return set_error(F16_EINVAL, "lambda must be finite and > 0");
+  for (int i = 0; i < 3; ++i)
+    if (!(h_sigma[i] >= 0.0) || !__builtin_isfinite(h_sigma[i])) return set_error(F16_EINVAL, "sigma must be finite and >= 0");
+  for (int k = 0; k < 22; ++k)
+    if (!(h_w->q[k] >= 0.0) || !__builtin_isfinite(h_w->q[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
+  if (method != F16_INT_EULER && method != F16_INT_RK4) return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
+  if (B0 == 0 || nperiods == 0) return F16_OK;
+  MppiArgs m{};
+  m.tab = ctx->d_tab; m.lofi = ctx->d_lofi; m.x = x; m.u = u; m.u_nom = u_nom; m.dem = dem; m.u_ref = u_ref; m.u_seq = u_seq; m.cost = cost;
+  m.stats = stats; m.traj = traj; m.status = status; m.B0 = B0; m.ld0 = ld0; m.K = K; m.ld = ld;
+  m.nperiods = nperiods; m.S = S; m.hold = hold; m.traj_every = traj ? traj_every : hold + 1;
+  m.dt = dt; m.xcg = xcg; m.lambda = lambda; m.sg[0] = h_sigma[0]; m.sg[1] = h_sigma[1]; m.sg[2] = h_sigma[2];
+  m.fi = fi_flag; m.flags = flags; m.key0 = (uint32_t)(seed & 0xffffffffu); m.key1 = (uint32_t)(seed >> 32); m.period0 = period0; m.w = *h_w;
+  const hipStream_t st = (hipStream_t)stream;
+  const int block = K <= 64 ? 64 : (K <= 128 ? 128 : 256);
+  if (flags & F16_FLAG_ONE_LANE) {
+    const dim3 grid((unsigned)(B0 < 65535 ? B0 : 65535));
+    if (method == F16_INT_RK4) hipLaunchKernelGGL((k_rollout_mppi_exact<4>), grid, dim3(block), 0, st, m);
+    else hipLaunchKernelGGL((k_rollout_mppi_exact<1>), grid, dim3(block), 0, st, m);
+    return hip_check(hipGetLastError(), "f16_rollout_mppi launch");
+  }
+  const dim3 grid((unsigned)(B0 < 256 ? B0 : 256));      // one workgroup per CU (the table image in LDS); the rest grid-stride
+  Geometry g{block, 0};
+  by_block(g, [&](auto blk) {
+    constexpr int BLOCK = decltype(blk)::value;
+    if constexpr (BLOCK <= 256) {
+      if (method == F16_INT_RK4) {
+        if (fi_flag == 0) hipLaunchKernelGGL((k_rollout_mppi<BLOCK, 0, 4>), grid, dim3(BLOCK), 0, st, m);
+        else hipLaunchKernelGGL((k_rollout_mppi<BLOCK, -1, 4>), grid, dim3(BLOCK), 0, st, m);
+      } else {
+        if (fi_flag == 0) hipLaunchKernelGGL((k_rollout_mppi<BLOCK, 0, 1>), grid, dim3(BLOCK), 0, st, m);
+        else hipLaunchKernelGGL((k_rollout_mppi<BLOCK, -1, 1>), grid, dim3(BLOCK), 0, st, m);
+      }
+    }
+  });
+  return hip_check(hipGetLastError(), "f16_rollout_mppi launch");
 }
 
 extern "C" int f16_rollout_lqr_linear(f16_ctx *ctx, double *x9, const double *Ad, const double *Bd, const double *K, const double *x_ref,

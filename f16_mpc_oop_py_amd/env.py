@@ -378,16 +378,94 @@ class F16Batch:
         out, _, stats = self._blend(cost, seq, K, lam)
         return out.permute(0, 2, 1), dict(cost=cost.view(K, self.B), min_cost=stats[0], ess=stats[1], status=st.view(K, self.B))
 
+    @staticmethod
+    def _sigma3(sigma):
+        """sigma, a scalar or the three surface deviations, as three host doubles (ctypes array)"""
+        s = np.asarray(sigma, dtype=np.float64)
+        if s.ndim > 1 or (s.ndim == 1 and s.shape[0] != 3):
+            raise ValueError(f"sigma is a scalar or the three surface deviations, not {tuple(s.shape)}")
+        return (ctypes.c_double * 3)(*np.broadcast_to(s, (3,)))
+
+    def _sample(self, nom, sg, K, seed, period):
+        """f16_mppi_sample: the nominal schedule nom [S, 4, B] (state-major, contiguous) -> the sample set [S, 4, K * B] of `period`"""
+        S, lanes = nom.shape[0], K * self.B
+        seq = torch.empty((S, 4, lanes), dtype=torch.float64, device=self.device)
+        self._check(self.lib.f16_mppi_sample(self.ctx.handle, _vp(nom), sg, int(seed), int(period), _vp(seq), lanes, lanes, self.B, self.B,
+                                             S, self._stream))
+        return seq
+
+    def sample_schedules(self, nominal, sigma, samples, seed, period):
+        """The sample set of one MPPI period by the library's own counter-based sampler (C-ABI f16_mppi_sample; the rule -- Philox4x32-10
+        with counter (period, row, sample, aircraft) and key `seed`, Box-Muller, clipping to the command limits -- is stated in
+        include/f16_hip.h and restated by mppi.sample_reference): nominal [S, B, 4], sigma a scalar or the three surface deviations
+        -> [S, K, B, 4] on the device.  The thrust command is the nominal one."""
+        nom = nominal if isinstance(nominal, torch.Tensor) else torch.as_tensor(np.asarray(nominal, dtype=np.float64))
+        if nom.dim() != 3 or tuple(nom.shape[1:]) != (self.B, 4) or nom.shape[0] < 1 or int(samples) < 1:
+            raise ValueError(f"nominal must be [S, {self.B}, 4] with S >= 1 and samples >= 1, not {tuple(nom.shape)}")
+        nom = nom.to(device=self.device, dtype=torch.float64).permute(0, 2, 1).contiguous()
+        seq = self._sample(nom, self._sigma3(sigma), int(samples), seed, period)
+        return seq.view(nom.shape[0], 4, int(samples), self.B).permute(0, 2, 3, 1)
+
+    def _rollout_MPPI_counter(self, periods, dem, horizon, hold, K, sigma, lam, seed, period0, traj_every, method, fused, weights):
+        """rollout_MPPI with sampler="counter": the host loop over the C-ABI entries f16_mppi_sample -> f16_rollout_cost(_rk) ->
+        f16_mppi_blend -> f16_rollout(_rk), or (fused) the ONE call f16_rollout_mppi that equals it."""
+        extra = set(weights) - {"q", "qf", "r", "penalty", "u_ref"}
+        if extra:
+            raise TypeError(f"unknown weights {sorted(extra)}")
+        sg = self._sigma3(sigma)
+        ur = None if weights.get("u_ref") is None else self._soa(weights["u_ref"], 3)
+        w = _lib.make_cost_weights(weights.get("q"), weights.get("qf"), weights.get("r"), weights.get("penalty", 0.0))
+        nom = self._u.unsqueeze(0).repeat(horizon, 1, 1)                       # [S, 4, B]
+        if fused:
+            lanes = K * self.B
+            seq = torch.empty((horizon, 4, lanes), dtype=torch.float64, device=self.device)
+            cost = torch.empty(lanes, dtype=torch.float64, device=self.device)
+            stats = torch.empty((periods, 2, self.B), dtype=torch.float64, device=self.device)
+            traj = self._samples(periods * hold, traj_every)
+            self._check(self.lib.f16_rollout_mppi(self.ctx.handle, _vp(self._x), _vp(self._u), _vp(nom), _vp(dem), _vp(ur), ctypes.byref(w), sg,
+                                                  float(lam), int(seed), int(period0), _vp(seq), _vp(cost), _vp(stats), _vp(traj),
+                                                  _vp(self.status), self.B, self.B, K, lanes, periods, horizon, hold, int(traj_every or 1),
+                                                  self.dt, self.xcg, self.fi_flag, int(method), self.flags, self._stream))
+            mins, ess = stats[:, 0], stats[:, 1]
+        else:
+            name = {v: k for k, v in _lib.INTEGRATORS.items()}[method]
+            trajs, mins, ess = [], [], []
+            for p in range(periods):
+                seq = self._sample(nom, sg, K, seed, int(period0) + p)
+                xr = self._x[P.mpc_x_idx].clone()
+                xr[4:7] = dem
+                cost, _, _, _ = self._score(seq, K, hold, None, xr, ur, w, None, False, method)
+                out, _, st = self._blend(cost, seq, K, lam)
+                self._u.copy_(out[0])
+                trajs.append(self.rollout(hold, traj_every=traj_every, method=name))
+                nom = torch.cat((out[1:], out[-1:]), 0)
+                mins.append(st[0])
+                ess.append(st[1])
+            traj = torch.cat(trajs, 0) if traj_every else None
+            mins, ess = torch.stack(mins), torch.stack(ess)
+        self.last_mppi = dict(nominal=nom.permute(0, 2, 1), cost=cost.view(K, self.B),
+                              samples=seq.view(horizon, 4, K, self.B).permute(0, 2, 3, 1))
+        return traj, dict(min_cost=mins, ess=ess)
+
     def rollout_MPPI(self, nsteps, p_dem, q_dem, r_dem, horizon, hold, samples, sigma, lam, seed=0, traj_every=None,
-                     return_info=False, method="euler", **weights):
-        """The closed MPPI loop as a host loop (fusing it into one launch is future work).  Per control period of `hold` plant steps:
+                     return_info=False, method="euler", sampler="torch", fused=False, period0=0, **weights):
+        """The closed MPPI loop.  Per control period of `hold` plant steps:
         noise = sigma * randn([horizon, samples, B, 3]) from a device torch.Generator seeded once with `seed`; calc_MPPI_action on
         the nominal schedule [horizon, B, 4] (at first the current u.values in every row); u.values = row 0 of the blend and
         `rollout(hold)`; the nominal becomes the blend shifted one row, its last row repeated.  nsteps must be a multiple of hold,
         hold of traj_every.  sigma: a scalar or the three surface deviations (deg).  x.values, u.values and status advance as under
         `rollout`.  Returns the samples [nsteps // traj_every, 18, B] (None without traj_every); with return_info also
-        dict(min_cost [periods, B], ess [periods, B]).  method="rk4": Runge-Kutta steps both in the scoring and in the plant advance."""
-        _lib.integrator(method)
+        dict(min_cost [periods, B], ess [periods, B]).  method="rk4": Runge-Kutta steps both in the scoring and in the plant advance.
+        sampler="torch" (the default) is that host loop.  sampler="counter" draws the noise with the library's own counter-based
+        sampler instead (sample_schedules: period p of the call uses the counter word period0 + p), as a host loop over the C-ABI
+        entries; with fused=True (sampler="counter", samples <= 256) the whole loop is ONE launch, f16_rollout_mppi, which equals
+        that host loop bit for bit under F16_FLAG_ONE_LANE.  Both counter forms leave `last_mppi` = dict(nominal [S, B, 4] the
+        shifted schedule, cost [K, B] and samples [S, K, B, 4] of the last period)."""
+        method_id = _lib.integrator(method)
+        if sampler not in ("torch", "counter"):
+            raise ValueError(f'sampler must be "torch" or "counter", not {sampler!r}')
+        if fused and (sampler != "counter" or int(samples) > 256):
+            raise ValueError('fused=True needs sampler="counter" and samples <= 256 (one workgroup holds an aircraft\'s samples)')
         nsteps, horizon, hold, samples = int(nsteps), int(horizon), int(hold), int(samples)
         if hold < 1 or horizon < 1 or samples < 1:
             raise ValueError("horizon, hold and samples must be >= 1")
@@ -400,6 +478,10 @@ class F16Batch:
         sig = torch.as_tensor(sigma, dtype=torch.float64, device=self.device)
         if sig.dim() > 1 or (sig.dim() == 1 and sig.shape[0] != 3):
             raise ValueError(f"sigma is a scalar or the three surface deviations, not {tuple(sig.shape)}")
+        if sampler == "counter":
+            traj, info = self._rollout_MPPI_counter(nsteps // hold, self._demands(p_dem, q_dem, r_dem), horizon, hold, samples, sigma, lam,
+                                                    seed, period0, traj_every, method_id, fused, weights)
+            return (traj, info) if return_info else traj
         g = torch.Generator(device=self.device)
         g.manual_seed(int(seed))
         nominal = self._u.t().unsqueeze(0).repeat(horizon, 1, 1)

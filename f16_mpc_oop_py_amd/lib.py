@@ -262,6 +262,12 @@ def load():
         L.f16_rollout_cost_rk.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
     if hasattr(L, "f16_mppi_blend"):         # (not part of the strict build, which holds the plant sources alone)
         L.f16_mppi_blend.argtypes = [vp, vp, vp, d, vp, vp, vp, l, l, l, l, i, vp]
+    if hasattr(L, "f16_mppi_sample"):        # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        u64, u32, d3 = ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(d)
+        L.f16_mppi_sample.argtypes = [vp, vp, d3, u64, u32, vp, l, l, l, l, i, vp]
+        L.f16_debug_philox.argtypes = [vp, vp, vp, l, vp]
+        L.f16_rollout_mppi.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(CostWeights), d3, d, u64, u32, vp, vp, vp, vp, vp,
+                                       l, l, l, l, i, i, i, i, d, d, i, i, u, vp]
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
     L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]

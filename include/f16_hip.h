@@ -265,6 +265,62 @@ int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long ld0, const
 int f16_mppi_blend(f16_ctx *ctx, const double *cost, const double *u_seq, double lambda,
                    double *u_blend, double *w_out, double *stats,
                    long B, long ld, long B0, long ld0, int nrows, void *stream);
+/* The SAMPLER of an MPPI step, defined by this library (not by a tensor library's generator): Philox4x32-10 plus Box-Muller.
+ *   Words.   (r0, r1, r2, r3) = Philox4x32-10(counter, key), counter = (period, row, sample k, aircraft a), each a uint32,
+ *     key = (seed & 0xffffffff, seed >> 32).  The round function is the published one (Salmon, Moraes, Dror, Shaw, SC'11): per round
+ *         (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0)),   M0 = 0xD2511F53, M1 = 0xCD9E8D57
+ *     (hi / lo: the halves of the 64-bit product), ten rounds, the key bumped by (0x9E3779B9, 0xBB67AE85) after each.  Known answers:
+ *         counter 00000000 x4, key 00000000 x2                               -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *         counter ffffffff x4, key ffffffff x2                               -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *         counter 243f6a88 85a308d3 13198a2e 03707344, key a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   Normals. U_i = (r_i + 0.5) * 2^-32 (never 0 or 1, so |n| <= 6.8);  n0 = sqrt(-2 ln U0) cos(2 pi U1),  n1 = sqrt(-2 ln U0) sin(2 pi U1),
+ *     n2 = sqrt(-2 ln U2) cos(2 pi U3): elevator, aileron, rudder in that order.
+ *   Sample.  Lane j = k * B0 + a, row s:  u_seq[s][0][j] = u_nom[s][0][a] (the thrust command is never perturbed),
+ *     u_seq[s][1 + i][j] = clip(u_nom[s][1 + i][a] + sigma[i] n_i, lo_i, hi_i) with the command limits of parameters.py:125-126
+ *     (+-25, +-21.5, +-30 deg) and np.clip's behaviour: a NaN nominal stays NaN.
+ * f16_mppi_sample writes rows 0..nrows-1 for counter word `period`: u_nom[nrows][4][ld0], u_seq[nrows][4][ld], B = K * B0 lanes;
+ * h_sigma: 3 values on the HOST, finite and >= 0.  F16_EINVAL: a NULL pointer, a bad sigma, B < 0, ld < B, nrows < 0, B0 < 1 while
+ * B > 0, B % B0 != 0, ld0 < B0.  B == 0 or nrows == 0 is a no-op.  Nothing is allocated.  f16_mpc_oop_py_amd/mppi.py
+ * `sample_reference` restates the rule in numpy.  The lane's row comes from ONE out-of-line device function, which the fused loop
+ * below calls too.
+ * f16_debug_philox (tests): the generator alone on n (counter, key) pairs given on the HOST -> h_out[n][4]; synchronous. */
+int f16_mppi_sample(f16_ctx *ctx, const double *u_nom, const double *h_sigma, uint64_t seed, uint32_t period, double *u_seq,
+                    long B, long ld, long B0, long ld0, int nrows, void *stream);
+int f16_debug_philox(f16_ctx *ctx, const uint32_t *h_ctr, const uint32_t *h_key, long n, uint32_t *h_out);
+/* The CLOSED MPPI LOOP with in-kernel sampling as ONE launch.  Per aircraft a and control period p = period0 .. period0 + nperiods - 1:
+ *   1. x_ref = the current x9 with entries 4..6 = dem (the convention of calc_MPPI_action);
+ *   2. the K sample rows u_seq[S][4][ld] by f16_mppi_sample's rule from u_nom, counter word period = p;
+ *   3. every sample scored over S * hold steps from the current state: f16_rollout_cost's formula, step rule, envelope freeze,
+ *      penalty and NaN behaviour (method F16_INT_RK4: f16_rollout_cost_rk's) -> cost[ld];
+ *   4. the blend by f16_mppi_blend's rule (minimum over the finite costs, k ascending in plain fp64, sample 0 when no cost is finite);
+ *   5. u[4][ld0] = row 0 of the blend;
+ *   6. the aircraft advances `hold` steps under u by f16_rollout's rules (f16_rollout_rk's): x[18][ld0] in place, the sticky
+ *      status[ld0] (may be NULL), traj (may be NULL) [nperiods * hold / traj_every][18][ld0] with hold % traj_every == 0;
+ *   7. u_nom[S][4][ld0] = the blend shifted by one row, its last row repeated.
+ * u_seq / cost are work buffers in the host loop's layout (lane k * B0 + a) and hold the LAST period's samples and costs on
+ * return; stats (may be NULL) [nperiods][2][ld0]: the minimum cost and the effective sample size of every period (f16_mppi_blend's).
+ * u_ref [3][ld0] may be NULL (= 0).  h_w, h_sigma: HOST.
+ * Mapping: one workgroup per aircraft, drawn grid-stride over B0; its lanes are the aircraft's K samples, 1 <= K <= 256, rounded up
+ * to 64, 128 or 256 lanes.  The table image is staged into LDS once per launch; sampling, scoring, blend, advance and shift are
+ * separated by workgroup barriers only: no waiting between workgroups, no counters.  The advance runs on one lane.
+ * Contracts.
+ *   Host-loop equality: under F16_FLAG_ONE_LANE the call equals the host loop  f16_mppi_sample -> f16_rollout_cost(_rk) ->
+ *     f16_mppi_blend -> u = row 0 -> f16_rollout(_rk) -> shift,  one round per period with the same flags, BIT FOR BIT, for both
+ *     integrators: x, u, u_nom, status, every traj sample, stats, and the last period's u_seq / cost.
+ *   Split calls: under that flag n periods followed by m periods with period0 + n equal n + m periods bit for bit; with
+ *     F16_INT_RK4 at every setting (nothing but the state is carried from step to step).
+ *   Batch independence: under that flag an aircraft's result does not depend on B0.
+ *   Default flags: the scoring runs the lane body of the 64 / 128 / 256-lane scored kernel (table image in LDS); results agree with
+ *     the flagged ones to the kernel-to-kernel band (1e-9 relative on the states; tests/test_gpu_mppi_loop.py).
+ * F16_EINVAL: a NULL pointer among ctx, x, u, u_nom, dem, h_w, h_sigma, u_seq, cost; K < 1 or K > 256; B0 < 0, ld0 < B0, ld < K * B0;
+ * S < 1, hold < 1, nperiods < 0; traj with traj_every < 1 or hold % traj_every != 0; lambda not finite or <= 0; a negative or
+ * non-finite sigma or weight; a method other than F16_INT_EULER / F16_INT_RK4.  B0 == 0 or nperiods == 0 is a no-op.  Nothing is
+ * allocated: the call can be captured into a graph.  K > 256 (several workgroups per aircraft) is out of scope. */
+int f16_rollout_mppi(f16_ctx *ctx, double *x, double *u, double *u_nom, const double *dem, const double *u_ref,
+                     const f16_cost_weights *h_w, const double *h_sigma, double lambda, uint64_t seed, uint32_t period0,
+                     double *u_seq, double *cost, double *stats, double *traj, int32_t *status,
+                     long B0, long ld0, long K, long ld, int nperiods, int S, int hold, int traj_every,
+                     double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
 /* The reference's LINEAR-model closed loops as ONE launch (9-state reduced model, 3 inputs; one lane per aircraft, its matrices in
  * registers):   per step   u = -K (x_ref - x) + u0,   x = Ad x + Bd u
  *   test_env_mk2.py:46-62 `LQR(linear=True)` (what main.py:35 runs): the frozen model ssr.Ad / ssr.Bd under env.py:360-371
