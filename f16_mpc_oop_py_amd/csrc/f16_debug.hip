@@ -10,11 +10,14 @@
 //                 bit for bit; the rollouts only show that through whole trajectories.
 //   k_dbg_pow     the atmosphere's exp(0.14 log tfac) as the device library composes it and as exp_k / log_k repeat it with
 //                 the constants in scalar registers, and qbar / ps of atmos_dev through either: the same bits.
+//   k_dbg_gain_lookup  the gain-schedule lookup over (h, V) of f16_rollout_lqr_gs (gain_lookup, f16_gain_sched.hpp) at given points:
+//                 the same bits as the host function and the numpy restatement.
 #include <hip/hip_runtime.h>
 
 #include "../../include/f16_hip.h"
 #include "f16_ctx.h"
 #include "f16_plant.hpp"
+#include "f16_gain_sched.hpp"
 
 namespace f16 {
 
@@ -113,9 +116,40 @@ __global__ __launch_bounds__(64) void k_dbg_pow(const double *__restrict__ alt, 
 }
 #endif
 
+// the gain-schedule lookup of the scheduled-gain rollouts (gain_lookup, f16_gain_sched.hpp) on its own: out [n][12]
+__global__ __launch_bounds__(64) void k_dbg_gain_lookup(f16_gain_grid g, const double *__restrict__ tab, const double *__restrict__ h,
+                                                        const double *__restrict__ v, double *__restrict__ out, long n) {
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double o[F16_GS_ENTRIES];
+    gain_lookup(g, tab, h[p], v[p], o);
+#pragma unroll
+    for (int e = 0; e < F16_GS_ENTRIES; ++e) out[p * F16_GS_ENTRIES + e] = o[e];
+  }
+}
+
 }  // namespace f16
 
 using namespace f16;
+
+extern "C" int f16_debug_gain_lookup(f16_ctx *ctx, const f16_gain_grid *g, const double *tab, const double *h_h, const double *h_v, long n,
+                                     double *h_out) {
+  if (!ctx || !tab || !h_h || !h_v || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_gain_lookup");
+  if (const char *bad = gain_grid_error(g)) return set_error(F16_EINVAL, bad);
+  if (n == 0) return F16_OK;
+  double *d = nullptr;
+  int rc;
+  if ((rc = hip_check(hipMalloc(&d, (2 + F16_GS_ENTRIES) * (size_t)n * sizeof(double)), "hipMalloc dbg gain lookup"))) return rc;
+  const size_t nb = (size_t)n * sizeof(double);
+  if (!(rc = hip_check(hipMemcpy(d, h_h, nb, hipMemcpyHostToDevice), "copy h")) &&
+      !(rc = hip_check(hipMemcpy(d + n, h_v, nb, hipMemcpyHostToDevice), "copy v"))) {
+    const long blocks = (n + 63) / 64;
+    hipLaunchKernelGGL(k_dbg_gain_lookup, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(64), 0, nullptr, *g, tab, d, d + n, d + 2 * n, n);
+    rc = hip_check(hipGetLastError(), "f16_debug_gain_lookup launch");
+    if (!rc) rc = hip_check(hipMemcpy(h_out, d + 2 * n, F16_GS_ENTRIES * nb, hipMemcpyDeviceToHost), "copy out");
+  }
+  (void)hipFree(d);
+  return rc;
+}
 
 extern "C" int f16_debug_table_lookup(f16_ctx *ctx, int tid, const double *h_alpha, const double *h_beta, const double *h_el,
                                       int n, double *h_out, int32_t *h_status) {

@@ -8,6 +8,8 @@
 //                         (F16_FLAG_ONE_LANE; the step the closed MPC loop f16_rollout_mpc takes)
 //   k_rollout / k_rollout_i / k_rollout_exact <..., STAGES = 4>  the scheduled rollouts with the classical Runge-Kutta step instead of
 //                         the Euler step (f16_rollout_rk, f16_rollout_lqr_rk, f16_rollout_cost_rk with F16_INT_RK4)
+//   k_rollout_gs / k_rollout_i_gs / k_rollout_exact_gs  the LQR loop with K[:, 4:7] and the offset u0[1:4] looked up in a gain table over
+//                         (altitude, airspeed) every gs_every steps (f16_rollout_lqr_gs; the rule: f16_gain_sched.hpp)
 //   k_rollout_mppi / k_rollout_mppi_exact  the closed MPPI loop -- sample, score, blend, advance, shift per control period -- as one
 //                         launch, one workgroup per aircraft, on the lane bodies of the scored and scheduled rollouts (f16_rollout_mppi)
 //   k_rollout_lqr_linear  test_env_mk2.py:46-62 / test_env.py:501-576: the linear-model LQR loops (f16_rollout_lqr_linear)
@@ -28,6 +30,7 @@
 #include "f16_plant.hpp"
 #include "f16_plant_quad.hpp"
 #include "f16_mppi.hpp"
+#include "f16_gain_sched.hpp"
 
 namespace f16 {
 
@@ -70,8 +73,20 @@ struct CostArgs : SchedArgs {
   long B0, ld0;
   f16_cost_weights w;
 };
+// The GS instantiations (f16_rollout_lqr_gs: LQR && SCHED && !COST) take K[i][4..6] and the offset u0[1..3] from a gain schedule over
+// (altitude, airspeed) instead of K / u rows 1..3: a fourth type, the three above stay what they are.  The grid travels by value
+// (scalar registers; nothing to allocate, so the call can be captured); the table is read from global memory through L2.
+struct GainSchedArgs : SchedArgs {
+  f16_gain_grid grid;
+  const double *gtab;   // [nh][nv][12]
+  int32_t *gs_out;      // [ld] or null: updates at which (h, V) lay outside the grid
+  int gs_every;         // steps between gain updates
+};
 template <bool SCHED, bool COST = false>
 using RolloutArgs = std::conditional_t<COST, CostArgs, std::conditional_t<SCHED, SchedArgs, DynArgs>>;
+// (an alias of its own: the kernels' mangled names spell RolloutArgs out, and they stay what they are)
+template <bool SCHED, bool COST, bool GS>
+using RolloutArgsGS = std::conditional_t<GS, GainSchedArgs, RolloutArgs<SCHED, COST>>;
 
 // parameters.py:135 / 198-210: x9 = x[3, 4, 7, 8, 9, 10, 11, 17, 16]
 F16_DEV double mpc_state(const double *x, int k) { return x[k < 2 ? 3 + k : (k < 7 ? 5 + k : 24 - k)]; }
@@ -217,6 +232,11 @@ constexpr bool INC_TRIG = false;
 // LANES: which lanes the calling thread rolls out, and where a scored lane finds its aircraft and its reference.  GridLanes: the
 // grid-stride loop of every k_rollout* kernel.  The fused MPPI loop (k_rollout_mppi) hands over the ONE lane of its thread instead
 // (MppiLane), whose reference is formed from the initial state and the demands rather than read from a.x_ref.
+// (GS) the schedule bookkeeping of a lane with two more counters: steps until the next gain update; updates outside the grid.  They
+// ride on the object the other instantiations have anyway -- a variable of their own there, even a dead one, was enough to make the
+// compiler order the operands of a scalar OR differently in existing kernels.
+template <int N, bool AHEAD>
+struct RowAheadGs : RowAhead<N, AHEAD> { int gs_left = 0, gs_cnt = 0; };
 struct GridLanes {
   F16_DEV long first(int block) const { return (long)blockIdx.x * block + threadIdx.x; }
   template <typename ARGS> F16_DEV long end(const ARGS &a) const { return a.B; }
@@ -234,11 +254,12 @@ struct MppiLane {
   F16_DEV double reference(const CostArgs &a, int k, const double *x, long c) const { return k >= 4 && k < 7 ? a.dem[(k - 4) * a.ld0 + c] : mpc_state(x, k); }
 };
 template <int BLOCK, int FI, typename TP, bool LQR = false, bool INCT = false, bool SCHED = false, bool COST = false, bool XRL = false,
-          int STAGES = 1, typename LANES = GridLanes>
-__device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
+          int STAGES = 1, typename LANES = GridLanes, bool GS = false>
+__device__ __forceinline__ void rollout_lanes(const RolloutArgsGS<SCHED, COST, GS> &a, TP T, double (*us)[BLOCK], double (*kq)[BLOCK] = nullptr,
                                               double (*tgs)[BLOCK] = nullptr, double (*xr)[BLOCK] = nullptr, const LANES lanes = {}) {
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   static_assert(STAGES == 1 || (STAGES == 4 && SCHED && !INCT), "the Runge-Kutta step: scheduled variants, exact sin / cos");
+  static_assert(!GS || (LQR && SCHED && !COST), "the gain schedule: the closed loop under a demand schedule");
   for (long b = lanes.first(BLOCK); b < lanes.end(a); b += lanes.stride(BLOCK)) {
     double x[18];
     long b0 = b;                                         // (COST) the aircraft of this lane: the column of x0 / x_ref / u_ref
@@ -265,10 +286,12 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
     }
     double ul[3] = {us[1][threadIdx.x], us[2][threadIdx.x], us[3][threadIdx.x]};   // (u_out of an aircraft that never steps: u0)
     if (LQR) {   // K[i][4..6] and the demands: lane-indexed LDS slots like the inputs (constant over the rollout, used once per step)
+      if constexpr (!GS) {                                 // (GS: the first gain update, at step 0, fills the nine slots)
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) kq[3 * i + j][threadIdx.x] = a.K[(9 * i + 4 + j) * a.ld + b];
+      }
 #pragma unroll
       for (int j = 0; j < 3; ++j) kq[9 + j][threadIdx.x] = a.dem[j * a.ld + b];
     }
@@ -281,11 +304,28 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
     constexpr int NR = LQR ? 3 : 4;
     // 64-lane workgroups (B <= 16,384) count the 32 steps between exact sin / cos evaluations from the start of the ROW, as the
     // chain of launches does for any hold; the larger ones from the start of the launch (the chain's steps when hold % 32 == 0)
-    constexpr bool ROW_TRIG = SCHED && INCT && BLOCK == 64;
+    // GS: every kernel that carries the pairs restarts them at every row AND at every gain update -- the segment starts of the chain
+    constexpr bool ROW_TRIG = SCHED && INCT && (BLOCK == 64 || GS);
     int t0 = 0;
-    RowAhead<NR, BLOCK <= 256> ra;
+    std::conditional_t<GS, RowAheadGs<NR, BLOCK <= 256>, RowAhead<NR, BLOCK <= 256>> ra;
     if constexpr (SCHED) { ra.init(a, NR, a.out + b); ra.settle(); }
     for (int t = 0; t < a.nsteps; ++t) {
+      // GS: a gain update at the state this step starts from, for frozen aircraft too.  The 48 corner values come from global
+      // memory (L2) as one batch of loads right here -- they depend on the state the previous step produced, so there is no
+      // earlier place for them -- and the install writes the slots the frozen-gain loop fills once: kq[0..8], us[1..3].
+      if constexpr (GS) {
+        if (ra.gs_left == 0) {
+          ra.gs_left = a.gs_every;
+          double g[F16_GS_ENTRIES];
+          ra.gs_cnt += gain_lookup(a.grid, a.gtab, x[2], x[6], g);
+#pragma unroll
+          for (int e = 0; e < 9; ++e) kq[e][threadIdx.x] = g[e];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) us[1 + i][threadIdx.x] = ul[i] = g[9 + i];      // (as a new launch: u0 until it steps)
+          if (ROW_TRIG) { t0 = t; stale = true; }
+        }
+        --ra.gs_left;
+      }
       // env.py:117-124: the reference exit()s; here the aircraft is frozen and flagged
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;
       if (!(st & ST_ENVELOPE)) {
@@ -356,6 +396,7 @@ __device__ __forceinline__ void rollout_lanes(const RolloutArgs<SCHED, COST> &a,
 #pragma unroll
       for (int i = 0; i < 3; ++i) a.u_out[(1 + i) * a.ld + b] = ul[i];
     }
+    if constexpr (GS) if (a.gs_out) a.gs_out[b] = ra.gs_cnt;
   }
 }
 
@@ -370,11 +411,18 @@ __global__ __launch_bounds__(64) void k_rollout_exact(RolloutArgs<SCHED, COST> a
   static_assert(!COST || (SCHED && !LQR), "the scored rollout is the open-loop scheduled one");
   static_assert(STAGES == 1 || (STAGES == 4 && SCHED), "the Runge-Kutta step: scheduled variants");
   const GridLanes lanes;
+  constexpr bool GS = false;
 #include "f16_rollout_exact.inc"
 }
-template <bool LQR, bool SCHED, bool COST, int STAGES, typename LANES>
-__device__ __forceinline__ void rollout_exact_lanes(const RolloutArgs<SCHED, COST> &a, const LANES lanes) {
+template <bool LQR, bool SCHED, bool COST, int STAGES, typename LANES, bool GS = false>
+__device__ __forceinline__ void rollout_exact_lanes(const RolloutArgsGS<SCHED, COST, GS> &a, const LANES lanes) {
 #include "f16_rollout_exact.inc"
+}
+// the scheduled-gain loop (f16_rollout_lqr_gs) under the flag: the same lane loop with the gain update in it.  A kernel of its own
+// (as k_rollout_gs / k_rollout_i_gs below), so that every existing kernel keeps its name and its argument block.
+template <int STAGES>
+__global__ __launch_bounds__(64) void k_rollout_exact_gs(GainSchedArgs a) {
+  rollout_exact_lanes<true, true, false, STAGES, GridLanes, true>(a, GridLanes{});
 }
 
 template <int BLOCK, int FI, bool LQR = false, bool SCHED = false, bool COST = false, int STAGES = 1>
@@ -415,6 +463,35 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_i(RolloutArgs<SCHED, COST> a)
   }
   rollout_lanes<BLOCK, 1, TabI32, LQR, INCT, SCHED, COST, COST, STAGES>(a, TabI32{tab}, us, reinterpret_cast<double (*)[BLOCK]>(kq),
                                                                 reinterpret_cast<double (*)[BLOCK]>(tgs), reinterpret_cast<double (*)[BLOCK]>(xr));
+}
+
+// The scheduled-gain twins of k_rollout<BLOCK, FI, true, true, false, STAGES> and k_rollout_i<BLOCK, true, true, false, STAGES>: the same
+// LDS slots (the install of a gain update writes kq[0..8] and us[1..3]: no new slot), the same lane body with GS = true.
+template <int BLOCK, int FI, int STAGES = 1>
+__global__ __launch_bounds__(BLOCK) void k_rollout_gs(GainSchedArgs a) {
+  __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
+  __shared__ double us[4][BLOCK];
+  __shared__ double kq[12][BLOCK];
+  constexpr bool INCT = INC_TRIG && STAGES == 1 && BLOCK < 256;      // (as k_rollout under the LQR law)
+  __shared__ double tgs[INCT ? 10 : 1][INCT ? BLOCK : 1];
+  static_assert(BLOCK <= 256 && sizeof(tab) + sizeof(us) + sizeof(kq) + sizeof(tgs) <= 163840, "static LDS of a CU");
+  if (a.fi == 1) stage_tables(tab, a.tab);
+  rollout_lanes<BLOCK, FI, const double *, true, INCT, true, false, false, STAGES, GridLanes, true>(
+      a, (const double *)tab, us, kq, reinterpret_cast<double (*)[BLOCK]>(tgs));
+}
+template <int BLOCK, int STAGES = 1>
+__global__ __launch_bounds__(BLOCK) void k_rollout_i_gs(GainSchedArgs a) {
+  __shared__ __attribute__((aligned(16))) int tab[i32::IMAGE_INTS];
+  __shared__ double us[4][BLOCK];
+  __shared__ double kq[12][BLOCK];
+  static_assert(sizeof(tab) + sizeof(us) + sizeof(kq) <= 163840, "static LDS of a CU");
+  {
+    const int4 *src = reinterpret_cast<const int4 *>(a.tab32);
+    int4 *dst = reinterpret_cast<int4 *>(tab);
+    for (int i = threadIdx.x; i < i32::IMAGE_INTS / 4; i += BLOCK) dst[i] = src[i];
+    __syncthreads();
+  }
+  rollout_lanes<BLOCK, 1, TabI32, true, false, true, false, false, STAGES, GridLanes, true>(a, TabI32{tab}, us, kq);
 }
 
 // The closed MPPI loop as ONE launch (f16_rollout_mppi): one workgroup = one aircraft, its lanes = that aircraft's K samples
@@ -1104,8 +1181,10 @@ constexpr bool RK4_512 = true;      // (resource table only: instantiate and rou
 #else
 constexpr bool RK4_512 = false;
 #endif
-template <bool LQR, bool SCHED, bool COST, int STAGES = 1>
-static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *stream) {
+// GS = true (f16_rollout_lqr_gs): the same rules without the quad and four-wave branches, as for COST and STAGES = 4 (a scheduled-gain
+// twin of the role-wave kernels is out of scope), on the kernels k_rollout_gs / k_rollout_i_gs / k_rollout_exact_gs.
+template <bool LQR, bool SCHED, bool COST, int STAGES = 1, bool GS = false>
+static int rollout_dispatch(f16_ctx *ctx, RolloutArgsGS<SCHED, COST, GS> &a, void *stream) {
   const hipStream_t st = (hipStream_t)stream;
   const long B = a.B;
   const bool hifi = a.fi == 1;
@@ -1115,10 +1194,12 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *str
   if (a.flags & F16_FLAG_ONE_LANE) {
     // results independent of the batch size: ONE kernel for every B, its step an out-of-line function (k_rollout_exact)
     const long blocks = (B + 63) / 64;
+    if constexpr (GS) hipLaunchKernelGGL((k_rollout_exact_gs<STAGES>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    else
     hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST, STAGES>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
     return hip_check(hipGetLastError(), what);
   }
-  if constexpr (!COST && STAGES == 1) {
+  if constexpr (!COST && STAGES == 1 && !GS) {
     if (hifi && B <= 2 * maxq) {
       // four lanes per aircraft.  At most 16 aircraft per CU: one 16-aircraft workgroup per CU; at most 32: two 16-aircraft
       // groups per workgroup
@@ -1145,6 +1226,8 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *str
   static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();
   if constexpr (WIDE) if (hifi && use_i32 && g.block == 512) {
     a.tab32 = ctx->d_tab32;
+    if constexpr (GS) hipLaunchKernelGGL((k_rollout_i_gs<512, STAGES>), dim3(g.grid), dim3(512), 0, st, a);
+    else
     hipLaunchKernelGGL((k_rollout_i<512, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(512), 0, st, a);
     return hip_check(hipGetLastError(), what);
   }
@@ -1152,6 +1235,10 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgs<SCHED, COST> &a, void *str
   if (LQR && g.block == 512) g.block = 256;  // (fp64 image + 16 slots of 512 lanes would not fit the 160 KB of a CU)
   by_block(g, [&](auto block) {
     constexpr int BLOCK = decltype(block)::value;
+    if constexpr (GS && BLOCK < 512) {
+      if (a.fi == 0) hipLaunchKernelGGL((k_rollout_gs<BLOCK, 0, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+      else hipLaunchKernelGGL((k_rollout_gs<BLOCK, -1, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
+    } else
     if constexpr (!((LQR || !WIDE) && BLOCK == 512)) {    // (never reached, and not instantiated)
       if (a.fi == 0) hipLaunchKernelGGL((k_rollout<BLOCK, 0, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
       else hipLaunchKernelGGL((k_rollout<BLOCK, -1, LQR, SCHED, COST, STAGES>), dim3(g.grid), dim3(BLOCK), 0, st, a);
@@ -1193,11 +1280,16 @@ struct PlantRollout {
   double *x_end = nullptr;
   const f16_cost_weights *w = nullptr;
   int method = F16_INT_EULER;          // the step rule: F16_INT_EULER, or (SCHED entry points f16_rollout*_rk) F16_INT_RK4
+  // GS: the gain schedule in place of K and of rows 1..3 of u
+  const f16_gain_grid *grid = nullptr;
+  const double *gtab = nullptr;
+  int gs_every = 1;
+  int32_t *gs_out = nullptr;
 };
 
-template <bool LQR, bool SCHED, bool COST>
+template <bool LQR, bool SCHED, bool COST, bool GS = false>
 static int plant_rollout(f16_ctx *ctx, const PlantRollout &d, void *stream) {
-  if ((SCHED && !d.seq) || (LQR && (!d.K || !d.dem)) || (COST && (!d.x_ref || !d.w || !d.out))) return set_error(F16_EINVAL, d.missing);
+  if ((SCHED && !d.seq) || (LQR && ((!GS && !d.K) || !d.dem)) || (COST && (!d.x_ref || !d.w || !d.out))) return set_error(F16_EINVAL, d.missing);
   if (int rc = check_rollout(ctx, d.x, d.u, d.traj, d.B, d.ld, d.nsteps, d.traj_every)) return rc;
   if (d.hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
   if constexpr (COST) {
@@ -1208,18 +1300,24 @@ static int plant_rollout(f16_ctx *ctx, const PlantRollout &d, void *stream) {
     for (int k = 0; k < 22; ++k)
       if (!(w[k] >= 0.0) || !__builtin_isfinite(w[k])) return set_error(F16_EINVAL, "cost weights must be finite and >= 0");
   }
+  if constexpr (GS) {
+    if (!d.gtab) return set_error(F16_EINVAL, "tab is NULL");
+    if (const char *bad = gain_grid_error(d.grid)) return set_error(F16_EINVAL, bad);
+    if (d.gs_every < 1) return set_error(F16_EINVAL, "gs_every must be >= 1");
+  }
   if (d.method != F16_INT_EULER && !(SCHED && d.method == F16_INT_RK4))
     return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
   // nothing to step; the scored call still launches for nsteps = 0: its cost is then the terminal term
   if (d.B == 0 || (!COST && d.nsteps == 0)) return F16_OK;
-  auto a = base_args<RolloutArgs<SCHED, COST>>(ctx, d.B, d.ld, d.xcg, d.fi, d.flags, d.status);
+  auto a = base_args<RolloutArgsGS<SCHED, COST, GS>>(ctx, d.B, d.ld, d.xcg, d.fi, d.flags, d.status);
   a.u = d.u; a.out = d.out; a.traj = d.traj;
   a.nsteps = d.nsteps; a.traj_every = d.traj ? d.traj_every : d.nsteps + 1; a.dt = d.dt;
   a.K = d.K; a.dem = d.dem; a.u_out = d.u_out;
   if constexpr (SCHED) { a.seq = d.seq; a.hold = d.hold; a.nrows = d.nsteps > 0 ? (d.nsteps - 1) / d.hold + 1 : 0; }
   if constexpr (COST) { a.x0 = d.x; a.x_ref = d.x_ref; a.u_ref = d.u_ref; a.x_end = d.x_end; a.B0 = d.B0; a.ld0 = d.ld0; a.w = *d.w; }
-  if constexpr (SCHED) if (d.method == F16_INT_RK4) return rollout_dispatch<LQR, SCHED, COST, 4>(ctx, a, stream);
-  return rollout_dispatch<LQR, SCHED, COST>(ctx, a, stream);
+  if constexpr (GS) { a.grid = *d.grid; a.gtab = d.gtab; a.gs_every = d.gs_every; a.gs_out = d.gs_out; }
+  if constexpr (SCHED) if (d.method == F16_INT_RK4) return rollout_dispatch<LQR, SCHED, COST, 4, GS>(ctx, a, stream);
+  return rollout_dispatch<LQR, SCHED, COST, 1, GS>(ctx, a, stream);
 }
 
 // The entry points: each states what distinguishes it.
@@ -1296,6 +1394,25 @@ extern "C" int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long
   d.seq = u_seq; d.hold = hold; d.method = method;
   d.B0 = B0; d.ld0 = ld0; d.x_ref = x_ref; d.u_ref = u_ref; d.x_end = x_end; d.w = h_w;
   return plant_rollout<false, true, true>(ctx, d, stream);
+}
+
+// The LQR loop under a gain schedule over (h, V) (include/f16_hip.h): f16_rollout_lqr_rk's checks in its order, then the schedule's,
+// the method last; both methods run the GS kernels (there is no older call to forward Euler to).
+extern "C" int f16_rollout_lqr_gs(f16_ctx *ctx, double *x, const double *u0, const f16_gain_grid *h_grid, const double *tab, int gs_every,
+                                  const double *dem_seq, double *traj, double *u_out, int32_t *gs_out, int32_t *status, long B, long ld,
+                                  int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags,
+                                  void *stream) {
+  PlantRollout d{"dem_seq is NULL", x, u0, x, traj, status, B, ld, nsteps, traj_every, dt, xcg, fi_flag, flags};
+  d.seq = dem_seq; d.hold = hold; d.dem = dem_seq; d.u_out = u_out; d.method = method;
+  d.grid = h_grid; d.gtab = tab; d.gs_every = gs_every; d.gs_out = gs_out;
+  return plant_rollout<true, true, false, true>(ctx, d, stream);
+}
+
+extern "C" int f16_gain_lookup_host(const f16_gain_grid *g, const double *h_tab, double h, double v, double *h_out12) {
+  if (const char *bad = gain_grid_error(g)) return set_error(F16_EINVAL, bad);
+  if (!h_tab || !h_out12) return set_error(F16_EINVAL, "h_tab / h_out12 is NULL");
+  gain_lookup(*g, h_tab, h, v, h_out12);
+  return F16_OK;
 }
 
 // The closed MPPI loop as one launch (k_rollout_mppi): one workgroup per aircraft, K rounded up to 64, 128 or 256 lanes.

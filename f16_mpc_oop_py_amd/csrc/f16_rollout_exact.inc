@@ -1,7 +1,8 @@
 // f16_rollout_exact.inc -- the lane loop of the F16_FLAG_ONE_LANE rollouts, included once in the kernel k_rollout_exact (whose
 // argument block it reads in place, as it always did) and once in rollout_exact_lanes, the device function through which the fused
 // MPPI loop (k_rollout_mppi_exact) runs the same statements on the one lane of each thread.  Expects: a (RolloutArgs<SCHED, COST>),
-// lanes (GridLanes / MppiLane), and the template parameters LQR, SCHED, COST, STAGES of the including function.
+// lanes (GridLanes / MppiLane), and the template parameters LQR, SCHED, COST, STAGES of the including function, and GS (the gain
+// schedule of f16_rollout_lqr_gs: a (GainSchedArgs); false in the kernel k_rollout_exact).
   for (long b = lanes.first(64); b < lanes.end(a); b += lanes.stride(64)) {
     double x[18], u[4];
     long b0 = b;                                         // (COST: as in rollout_lanes; the reference in registers)
@@ -24,10 +25,12 @@
     if constexpr (COST) if (a.nsteps > 0) ju = cost_command_term(a, b0, u[1], u[2], u[3]);
     double kq[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, u0[3] = {u[1], u[2], u[3]};
     if (LQR) {
+      if constexpr (!GS) {                                 // (GS: the first gain update, at step 0, fills the nine)
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) kq[3 * i + j] = a.K[(9 * i + 4 + j) * a.ld + b];
+      }
 #pragma unroll
       for (int j = 0; j < 3; ++j) kq[9 + j] = a.dem[j * a.ld + b];
     }
@@ -37,7 +40,20 @@
     constexpr int NR = LQR ? 3 : 4;
     RowAhead<NR> ra;
     if constexpr (SCHED) { ra.init(a, NR, a.out + b); ra.settle(); }
+    [[maybe_unused]] int gs_left = 0, gs_cnt = 0;         // (GS: as in rollout_lanes)
     for (int t = 0; t < a.nsteps; ++t) {
+      if constexpr (GS) {                                  // a gain update at the state this step starts from, frozen or not
+        if (gs_left == 0) {
+          gs_left = a.gs_every;
+          double g[F16_GS_ENTRIES];
+          gs_cnt += gain_lookup(a.grid, a.gtab, x[2], x[6], g);
+#pragma unroll
+          for (int e = 0; e < 9; ++e) kq[e] = g[e];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) u0[i] = u[1 + i] = g[9 + i];      // (as a new launch: u0 until it steps)
+        }
+        --gs_left;
+      }
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;      // env.py:117-124
       if (!(st & ST_ENVELOPE)) {
         if (LQR) {
@@ -84,4 +100,5 @@
 #pragma unroll
       for (int i = 0; i < 4; ++i) a.u_out[i * a.ld + b] = u[i];
     }
+    if constexpr (GS) if (a.gs_out) a.gs_out[b] = gs_cnt;
   }

@@ -685,7 +685,7 @@ class F16Batch:
         return seq.contiguous(), k
 
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
-                    R=None, hold=None, method="euler"):
+                    R=None, hold=None, method="euler", schedule=None, gains_every=1, return_info=False):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -704,7 +704,19 @@ class F16Batch:
         relinearise=True (ValueError).  Scalar / [B] demands call f16_rollout_lqr exactly as before; hold is then not taken.
         method="rk4" (the frozen-gain nonlinear loop only; ValueError with linear=True or relinearise=True, whose kernels step with
         the Euler step): Runge-Kutta steps, the action formed from the state at the start of a step and held over its four stages
-        (f16_rollout_lqr_rk; constant demands are one row held for every step)."""
+        (f16_rollout_lqr_rk; constant demands are one row held for every step).
+        schedule=gs (a schedule.GainSchedule), gains_every=k: the same nonlinear loop with K[:, 4:7] and the offset u0[1:] looked up
+        in the gain table at the altitude and airspeed of the state at the start of every k-th step and held in between, in one
+        launch of f16_rollout_lqr_gs, for both methods; the thrust command is held.  Not combined with K, linear=True or
+        relinearise=True, and gains_every >= 1 (ValueError).  return_info=True (with a schedule) returns (traj, info) with
+        info["gs_out"] [B]: at how many gain updates the aircraft was outside the table's grid (the edge cell is extended flat there)."""
+        if schedule is not None:
+            if K is not None or linear or relinearise:
+                raise ValueError("schedule= takes the gain from the table: not combined with K, linear=True or relinearise=True")
+            if int(gains_every) < 1:
+                raise ValueError(f"gains_every must be >= 1 (got {gains_every})")
+        elif return_info or gains_every != 1:
+            raise ValueError("gains_every and return_info go with schedule=")
         method = _lib.integrator(method, rk4=not (linear or relinearise))
         dem_seq = self._demand_schedule(p_dem, q_dem, r_dem)
         if dem_seq is not None:
@@ -725,6 +737,18 @@ class F16Batch:
             traj = self._rollout_relin(nsteps, xref, 0x70, u03.contiguous(), _lib.make_weights(Q=Q, R=R), 1e-5, k,
                                        bool(traj_every), False, False)[0]
             return traj
+        if schedule is not None:
+            nsteps = int(nsteps)
+            u0s = torch.cat((self._u[0:1], self._u_init[1:4]), 0).contiguous() if u0 is None else self._soa(u0, 4)
+            rows, held = (self._demands(p_dem, q_dem, r_dem), max(nsteps, 1)) if dem_seq is None else (dem_seq, hold)
+            traj = self._samples(nsteps, traj_every)
+            gs_out = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            grid, tab = schedule.grid(), schedule.device_table(self.device)
+            self._check(self.lib.f16_rollout_lqr_gs(self.ctx.handle, _vp(self._x), _vp(u0s), ctypes.byref(grid), _vp(tab), int(gains_every),
+                                                    _vp(rows), _vp(traj), _vp(self._u), _vp(gs_out), _vp(self.status), self.B, self.B,
+                                                    nsteps, held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag, int(method),
+                                                    self.flags, self._stream))
+            return (traj, dict(gs_out=gs_out)) if return_info else traj
         if K is None:
             K = self._calc_LQR_gain()
         Ks = torch.as_tensor(K, device=self.device, dtype=torch.float64).reshape(self.B, 27).t().contiguous()

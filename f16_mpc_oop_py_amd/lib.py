@@ -73,6 +73,15 @@ class CostWeights(ctypes.Structure):
     _fields_ = [("q", ctypes.c_double * 9), ("qf", ctypes.c_double * 9), ("r", ctypes.c_double * 3), ("pen", ctypes.c_double)]
 
 
+class GainGrid(ctypes.Structure):
+    """include/f16_hip.h `f16_gain_grid`: the uniform (altitude, airspeed) grid of a gain schedule (nh, nv >= 2; dh, dv > 0)."""
+    _fields_ = [("h0", ctypes.c_double), ("dh", ctypes.c_double), ("v0", ctypes.c_double), ("dv", ctypes.c_double),
+                ("nh", ctypes.c_int), ("nv", ctypes.c_int)]
+
+
+F16_GS_ENTRIES = 12            # doubles per node of a gain table: K[i][4 + j] at 3 i + j, the trim surface commands at 9 + i
+
+
 def make_cost_weights(q=None, qf=None, r=None, penalty=0.0):
     """CostWeights with the defaults q = qf = ones(9), r = ones(3): the diagonals of the reference's Q = Cd'Cd (Cd = I9) and R = I3."""
     import numpy as np
@@ -260,6 +269,11 @@ def load():
         L.f16_rollout_rk.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
         L.f16_rollout_lqr_rk.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
         L.f16_rollout_cost_rk.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
+    if hasattr(L, "f16_rollout_lqr_gs"):     # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        gp = ctypes.POINTER(GainGrid)
+        L.f16_gain_lookup_host.argtypes = [gp, vp, d, d, vp]
+        L.f16_debug_gain_lookup.argtypes = [vp, gp, vp, vp, vp, l, vp]
+        L.f16_rollout_lqr_gs.argtypes = [vp, vp, vp, gp, vp, i, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
     if hasattr(L, "f16_mppi_blend"):         # (not part of the strict build, which holds the plant sources alone)
         L.f16_mppi_blend.argtypes = [vp, vp, vp, d, vp, vp, vp, l, l, l, l, i, vp]
     if hasattr(L, "f16_mppi_sample"):        # (absent from an older library loaded through F16HIP_SO for an A/B run)

@@ -254,6 +254,69 @@ int f16_rollout_cost_rk(f16_ctx *ctx, const double *x0, long B0, long ld0, const
                         double *cost, double *x_end, double *traj, int32_t *status,
                         long B, long ld, int nsteps, int hold, int traj_every,
                         double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
+/* The LQR loop under a GAIN SCHEDULE over (altitude, airspeed), as ONE launch: between the frozen gain of f16_rollout_lqr*
+ * (valid near the trim point it was derived at) and the gain re-derived at every step (f16_rollout_lqr_relin: linearise -> ZOH ->
+ * DARE per step) stands flight-control practice -- a gain table derived once over a grid of flight conditions (one batch through
+ * f16_trim_batch -> f16_linearise_batch -> f16_c2d_batch -> f16_lqr_batch_w, one aircraft per node) and interpolated on the measured
+ * altitude and airspeed while flying.
+ *   The table.  tab[nh][nv][F16_GS_ENTRIES] doubles, row-major, node (ih, iv) at (ih * nv + iv) * 12 + e, on the uniform grid
+ *     h0 + ih dh, v0 + iv dv (nh, nv >= 2; dh, dv > 0).  Entry 3 i + j = K[i][4 + j], K as the reference holds it (K = -dlqr,
+ *     f16_lqr_batch's output; the law reads nothing else of K); entry 9 + i = the trim surface command u_trim[1 + i].
+ *   The lookup rule, for altitude h = x[2] and airspeed V = x[6]:
+ *         th = (h - h0) / dh;   ih = (int) fmin(fmax(floor(th), 0), nh - 2);   lh = fmin(fmax(th - ih, 0), 1)
+ *         tv, iv, lv            the same from V, v0, dv, nv
+ *         a = G[ih][iv][e]   + lv * (G[ih][iv+1][e]   - G[ih][iv][e])
+ *         b = G[ih+1][iv][e] + lv * (G[ih+1][iv+1][e] - G[ih+1][iv][e])
+ *         g[e] = a + lh * (b - a)
+ *     where a lerp p + l * (q - p) with l = 1 (the last node of an axis and everything beyond it) takes q itself -- p + (q - p) need
+ *     not round to q, and the properties below are meant to hold at that edge too;
+ *     every operation rounded on its own (IEEE division, no FMA contraction), so the host function, the device and the numpy
+ *     restatement (f16_mpc_oop_py_amd/schedule.py GainSchedule.lookup) give the same bits.  Outside the grid the edge cell is
+ *     extended flat: a clamp, NOT an extrapolation.  A NaN coordinate takes index 0 with weight 0 (fmax(NaN, 0) = 0).  At a node the
+ *     node's values come back exactly; a table of equal nodes returns them exactly.  The rule is written once
+ *     (csrc/f16_gain_sched.hpp) for the three users: the rollout kernels, f16_gain_lookup_host (pure host code: no context, no
+ *     GPU; h_tab on the host) and f16_debug_gain_lookup (tests: DEVICE table, n points and n x 12 results on the HOST; synchronous).
+ *   f16_rollout_lqr_gs is f16_rollout_lqr_rk with the per-aircraft K replaced by the schedule:
+ *     at every step t with t % gs_every == 0 the 12 values g are looked up at the state at the START of that step -- for frozen
+ *     aircraft too, at their frozen state -- and held until the next update; until then the law of env.py:360-371 runs with
+ *     K[i][4..6] = g[3 i .. 3 i + 2] and the offset u0[1 + i] = g[9 + i].  The thrust command u0[0][b] is held throughout (the
+ *     reference's LQR never commands thrust).
+ *     u0[4][ld]: row 0 is the thrust command; ROWS 1..3 ARE NOT READ -- the offset comes from the schedule.
+ *     h_grid: HOST, travels by value in the kernel argument block; tab: DEVICE, read through L2 (at 32 x 32 nodes 98 KB).
+ *     gs_out[ld] (may be NULL): the number of gain updates of this call at which (h, V) lay outside
+ *     [h0, h0 + (nh-1) dh] x [v0, v0 + (nv-1) dv] (th < 0 or th > nh - 1, likewise tv) or was not finite.  The loop does not stop
+ *     there and no status bit is set: the count is how a caller learns that the schedule was left.
+ *     Everything else is f16_rollout_lqr_rk's: dem_seq, hold, traj, traj_every, the envelope freeze, the sticky status bits, the
+ *     flags, method = F16_INT_EULER or F16_INT_RK4 (the action held over the four stages), the NaN rules.  Nothing is allocated:
+ *     the call can be captured into a graph.
+ *   F16_EINVAL, in the order of the call it extends: everything f16_rollout_lqr_rk refuses but the method (its "K / dem_seq is NULL"
+ *     reads "dem_seq is NULL"); a NULL h_grid or tab; nh < 2 or nv < 2; a non-finite or non-positive dh or dv, a non-finite h0 or v0;
+ *     gs_every < 1; the method last.  B == 0 (and nsteps == 0) is a no-op.
+ *   Contract (the chain).  Split the steps wherever t % gs_every == 0 or t % hold == 0.  The call equals the chain of
+ *     f16_rollout_lqr_rk calls, one per segment, each with that segment's demand row and with K and u0 = [thrust, g[9..11]] from the
+ *     most recent gain update as f16_gain_lookup_host computes it from the chain's own state, BIT FOR BIT in the final state, the
+ *     status, every stored sample and u_out (what the chain's last call reports): under F16_FLAG_ONE_LANE for both methods and every
+ *     B; with F16_INT_RK4 at every size and any segmentation; for lofi at every size and for hifi above 16,384 aircraft with Euler
+ *     when every segment length is a multiple of 32 (the Euler kernels that carry their sin / cos pairs restart them at every
+ *     segment start, as the chain's launches do).  A table of identical nodes gives f16_rollout_lqr_rk's own bits wherever both run
+ *     the same kernel and restart their carried pairs at the same steps (RK4 and F16_FLAG_ONE_LANE: always).  gs_every >= nsteps is
+ *     one update at step 0; n steps followed by m steps equal n + m steps where n % gs_every == 0 and n % hold == 0, under the
+ *     conditions of the chain.
+ *   Launch rules: the one-lane-per-aircraft kernels at every size (64 / 128 / 256 lanes per workgroup, 512 on the integer table
+ *     image; RK4: at most 256), the single kernel of F16_FLAG_ONE_LANE under the flag -- f16_rollout_lqr_rk's rules without the
+ *     four-lanes-per-aircraft and four-wavefront branches.  For hifi batches of at most 16,384 aircraft this is a different, slower
+ *     kernel than the one f16_rollout_lqr runs (same terms, ulp-level differences).
+ *   OUT OF SCOPE: a scheduled-gain twin of those role-wave kernels; a schedule on anything other than (h, V); scheduled thrust;
+ *     extrapolation beyond the grid. */
+#define F16_GS_ENTRIES 12
+typedef struct f16_gain_grid { double h0, dh, v0, dv; int nh, nv; } f16_gain_grid;   /* host; uniform grid, nh, nv >= 2, dh, dv > 0 and finite */
+int f16_gain_lookup_host(const f16_gain_grid *g, const double *h_tab, double h, double v, double *h_out12);
+int f16_debug_gain_lookup(f16_ctx *ctx, const f16_gain_grid *g, const double *tab, const double *h_h, const double *h_v, long n,
+                          double *h_out);
+int f16_rollout_lqr_gs(f16_ctx *ctx, double *x, const double *u0, const f16_gain_grid *h_grid, const double *tab, int gs_every,
+                       const double *dem_seq, double *traj, double *u_out, int32_t *gs_out, int32_t *status, long B, long ld,
+                       int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags,
+                       void *stream);
 /* The softmin blend of an MPPI step over the costs f16_rollout_cost wrote.  For aircraft a and its samples k = 0..K-1 (K = B / B0) at
  * lanes k * B0 + a:  m = the minimum over the FINITE cost,  w_k = exp(-(J_k - m) / lambda) for finite J_k and 0 otherwise,
  *     u_blend[nrows][4][ld0] = sum_k w_k u_seq[row][c][k * B0 + a] / sum_k w_k        (all four commands; u_seq[nrows][4][ld])
