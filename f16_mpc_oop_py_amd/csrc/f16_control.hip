@@ -1006,7 +1006,9 @@ static f16_ctx::sched_entry *mpc_sched_entry(f16_ctx *ctx, void *stream, long B,
 
 // The solve behind a build: one wavefront per aircraft where that solver applies (k_mpc_fast then only equilibrates, mode 3),
 // else the 512-lane workgroup per aircraft.  F16_MPC_WAVE=0 keeps the latter everywhere (A/B runs, cross-checks).
-static int mpc_solve_dispatch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
+static int mpc_solve_dispatch(f16_ctx *ctx, const MpcArgs &a, void *stream, const double *soft6 = nullptr) {
+  if (soft6 && !(a.mode == 0 && mpc_wave_enabled(a)))
+    return set_error(F16_EINVAL, "soft state rows run on the one-wavefront solver only (hzn <= 30, scaling > 0, max_iter > 0)");
   if (a.mode == 0 && mpc_wave_enabled(a)) {
     static const bool ruiz_outside = [] { const char *e = getenv("F16_WAVE_RUIZ"); return e && e[0] == '0'; }();
     MpcArgs w = a;
@@ -1016,7 +1018,7 @@ static int mpc_solve_dispatch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
       e.mode = 3; e.order = nullptr; e.iters_out = nullptr; e.warm = nullptr;
       if (int rc = mpc_fast_solve_launch(ctx, e, stream)) return rc;
     }
-    return mpc_wave_solve_launch(ctx, w, stream);
+    return mpc_wave_solve_launch(ctx, w, stream, soft6);
   }
   return mpc_fast_solve_launch(ctx, a, stream);
 }
@@ -1037,7 +1039,8 @@ static int mpc_build_launch(const MpcArgs &a, bool setup_only, void *stream, con
 // stale one only loses the gain.  hist: [2][B] the iteration counts of this solve (written here) | the order made of them for the next
 // one; null: the caller's order, nothing recorded.  ordered: hist holds the order of a previous solve.  Without one, and with
 // first_order (the solvers up to FAST_MAXN), a batch beyond 1024 is ordered by the QPs themselves (mpc_first_order_launch: by ||q||_inf).
-static int mpc_ordered_solve(f16_ctx *ctx, MpcArgs a, int32_t *hist, bool ordered, bool first_order, void *stream) {
+static int mpc_ordered_solve(f16_ctx *ctx, MpcArgs a, int32_t *hist, bool ordered, bool first_order, void *stream,
+                             const double *soft6 = nullptr) {      // soft6: a plan's soft state rows, or null
   const bool big = a.N > FAST_MAXN;          // the workgroup solver with its operands in HBM: it starts cold
   a.iters_out = hist;
   a.order = hist && ordered ? hist + a.B : nullptr;
@@ -1046,7 +1049,8 @@ static int mpc_ordered_solve(f16_ctx *ctx, MpcArgs a, int32_t *hist, bool ordere
     a.order = hist + a.B;
   }
   if (big) a.warm = nullptr;
-  if (int rc = big ? mpc_big_solve_launch(ctx, a, stream) : mpc_solve_dispatch(ctx, a, stream)) return rc;
+  if (big && soft6) return set_error(F16_EINVAL, "soft state rows run on the one-wavefront solver only (hzn <= 30)");
+  if (int rc = big ? mpc_big_solve_launch(ctx, a, stream) : mpc_solve_dispatch(ctx, a, stream, soft6)) return rc;
   return hist ? mpc_plan_order_launch(hist, hist + a.B, a.B, a.s.check_every, stream) : F16_OK;
 }
 
@@ -1196,6 +1200,8 @@ struct f16_mpc_plan {
   void *roll_sync;     // f16_rollout_mpc: ticket counter + per-aircraft progress counters (allocated by its first call)
   double *relin_w;     // f16_rollout_mpc_relin: Q[81] | R[9] | Rinv[9] of the plan's weights on the device (allocated by its first call)
   bool relin_model;    // the model blocks were overwritten by f16_rollout_mpc_relin: no frozen-model call may read them any more
+  bool soft_on;        // f16_mpc_plan_soft_rows: some kept state row is a soft row ...
+  double soft6[6];     // ... with these penalty weights (SROW order: alpha, beta, p, q, r, lf2; 0: the row stays hard)
   MpcArgs a;
 };
 
@@ -1221,6 +1227,8 @@ extern "C" int f16_mpc_plan_create_w(f16_ctx *ctx, f16_mpc_plan **plan, const do
   p->ctx = ctx; p->B = B; p->ld = ld; p->N = hzn; p->dt = dt;
   p->warm = nullptr; p->warm_on = false; p->have_prev = false; p->sched = nullptr; p->have_order = false; p->last_stream = stream;
   p->roll_sync = nullptr; p->relin_w = nullptr; p->relin_model = false;
+  p->soft_on = false;
+  for (double &w : p->soft6) w = 0.0;
   p->s = st;
   const MpcWork w = mpc_work_plan(hzn, mpc_ext_doubles(hzn), mpc_big_ws_doubles(hzn));
   if (int rc = hip_check(hipMalloc(&p->buf, w.total() * (size_t)B * sizeof(double)), "hipMalloc MPC plan")) { delete p; return rc; }
@@ -1260,7 +1268,7 @@ extern "C" int f16_mpc_plan_solve_w(f16_mpc_plan *p, const double *x, const doub
   if (int rc = mpc_build_launch(a, true, stream, "f16_mpc_plan build launch")) return rc;
   if (p->s.scaling > 0 || p->N > FAST_MAXN) a.mode = 0;   // nothing cached beyond the model part: full solver prologue
   // the history is the plan's own; a first solve is ordered by the QPs just built (F16_MPC_DISPATCH_ORDER steers one-shot calls only)
-  if (int rc = mpc_ordered_solve(p->ctx, a, p->sched, p->have_order, p->N <= FAST_MAXN, stream)) return rc;
+  if (int rc = mpc_ordered_solve(p->ctx, a, p->sched, p->have_order, p->N <= FAST_MAXN, stream, p->soft_on ? p->soft6 : nullptr)) return rc;
   p->have_order = true;
   p->have_prev = p->warm_on;
   return F16_OK;
@@ -1337,6 +1345,7 @@ static int rollout_mpc_loop(f16_mpc_plan *p, const MpcLoop &d, void *stream) {
   c.relin = d.relin; c.eps = d.eps; c.model_traj = d.model_traj; c.model_every = model_every; c.wq = p->relin_w;
   c.warm = p->warm_on ? p->warm : nullptr;
   c.warm_load = p->warm_on && p->have_prev;
+  c.soft6 = p->soft_on ? p->soft6 : nullptr;
   const int rc = mpc_wave_rollout_launch(p->ctx, p->a, c, stream);
   if (!rc) p->have_prev = p->warm_on;
   return rc;
@@ -1407,6 +1416,37 @@ extern "C" int f16_mpc_plan_warm_start(f16_mpc_plan *p, int on) {
   }
   p->warm_on = on != 0;
   p->have_prev = false;
+  return F16_OK;
+}
+
+// Soft state rows (f16_osqp_rules.hpp): a property of the plan, honoured by every call that solves on it.  Served by the one-wavefront
+// solver alone (f16_mpc_wave.hip: k_mpc_wave_soft, k_rollout_mpc_soft); the 512-lane solver, the long-horizon solver and the plans
+// without equilibration have no soft twin.
+extern "C" int f16_mpc_plan_soft_rows(f16_mpc_plan *p, const double *h_w9) {
+  if (!p) return set_error(F16_EINVAL, "bad argument to f16_mpc_plan_soft_rows");
+  double w6[6] = {0, 0, 0, 0, 0, 0};
+  bool on = false;
+  if (h_w9) {
+    const int kept[9] = {-1, -1, 0, 1, 2, 3, 4, -1, 5};      // MPC state -> kept row (SROW); phi, theta, lf1 carry no bounds
+    for (int i = 0; i < 9; ++i) {
+      const double w = h_w9[i];
+      if (!(w >= 0.0) || isinf(w)) return einval("f16_mpc_plan_soft_rows: weight %d must be finite and >= 0", i);
+      if (w > 0.0 && kept[i] < 0) return einval("f16_mpc_plan_soft_rows: MPC state %d (phi, theta, lf1) carries no bounds to soften", i);
+      if (kept[i] >= 0) w6[kept[i]] = w;
+      on = on || w > 0.0;
+    }
+  }
+  if (on && (p->N > WAVE_MAXN || p->s.scaling <= 0 || p->s.max_iter <= 0))
+    return einval("f16_mpc_plan_soft_rows needs a plan of the one-wavefront solver: hzn <= 30 and equilibrated solves (scaling > 0); got hzn %d, "
+                  "scaling %d", p->N, p->s.scaling);
+  if (on) {
+    MpcArgs probe = p->a;
+    probe.mode = 0;
+    if (!mpc_wave_enabled(probe)) return einval("f16_mpc_plan_soft_rows: the one-wavefront solver is switched off (F16_MPC_WAVE=0)");
+  }
+  p->soft_on = on;
+  for (int i = 0; i < 6; ++i) p->soft6[i] = w6[i];
+  p->have_prev = false;      // (as f16_mpc_plan_warm_start: a stored solution of the other problem is forgotten)
   return F16_OK;
 }
 

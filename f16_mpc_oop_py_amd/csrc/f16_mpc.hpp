@@ -131,7 +131,9 @@ constexpr int WAVE_MAXN = 30;
 constexpr int WAVE_SCAL_OFF = 7936;
 constexpr int WAVE_PBLK_DOUBLES = 2 * 36 * 64 * 2;      // P block image | per-lane image of the Toeplitz operands
 bool mpc_wave_enabled(const MpcArgs &a);
-int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream);
+// soft6: a plan's soft state rows (f16_mpc_plan_soft_rows) -- the penalty weights of the six kept state rows, SROW order (host) -- or
+// null: the hard kernel
+int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream, const double *soft6 = nullptr);
 // the closed-loop rollout (f16_rollout_mpc): per-call arguments beside the plan's MpcArgs
 struct RolloutMpcCall {
   double *x, *u;
@@ -153,6 +155,7 @@ struct RolloutMpcCall {
   double *model_traj;         // relin: [T / model_every][189][ld] Ad | Bd | Cd of every stored control step, or null
   int model_every;
   const double *wq;           // relin: the plan's weights on the device, Q[81] | R[9] | Rinv[9]
+  const double *soft6;        // the plan's soft state rows (host: six penalty weights, SROW order), or null: hard rows
 };
 int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall &c, void *stream);
 

@@ -28,6 +28,10 @@
 //   of several plant steps; pair_finish); f16_rollout_mpc / f16_rollout_mpc_relin are the hold = 1 calls of the same two kernels.
 //   Under a demand schedule (f16_rollout_mpc_sched / f16_rollout_mpc_relin_sched) control step t reads demand row t / dem_hold; the
 //   calls with one constant demand are the one-row case.
+//   Soft state rows (f16_mpc_plan_soft_rows; the rule: f16_osqp_rules.hpp) are a compile-time twin of all of the above: k_mpc_wave_soft,
+//   k_rollout_mpc_soft<RELIN> -> solve_aircraft<true> -> run_iterations / terminate_test<ANYEQ, true>.  A lane gains kappa and c w / W of
+//   its three state rows (SoftOps, LaneConstSoft); the KKT matrix, the Toeplitz stages, the LDS map and the problem size are the hard
+//   solve's.  The kernels themselves are written once, in f16_mpc_wave_kernels.inc.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -143,6 +147,28 @@ struct LaneConst {
   double loA[3], hiA[3], WA[3], loB[3], hiB[3], WB[3];   // bounds and row weight W = E^2
   int eqA, eqB;                                // bit c: the row carries 1e3 rho (equality row after scaling)
   double cs, cinv;
+};
+// ... and of a solve with soft state rows (f16_osqp_rules.hpp): c w / W of the lane's three state rows, and which of them are soft.  The
+// command and rate rows stay hard.  A type of its own behind the same pointer: the hard instantiations neither carry nor see it.
+struct LaneConstSoft : LaneConst {
+  double cwA[3];
+  int softA;                                   // bit c: state row c is soft (w > 0)
+};
+template <bool SOFT> using LaneConstOf = typename std::conditional<SOFT, LaneConstSoft, LaneConst>::type;
+// The six penalty weights w (kept state rows, SROW order): a kernel argument of the soft instantiations alone.
+struct SoftRows { double w[6]; };
+// per-row kappa of a lane's state rows at the present rho: formed at every entry of the hot loop (rho changes between entries only)
+template <bool SOFT> struct SoftOps {
+  template <class RO> __device__ __forceinline__ SoftOps(const RO &, const LaneConst &) {}
+};
+template <> struct SoftOps<true> {
+  double kap[3];
+  int softA;
+  template <class RO> __device__ __forceinline__ SoftOps(const RO &ro, const LaneConstSoft &C) {
+    softA = C.softA;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) kap[c] = osqp_soft_kappa((C.softA >> c) & 1, ro.roA(c), C.cwA[c]);
+  }
 };
 struct SolveState {
   double x[3], zA[3], yA[3], zB[3], yB[3], dyA[3], dyB[3];
@@ -739,7 +765,7 @@ __device__ __forceinline__ double *x4_step(int step) { return s_w + XT_OFF + 4 *
 // decision is "go on" whatever P x and A' y are -- same decisions as evaluating everything, and the P image (37 KB from the
 // Infinity Cache), the second Toeplitz pass and the reload of this function's operands are paid on a third of the block ends
 // (config-4 batch: 5.6 of 18.3).  Leaves the state, the dual step of the last iteration, w of the new point, st->it / to_check.
-template <bool ANYEQ>
+template <bool ANYEQ, bool SOFT = false>
 __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp, const double *Gg, const double *kimg, int N, IterSettings oa) {
   IterSettings o;                                           // (arguments of a device function arrive in vector registers)
   o.alpha = uniform_f64(oa.alpha); o.eps_abs = uniform_f64(oa.eps_abs); o.eps_rel = uniform_f64(oa.eps_rel);
@@ -750,7 +776,7 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
   const Role R = role(N);
   const TJob J = tjob();
   const Consume Q = consume_addresses(R);
-  const LaneConst C = *lcp;
+  const LaneConstOf<SOFT> C = *static_cast<const LaneConstOf<SOFT> *>(lcp);
   double Gd[TB][2][3], KA[6][6];
   load_G_image(Gd, Gg, R.l);                                // (Gg: the per-lane image)
   load_KA_image(KA, kimg, R.l);
@@ -758,6 +784,7 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
 #pragma unroll
   for (int c = 0; c < 3; ++c) { x[c] = st->x[c]; zA[c] = st->zA[c]; yA[c] = st->yA[c]; zB[c] = st->zB[c]; yB[c] = st->yB[c]; }
   const RowOps<ANYEQ> ro(st->rho, C);
+  const SoftOps<SOFT> so(ro, C);
   const RowSlots slots(R);
   double *const wc = s_w + WC_OFF, *const wr = s_w + WR_OFF;
   double *const rhs = wc;                                   // (the owner of k reads wc[k] before it writes rhs[k])
@@ -822,7 +849,13 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
         x[c] = alpha * xk[c] + (1 - alpha) * x[c];
         {
           const double zr = alpha * z3[c] + (1 - alpha) * zA[c];
-          const double zn = fmin(fmax(fma(yA[c], ro.riA(c), zr), C.loA[c]), C.hiA[c]);
+          double zn;
+          if constexpr (SOFT) {
+            const double v = fma(yA[c], ro.riA(c), zr);
+            zn = osqp_soft_prox(v, fmin(fmax(v, C.loA[c]), C.hiA[c]), so.kap[c]);
+          } else {
+            zn = fmin(fmax(fma(yA[c], ro.riA(c), zr), C.loA[c]), C.hiA[c]);
+          }
           const double d = ro.roA(c) * (zr - zn);
           if (KEEP) dyA[c] = d;
           yA[c] = yA[c] + d; zA[c] = zn;
@@ -861,7 +894,7 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
     wave_lds_sync();
     stage3_partials(Gd, J);
     wave_lds_sync();
-    double ax3[3], v0 = 0.0, v12 = 0.0, v7 = 0.0, v8 = 0.0;
+    double ax3[3], v0 = 0.0, v12 = 0.0, v7 = 0.0, v8 = 0.0, vs = 0.0;
     stage3_totals(Q.a3, ax3);
     if (R.act) {
 #pragma unroll
@@ -871,15 +904,24 @@ __device__ __noinline__ void run_iterations(SolveState *st, const LaneConst *lcp
         v0 = fmax(v0, fmax(fabs(ax3[c] - zA[c]), fabs(axB - zB[c])));
         v12 = fmax(v12, fmax(fmax(fabs(ax3[c]), fabs(axB)), fmax(fabs(zA[c]), fabs(zB[c]))));
         v7 = fmax(v7, fmax(C.WA[c] * fabs(dyA[c]), C.WB[c] * fabs(dyB[c])));
-        v8 += C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0)) +
-              C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+        if constexpr (SOFT) {      // (a soft row: nothing in the support function, and its own share of |E dyb| on the side)
+          const bool sf = (so.softA >> c) & 1;
+          vs = fmax(vs, sf ? C.WA[c] * fabs(dyA[c]) : 0.0);
+          v8 += (sf ? 0.0 : C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0))) +
+                C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+        } else {
+          v8 += C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0)) +
+                C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+        }
       }
     }
     v0 = wave_reduce_dpp<false>(v0); v12 = wave_reduce_dpp<false>(v12);
     v7 = wave_reduce_dpp<false>(v7); v8 = wave_reduce_dpp<true>(v8);
+    if constexpr (SOFT) vs = wave_reduce_dpp<false>(vs);
     rp = v0;
     const bool prim_ok = osqp_residual_small(rp, v12, o.eps_abs, o.eps_rel);
-    const bool cert = osqp_infeasibility_candidate(v7, v8, o.eps_prim_inf);
+    bool cert = osqp_infeasibility_candidate(v7, v8, o.eps_prim_inf);
+    if constexpr (SOFT) cert = cert && !osqp_soft_rows_reject(vs, v7, o.eps_prim_inf);
     const bool full = prim_ok || cert || it >= o.max_iter || (o.adaptive_rho && it % o.rho_every == 0);
     WSTAMP(7)
     if (__builtin_amdgcn_readfirstlane((int)full)) break;   // (wave-uniform: the reductions leave the same value on every lane)
@@ -915,13 +957,13 @@ __device__ __noinline__ void start_point(const SolveState *st, const LaneConst *
 // certificate and, every rho_every iterations, the rho estimate on the scaled residuals.  Sets done / converged / infeasible,
 // returns 1 when rho left the 5x band (st->rho then holds the new value and the caller re-factorises); leaves w of the
 // current point in LDS for the next iteration otherwise.
-template <bool ANYEQ>
+template <bool ANYEQ, bool SOFT = false>
 __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp, const double *Pg, const double *Gg, const double *qv,
                                            const double *Dv, int N, IterSettings o) {
   const Role R = role(N);
   const TJob J = tjob();
   const Consume Q = consume_addresses(R);
-  const LaneConst C = *lcp;
+  const LaneConstOf<SOFT> C = *static_cast<const LaneConstOf<SOFT> *>(lcp);
   double x[3], zA[3], yA[3], zB[3], yB[3], dyA[3], dyB[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) { x[c] = st->x[c]; zA[c] = st->zA[c]; yA[c] = st->yA[c]; zB[c] = st->zB[c]; yB[c] = st->yB[c];
@@ -990,6 +1032,7 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
     axB[c] = R.par ? xkk - xkm : xkk;
   }
   double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};                // r1, |Ax|, |z|, r2, |Px|, |A'y|, |q|, |E dyb|, support(dyb)
+  double vs = 0.0;                                          // SOFT: |E dyb| over the soft rows
   if (R.act) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -997,8 +1040,15 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
       v[1] = fmax(v[1], fmax(fabs(ax3[c]), fabs(axB[c])));
       v[2] = fmax(v[2], fmax(fabs(zA[c]), fabs(zB[c])));
       v[7] = fmax(v[7], fmax(C.WA[c] * fabs(dyA[c]), C.WB[c] * fabs(dyB[c])));
-      v[8] += C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0)) +
-              C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+      if constexpr (SOFT) {
+        const bool sf = (C.softA >> c) & 1;
+        vs = fmax(vs, sf ? C.WA[c] * fabs(dyA[c]) : 0.0);
+        v[8] += (sf ? 0.0 : C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0))) +
+                C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+      } else {
+        v[8] += C.WA[c] * (C.hiA[c] * fmax(dyA[c], 0.0) + C.loA[c] * fmin(dyA[c], 0.0)) +
+                C.WB[c] * (C.hiB[c] * fmax(dyB[c], 0.0) + C.loB[c] * fmin(dyB[c], 0.0));
+      }
       v[3] = fmax(v[3], fabs(px[c] + qu[c] + aty[c]));
       v[4] = fmax(v[4], fabs(px[c])); v[5] = fmax(v[5], fabs(aty[c])); v[6] = fmax(v[6], fabs(qu[c]));
     }
@@ -1006,6 +1056,7 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = wave_reduce_dpp<false>(v[i]);
   v[8] = wave_reduce_dpp<true>(v[8]);
+  if constexpr (SOFT) vs = wave_reduce_dpp<false>(vs);
   TSTAMP(3)
   const double rp = v[0], rd = v[3];
   const double np_ = fmax(v[1], v[2]), nd_ = fmax(fmax(v[4], v[5]), v[6]);
@@ -1013,7 +1064,9 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
   else {
     // OSQP primal-infeasibility certificate on dy (auxil.c:is_primal_infeasible)
     const double ndy = v[7], supp = v[8];
-    if (osqp_infeasibility_candidate(ndy, supp, o.eps_prim_inf)) {
+    bool candidate = osqp_infeasibility_candidate(ndy, supp, o.eps_prim_inf);
+    if constexpr (SOFT) candidate = candidate && !osqp_soft_rows_reject(vs, ndy, o.eps_prim_inf);
+    if (candidate) {
       {
         double eA[3], eB[3];
 #pragma unroll
@@ -1072,7 +1125,7 @@ __device__ __noinline__ int terminate_test(SolveState *st, const LaneConst *lcp,
 }
 
 // factorise / iterate / test until done (st->done) for one ANYEQ flavour; returns whether every factorisation succeeded
-template <bool ANYEQ>
+template <bool ANYEQ, bool SOFT = false>
 __device__ __forceinline__ bool solve_loop(SolveState *st, const LaneConst *lcp, const double *Pg, const double *pb, const double *gw, const double *Gg,
                                            const double *qv, const double *Dv, int N, double cs, IterSettings o, const Role &R) {
   double *const xt = s_w + XT_OFF;
@@ -1099,9 +1152,9 @@ __device__ __forceinline__ bool solve_loop(SolveState *st, const LaneConst *lcp,
     bool refactor = false;
     while (!st->done && !refactor) {
       WSTAMPK(14, 15)
-      run_iterations<ANYEQ>(st, lcp, Gg, Gg + GIMG_DOUBLES, N, o);      // (to the next block end whose test needs the dual side too)
+      run_iterations<ANYEQ, SOFT>(st, lcp, Gg, Gg + GIMG_DOUBLES, N, o);      // (to the next block end whose test needs the dual side too)
       WSTAMPK(13, 15)
-      refactor = terminate_test<ANYEQ>(st, lcp, pb, Gg, qv, Dv, N, o) != 0;
+      refactor = terminate_test<ANYEQ, SOFT>(st, lcp, pb, Gg, qv, Dv, N, o) != 0;
       WSTAMPK(9, 11)
     }
   }
@@ -1343,11 +1396,14 @@ __device__ __noinline__ void p_block_image(const double *Pg, double *pb, int n) 
 // ... of aircraft b by this wavefront: prologue, equilibration, factorise / iterate / test until done.  Leaves the solution in
 // `st` (lane 0 holds the first move st.x[0..2]) and, with a warm-start buffer, the solution for the next call; returns whether every
 // factorisation succeeded.  Called by k_mpc_wave (one calc_MPC_action per aircraft) and by k_rollout_mpc (one per aircraft and step).
+// SOFT (k_mpc_wave_soft / k_rollout_mpc_soft): the kept state rows with sw.w > 0 are soft rows (f16_osqp_rules.hpp); *soft_active: some soft
+// row's z of the returned iterate lies outside its [l, u] (exact: z == clip(v) whenever v is inside).
+template <bool SOFT = false>
 __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long job, const Role &R, SolveState &st, int warm_load
 #ifdef F16_EXP_STAMPW
                                                , unsigned long long &tK0
 #endif
-                                               ) {
+                                               , SoftRows sw = SoftRows{}, bool *soft_active = nullptr) {
   const int N = a.N, n = 3 * N;
   const int l = R.l;
   (void)job;
@@ -1389,10 +1445,11 @@ __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long jo
     rz.cs = scal[480];
   }
   // ---- lane constants: owned variables, state rows (step istep, kept rows 3h..3h+2), command / rate rows of the same step
-  LaneConst C;
+  LaneConstOf<SOFT> C;
   const double cs = rz.cs;
   C.cs = cs; C.cinv = 1.0 / cs;
   C.eqA = 0; C.eqB = 0;
+  if constexpr (SOFT) C.softA = 0;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int k = R.act ? kx + c : 0;
@@ -1405,6 +1462,11 @@ __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long jo
       const double lo = R.act ? a.pb.slb[kk] - pm : 0.0, hi = R.act ? a.pb.sub[kk] - pm : 0.0;
       const bool eq = R.act && Eo * (hi - lo) < OSQP_RHO_TOL;
       C.loA[c] = lo; C.hiA[c] = hi; C.WA[c] = Eo * Eo; C.eqA |= eq ? (1 << c) : 0;
+      if constexpr (SOFT) {
+        const double wk = R.h ? sw.w[3 + c] : sw.w[c];      // kept row 3h + c
+        const bool sf = R.act && wk > 0.0;
+        C.cwA[c] = sf ? cs * wk / (Eo * Eo) : 0.0; C.softA |= sf ? (1 << c) : 0;
+      }
       if (R.act) s_w[WG_OFF + 6 * R.istep + kk] = Eo * Eo * (eq ? OSQP_RHO_EQ_OVER_RHO_INEQ : 1.0);
     }
     {   // command row (par = 0, utils.py:139-140) or rate row (par = 1, utils.py:148-152) of variable k
@@ -1449,8 +1511,14 @@ __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long jo
 #endif
   const IterSettings o = iter_settings(a.s);
   const bool anyeq = __ballot((C.eqA | C.eqB) != 0) != 0;      // (wave-uniform)
-  const bool ok = anyeq ? solve_loop<true>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R)
-                        : solve_loop<false>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R);
+  const bool ok = anyeq ? solve_loop<true, SOFT>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R)
+                        : solve_loop<false, SOFT>(&st, &C, Pg, pb, gw, gimg, exw, scal, N, cs, o, R);
+  if constexpr (SOFT) {
+    bool out = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out = out || (((C.softA >> c) & 1) && (st.zA[c] < C.loA[c] || st.zA[c] > C.hiA[c]));
+    *soft_active = __ballot(out) != 0;
+  }
   if (wm) {                                                  // keep the solution for the next warm start
     const bool good = st.converged != 0 && st.infeasible == 0;
 #pragma unroll
@@ -1462,75 +1530,7 @@ __device__ __forceinline__ bool solve_aircraft(const MpcArgs &a, long b, long jo
   return ok;
 }
 
-__global__ __launch_bounds__(64, 1) void k_mpc_wave(MpcArgs a) {
-  const int N = a.N;
-  const Role R = role(N);
-  const int l = R.l;
-  for (long job = blockIdx.x;; ) {
-  if (a.wave_queue) {
-    unsigned q = 0;
-    if (l == 0) q = atomicAdd(a.wave_queue, 1u);
-    job = (long)(unsigned)__builtin_amdgcn_readfirstlane((int)q);
-    if (job >= a.B) break;
-    wave_lds_sync();                                         // (the previous aircraft's LDS traffic is over on every lane)
-  }
-#ifdef F16_EXP_STAMPW
-  const unsigned long long wc0_ = wall_clock64();
-  if (job == 0 && l == 0) g_stamp_wg = (int)blockIdx.x;
-  unsigned long long tK0 = 0;
-#endif
-  // No order from a previous call (first call on this stream / batch size): NOT the caller's order either -- workgroup ids go to
-  // the XCDs round-robin, and how hard an aircraft is tends to follow its index (the config-4 workload: every aircraft = 0, 3, 6
-  // mod 8 needs twice the iterations), so the identity gives three XCDs twice the work of the others.  A fixed stride coprime to
-  // B spreads any such pattern; the results do not depend on the map.
-  const long b = a.order ? (long)__builtin_amdgcn_readfirstlane(a.order[job])
-                         : (a.wave_stride ? (long)(((unsigned long long)job * a.wave_stride) % (unsigned long long)a.B) : job);
-  if (mpc_job_nonfinite(a.ext, a.N, b)) {                             // (wave-uniform) no QP to solve: NaN command, zero iterations
-    mpc_write_nonfinite(a.ucmd, a.useq, a.info, a.iters_out, a.status, a.ld, a.N, a.s.rho, b, l, 64);
-    if (!a.wave_queue) break;
-    continue;
-  }
-  SolveState st;
-#ifdef F16_EXP_STAMPW
-  const bool ok = solve_aircraft(a, b, job, R, st, a.warm_load, tK0);
-#else
-  const bool ok = solve_aircraft(a, b, job, R, st, a.warm_load);
-#endif
-  const int kx = 3 * R.istep;
-  const bool converged = st.converged != 0, infeasible = st.infeasible != 0;
-  // res.x[0:3] (env.py:424); OSQP hands back NaN for a problem it certifies infeasible
-  if (R.act && R.par == 0) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      if (R.istep == 0) a.ucmd[c * a.ld + b] = infeasible ? NAN : st.x[c];
-      if (a.useq) a.useq[(kx + c) * a.ld + b] = infeasible ? NAN : st.x[c];
-    }
-  }
-#ifdef F16_EXP_STAMPW
-  if (job == 0 && l == 0 && a.useq) {      // diagnostic build: the stamps replace rows 60.. of this aircraft's u_seq column
-    for (int i = 0; i < 8; ++i) a.useq[(60 + i) * a.ld + b] = (double)g_wstamp[i];
-    a.useq[68 * a.ld + b] = (double)st.it;
-    for (int i = 9; i < 16; ++i) a.useq[(60 + 12 + i - 9) * a.ld + b] = (double)g_wstamp[i];
-    for (int i = 0; i < 8; ++i) a.useq[(80 + i) * a.ld + b] = (double)g_tstamp[i];
-    a.useq[71 * a.ld + b] = (double)(__builtin_amdgcn_s_memtime() - tK0);
-  }
-#endif
-  if (l == 0) {
-    mpc_write_result(a.info, a.iters_out, a.status, a.ld, b, st.it, st.rp, st.rd, st.rho, mpc_status_bits(converged, infeasible, ok, a.s.max_iter));
-#ifdef F16_EXP_STAMPW
-    if (a.info) {
-      a.info[1 * a.ld + b] = (double)wc0_;                 // diagnostic build: start / end of this solve on the 100 MHz clock
-      a.info[2 * a.ld + b] = (double)wall_clock64();
-      a.info[3 * a.ld + b] = (double)((__builtin_amdgcn_s_getreg(63508) & 15) * 65536 + (__builtin_amdgcn_s_getreg(63492) & 0xFFFF));    // XCC_ID | HW_ID: which SIMD
-    }
-#endif
-  }
-#ifdef F16_EXP_STAMPW
-  if (job == 0 && l == 0) g_stamp_wg = -1;
-#endif
-  if (!a.wave_queue) break;
-  }
-}
+// (k_mpc_wave and its soft twin: f16_mpc_wave_kernels.inc, included at the end of this namespace)
 
 // ----------------------------------------------------------------------------------------------------------------
 // The closed-loop MPC rollout as ONE launch (BASELINE config 5; the reference's loop test_env.py:480-495:
@@ -1840,98 +1840,30 @@ struct RollRelinArgs {
 };
 __device__ __forceinline__ const RollMpcArgs &rollout_args(const RollMpcArgs &k) { return k; }
 __device__ __forceinline__ const RollMpcArgs &rollout_args(const RollRelinArgs &k) { return k.r; }
-template <bool RELIN>
-__global__ __launch_bounds__(64, 1) void k_rollout_mpc(typename std::conditional<RELIN, RollRelinArgs, RollMpcArgs>::type kargs) {
-  const RollMpcArgs &ra = rollout_args(kargs);
-  const MpcArgs &a = ra.m;
-  const int N = a.N;
-  const Role R = role(N);
-  const int l = R.l;
-  const unsigned Bu = (unsigned)a.B;
-#ifdef F16_DBG_PAIRSTAMP
-  unsigned long long tp0_ = __builtin_amdgcn_s_memtime();
-#endif
-  for (;;) {
-    unsigned k = 0;
-    if (l == 0) k = atomicAdd(ra.queue, 1u);
-    k = (unsigned)__builtin_amdgcn_readfirstlane((int)k);
-    PSTAMP(0)
-    DBGM(0, 1000 + k)
-    if (k >= ra.total) break;
-    const int t = __builtin_amdgcn_readfirstlane((int)(k / Bu));
-    const unsigned j = k - (unsigned)t * Bu;
-    const long b = (long)(unsigned)__builtin_amdgcn_readfirstlane((int)(ra.stride ? (unsigned)(((unsigned long long)j * ra.stride) % Bu) : j));
-    // ---- wait for step t - 1 of this aircraft, then acquire what its wavefront published.  (Every lane polls the same word -- one
-    // broadcast load -- and every lane publishes below: no lane-0-only region on either side of the loop's back edge.)
-    // The wait is bounded (2^24 polls, tens of seconds -- the longest legitimate wait is one 40,000-iteration solve, ~0.1 s): a wave
-    // that never sees its predecessor flags the aircraft (F16_ST_LOOP_STALL) and goes on, so that the grid drains whatever happens.
-    int stall = 0;
-    if (t > 0) {
-      int polls = 0;
-      while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&ra.progress[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < t) {
-        __builtin_amdgcn_s_sleep(16);
-        if (++polls > (1 << 24)) { stall = F16_ST_LOOP_STALL; break; }
-      }
-    }
-    PSTAMP(1)
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    PSTAMP(2)
-    PairIO io;
-    io.x = ra.x; io.u = ra.u; io.dem = ra.dem + (size_t)(t / ra.dem_hold) * 3 * a.ld; io.traj = ra.traj; io.cmd_traj = ra.cmd_traj; io.iters_traj = ra.iters_traj;
-    io.status = ra.status; io.tab = ra.tab; io.lofi = ra.lofi; io.exw = a.ext + (size_t)b * mpc_ext_doubles(N);
-    io.ld = a.ld; io.b = b; io.t = t; io.N = N; io.every = ra.every; io.fi = ra.fi; io.flags = ra.flags; io.xcg = ra.xcg; io.dt = a.dt;
-    io.hold = ra.hold; io.dtp = ra.dtp;
-    io.cmd[0] = NAN; io.cmd[1] = NAN; io.cmd[2] = NAN; io.iters = 0; io.stw = 0; io.stall = stall;
-    DBGM(1, 2000 + t)
-    int code;
-    if constexpr (RELIN) {
-      ModelIO mo;
-      mo.Pg = a.Ppk + (size_t)b * (size_t)(3 * N * (3 * N + 1) / 2);
-      mo.model = (kargs.model_traj && (t + 1) % kargs.model_every == 0) ? kargs.model_traj + (size_t)((t + 1) / kargs.model_every - 1) * MODEL_ROWS * a.ld + b : nullptr;
-      mo.pb.Q = kargs.wq; mo.pb.R = kargs.wq + 81; mo.pb.Rinv = kargs.wq + 90; mo.pb.custom_q = a.pb.custom_q; mo.pb.custom_r = a.pb.custom_r; mo.eps = kargs.eps;
-      code = __builtin_amdgcn_readfirstlane(pair_model(&io, &mo));
-      if (code == PAIR_SOLVE) code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
-    } else {
-      code = __builtin_amdgcn_readfirstlane(pair_prepare(&io));
-    }
-    DBGM(2, 3000 + code)
-    PSTAMP(3)
-    if (code == PAIR_SOLVE) {
-      SolveState st;
-#ifdef F16_DBG_SKIP_SOLVE      // (measurement build: what a pair costs WITHOUT its solve -- tools/gpu_config5_only.py under F16HIP_SO)
-      st.infeasible = 0; st.converged = 1; st.it = 0; st.x[0] = -0.5; st.x[1] = 0.0; st.x[2] = 0.0;
-      const bool ok = true;
-#elif defined(F16_EXP_STAMPW)
-      unsigned long long tK0 = 0;
-      const bool ok = solve_aircraft(a, b, (long)k + 1, R, st, (t > 0 || a.warm_load) ? 1 : 0, tK0);
-#else
-      // (warm start, opt-in: step 0 starts from the plan's previous call if there was one, every later step from the step before --
-      //  the buffer is handed from wavefront to wavefront with the state, behind the same release / acquire)
-      const bool ok = solve_aircraft(a, b, (long)k + 1, R, st, (t > 0 || a.warm_load) ? 1 : 0);
-#endif
-      const bool infeasible = __builtin_amdgcn_readfirstlane(st.infeasible) != 0;
-      const bool converged = __builtin_amdgcn_readfirstlane(st.converged) != 0;
-      const double c0 = bcast0_f64(st.x[0]), c1 = bcast0_f64(st.x[1]), c2 = bcast0_f64(st.x[2]);      // res.x[0:3], env.py:424 (lane 0 owns step 0)
-      io.iters = __builtin_amdgcn_readfirstlane(st.it);
-      io.cmd[0] = infeasible ? NAN : c0; io.cmd[1] = infeasible ? NAN : c1; io.cmd[2] = infeasible ? NAN : c2;
-      io.stw |= mpc_status_bits(converged, infeasible, uniform_flag(ok), a.s.max_iter);      // (OSQP hands back NaN for a problem it certifies infeasible)
-      wave_lds_sync();
-    }
-    DBGM(3, 4000 + io.iters)
-    PSTAMP(4)
-    pair_finish(&io, code);
-    PSTAMP(5)
-    DBGM(4, 5000)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&ra.progress[b], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (64 lanes, one word, one value)
-    PSTAMP(6)
-    DBGM(5, 6000 + t)
-  }
-  DBGM(6, 7000)
-}
+template <bool RELIN> using RollArgsOf = typename std::conditional<RELIN, RollRelinArgs, RollMpcArgs>::type;
+
+// The kernels, TEXTUALLY twice: hard rows (k_mpc_wave, k_rollout_mpc<RELIN>) and soft state rows (k_mpc_wave_soft, k_rollout_mpc_soft<RELIN>,
+// with the six weights as an argument of theirs alone).  Not one body behind `const MpcArgs &`: a kernel that hands its argument block
+// to a function, even an inlined one, is compiled differently (f16_mpc.hpp: mpc_job_nonfinite) -- the hard kernels keep their code and
+// their resource figures this way (tools/mpc_soft_resources.py).
+#define WAVE_SOFT 0
+#define WAVE_KERNEL(name) name
+#define WAVE_SOFT_PARAM
+#define WAVE_SOFT_ARGS
+#include "f16_mpc_wave_kernels.inc"
+#undef WAVE_SOFT
+#undef WAVE_KERNEL
+#undef WAVE_SOFT_PARAM
+#undef WAVE_SOFT_ARGS
+#define WAVE_SOFT 1
+#define WAVE_KERNEL(name) name##_soft
+#define WAVE_SOFT_PARAM , SoftRows sw
+#define WAVE_SOFT_ARGS , sw, &soft_active
+#include "f16_mpc_wave_kernels.inc"
+#undef WAVE_SOFT
+#undef WAVE_KERNEL
+#undef WAVE_SOFT_PARAM
+#undef WAVE_SOFT_ARGS
 }  // namespace wave
 
 bool mpc_wave_enabled(const MpcArgs &a) {
@@ -1939,7 +1871,7 @@ bool mpc_wave_enabled(const MpcArgs &a) {
   return !off && a.N >= 1 && a.N <= WAVE_MAXN && a.s.scaling > 0 && a.s.max_iter > 0 && a.gramws != nullptr && a.pblk != nullptr;
 }
 
-int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
+int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream, const double *soft6) {
   (void)ctx;
   if (a.N < 1 || a.N > WAVE_MAXN || !a.gramws) return set_error(F16_EINVAL, "wavefront MPC solver needs 1 <= N <= 30 and a workspace");
   if (a.B > 0x7fffffffL) return set_error(F16_EINVAL, "batch too large for one launch");
@@ -1968,7 +1900,13 @@ int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream) {
       grid = 4u * (unsigned)cus;
     }
   }
-  hipLaunchKernelGGL(wave::k_mpc_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w);
+  if (soft6) {
+    wave::SoftRows sw;
+    for (int i = 0; i < 6; ++i) sw.w[i] = soft6[i];
+    hipLaunchKernelGGL(wave::k_mpc_wave_soft, dim3(grid), dim3(64), 0, (hipStream_t)stream, w, sw);
+  } else {
+    hipLaunchKernelGGL(wave::k_mpc_wave, dim3(grid), dim3(64), 0, (hipStream_t)stream, w);
+  }
   return hip_check(hipGetLastError(), "f16_mpc_batch wavefront solve launch");
 }
 
@@ -2002,13 +1940,17 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   // only wait
   const long slots = cus > 0 ? 4L * cus : 1024;
   const unsigned grid = (unsigned)(a.B < slots ? a.B : slots);
+  wave::SoftRows sw{};      // the plan's soft state rows (f16_mpc_plan_soft_rows), or none: the hard kernels
+  for (int i = 0; i < 6 && c.soft6; ++i) sw.w[i] = c.soft6[i];
   if (c.relin) {      // f16_rollout_mpc_relin: the model of every step is derived inside the pair (pair_model)
     wave::RollRelinArgs rr{};
     rr.r = r; rr.model_traj = c.model_traj; rr.model_every = c.model_every; rr.wq = c.wq; rr.eps = c.eps;
-    hipLaunchKernelGGL(wave::k_rollout_mpc<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rr);
+    if (c.soft6) hipLaunchKernelGGL(wave::k_rollout_mpc_soft<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rr, sw);
+    else hipLaunchKernelGGL(wave::k_rollout_mpc<true>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rr);
     return hip_check(hipGetLastError(), "f16_rollout_mpc_relin launch");
   }
-  hipLaunchKernelGGL(wave::k_rollout_mpc<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, r);
+  if (c.soft6) hipLaunchKernelGGL(wave::k_rollout_mpc_soft<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, r, sw);
+  else hipLaunchKernelGGL(wave::k_rollout_mpc<false>, dim3(grid), dim3(64), 0, (hipStream_t)stream, r);
   return hip_check(hipGetLastError(), "f16_rollout_mpc launch");
 }
 

@@ -28,6 +28,19 @@ __device__ __forceinline__ bool osqp_infeasibility_certified(double nat, double 
   return nat < eps_prim_inf * ndy;
 }
 
+// ---- soft rows (f16_mpc_plan_soft_rows; k_mpc_wave_soft / k_rollout_mpc_soft): row i carries the penalty (w_i / 2) dist(a_i'u, [l_i, u_i])^2
+// instead of the constraint.  No slack variable: the z-update of the row is the proximal step of that penalty,
+//   v = zr + y / rho_i,  zc = clip(v, l, u),  z = zc + kappa_i (v - zc),  kappa_i = rho_i / (rho_i + c w_i / E_i^2)
+// (cw_over_W: c w_i / E_i^2, the penalty weight in the scaled variables; kappa = 0 on a hard row).  z == zc exactly while v is inside.
+__device__ __forceinline__ double osqp_soft_kappa(bool soft, double rho_row, double cw_over_W) {
+  return soft ? rho_row / (rho_row + cw_over_W) : 0.0;
+}
+__device__ __forceinline__ double osqp_soft_prox(double v, double zc, double kappa) { return zc + kappa * (v - zc); }
+// ... and in the certificate a soft row is a row without bounds: nothing in the support function, and a candidate whose dy does not
+// vanish on it is no certificate (is_primal_infeasible: |E_i dyb_i| > eps_prim_inf |E dyb|_inf on a row with two infinite bounds).
+// soft_dy: the largest |E_i dyb_i| over the soft rows.
+__device__ __forceinline__ bool osqp_soft_rows_reject(double soft_dy, double ndy, double eps_prim_inf) { return soft_dy > eps_prim_inf * ndy; }
+
 // auxil.c:compute_rho_estimate on the SCALED residuals ||Ab xb - zb||, ||Pb xb + qb + Ab' yb|| and their norms: the clamped
 // candidate, and whether it leaves the band around the present rho (then the solver factorises again)
 __device__ __forceinline__ double osqp_rho_estimate(double rho, double r_prim_s, double n_z_s, double n_Ax_s, double r_dual_s,

@@ -841,15 +841,32 @@ class F16Batch:
         return trx, tru
 
     # ------------------------------------------------------------------ env.py:373-424
-    def prepare_MPC(self, hzn, settings=None, warm_start=False, weights=None, ctrl_every=1):
+    @staticmethod
+    def _soft_rows(soft):
+        """The `soft` keyword as the nine weights of f16_mpc_plan_soft_rows (MPC-state order), or None for hard rows: a scalar is that
+        weight on the six bounded rows (alpha, beta, p, q, r, lf2), a 9-vector is taken as it is; None and all zeros mean hard rows."""
+        if soft is None:
+            return None
+        w = np.asarray(soft, dtype=np.float64)
+        if w.ndim == 0:
+            w = np.where(np.array([0, 0, 1, 1, 1, 1, 1, 0, 1], dtype=bool), float(w), 0.0)
+        if w.shape != (9,):
+            raise ValueError(f"soft must be a scalar or nine weights in MPC-state order (got shape {w.shape})")
+        return None if not w.any() else tuple(float(v) for v in w)
+
+    def prepare_MPC(self, hzn, settings=None, warm_start=False, weights=None, ctrl_every=1, soft=None):
         """Prepare the model-only part of calc_MPC_action for horizon hzn from the frozen reduced model self.ssr
         (env.py:49-60 freezes it; the reference still rebuilds the QP on every call): DARE, terminal weight, prediction
         blocks, P, A'A, start rho and the KKT factorisation stay on the device.  `_calc_MPC_action(..., use_plan=True)`
         then only forms the state-dependent vectors and iterates; results are bit-identical to the one-shot call.
         ctrl_every = k > 1: a plan for a controller that runs every k plant steps (rollout_MPC(..., ctrl_every=k)).  Its model is this
         environment's linearisation -- the continuous (Ac, Bc) of build_ssr's point -- through the zero-order hold at the control
-        period k * self.dt, which is also the dt of its rate rows; self.ssr itself is untouched."""
+        period k * self.dt, which is also the dt of its rate rows; self.ssr itself is untouched.
+        soft: soft state rows (C-ABI f16_mpc_plan_soft_rows) -- a scalar is that penalty weight on the six bounded state rows, a
+        9-vector is in MPC-state order; every solve on the plan then penalises leaving the state box instead of forbidding it, and
+        status bit F16_ST_QP_SOFT_ACTIVE marks a solve that did leave it.  hzn <= 30 and equilibrated solves only."""
         ctrl_every = int(ctrl_every)
+        w9 = self._soft_rows(soft)
         if ctrl_every < 1:
             raise ValueError(f"ctrl_every must be >= 1 (got {ctrl_every})")
         if self.ssr is None:
@@ -870,20 +887,30 @@ class F16Batch:
         self._check(self.lib.f16_mpc_plan_create_w(self.ctx.handle, ctypes.byref(h), _vp(Ad), _vp(Bd), _vp(Cd),
                                                    ctypes.byref(w) if w else None, self.B, self.B, int(hzn), plan_dt, ctypes.byref(s),
                                                    self._stream))
+        if w9 is not None:
+            rc = self.lib.f16_mpc_plan_soft_rows(h, (ctypes.c_double * 9)(*w9))
+            if rc:                      # (a plan the one-wavefront solver does not serve: no half-made plan is kept)
+                self.lib.f16_mpc_plan_destroy(h)
+                self._check(rc)
         self._plan, self._plan_hzn, self._plan_ctrl_every = h, int(hzn), ctrl_every
         self._plan_default_settings = int((settings or {}).get("scaling", 10)) > 0       # (what f16_rollout_mpc takes: equilibrated solves)
         if warm_start:      # OSQP's in-object default; the reference starts cold on every call (new object), so: opt-in
             self._check(self.lib.f16_mpc_plan_warm_start(h, 1))
-        self._plan_args = dict(settings=settings, warm_start=warm_start, weights=weights)
+        self._plan_args = dict(settings=settings, warm_start=warm_start, weights=weights, soft=soft)
         self._plan_foreign = False      # True once rollout_MPC(relinearise=True) has overwritten the plan's model blocks
         return self
 
-    def _frozen_plan(self, hzn, ctrl_every=1):
+    _KEEP_SOFT = object()      # (the `soft` of a call that does not name it: whatever the plan has)
+
+    def _frozen_plan(self, hzn, ctrl_every=1, soft=_KEEP_SOFT):
         """The prepared plan of (horizon hzn, control period ctrl_every plant steps) for a frozen-model call: made if absent; prepared
-        AGAIN from self.ssr (same settings, weights and warm-start switch) if the re-linearised loop has run on it -- its model blocks
-        then hold per-step models, and the library refuses it for frozen-model calls."""
+        AGAIN from self.ssr (same settings, weights, warm-start switch and soft rows) if the re-linearised loop has run on it -- its
+        model blocks then hold per-step models, and the library refuses it for frozen-model calls.  soft: the soft rows the call asks
+        for; a plan with other ones is prepared again with these."""
         if getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), int(ctrl_every)):
-            self.prepare_MPC(hzn, ctrl_every=ctrl_every)
+            self.prepare_MPC(hzn, ctrl_every=ctrl_every, soft=None if soft is self._KEEP_SOFT else soft)
+        elif soft is not self._KEEP_SOFT and self._soft_rows(soft) != self._soft_rows(self._plan_args.get("soft")):
+            self.prepare_MPC(hzn, ctrl_every=ctrl_every, **dict(self._plan_args, soft=soft))
         elif getattr(self, "_plan_foreign", False):
             self.prepare_MPC(hzn, ctrl_every=ctrl_every, **self._plan_args)
         return self._plan
@@ -931,7 +958,7 @@ class F16Batch:
         return P, q, A, l, u
 
     def _calc_MPC_action(self, p_dem, q_dem, r_dem, hzn, settings=None, return_info=False, relinearise=False,
-                         use_plan=False, weights=None, x_ref=None, ctrl_every=1, model=None, period=None):
+                         use_plan=False, weights=None, x_ref=None, ctrl_every=1, model=None, period=None, soft=None):
         """First MPC move [B,3] (dh,da,dr commands) for demands p,q,r (scalars or [B]) over horizon hzn, from the
         frozen reduced model self.ssr (env.py:385-387) and the current state.  The QP of utils.py:21-167 is solved
         on the GPU by OSQP-style ADMM (the reference calls the `osqp` package, env.py:420-422).
@@ -939,7 +966,11 @@ class F16Batch:
         prepare_MPC, x_ref is per call).  ctrl_every = k > 1 (use_plan only): the plan of control period k * self.dt
         (prepare_MPC(ctrl_every=k)) -- the solve of the multi-rate loop rollout_MPC(..., ctrl_every=k).
         model = (Ad, Bd, Cd) (state-major [81,B], [27,B], [81,B]) and period (seconds, default self.dt; the dt of the rate rows), not
-        with use_plan: the solve on that model instead of self.ssr, which is then neither read nor written."""
+        with use_plan: the solve on that model instead of self.ssr, which is then neither read nor written.
+        soft (use_plan only): the plan's soft state rows (prepare_MPC); a plan with other ones is prepared again.  A call that does not
+        name it solves with whatever the plan has."""
+        if soft is not None and not use_plan:
+            raise ValueError("soft state rows are a property of a prepared plan: use_plan=True")
         if int(ctrl_every) != 1 and not use_plan:
             raise ValueError("ctrl_every > 1 is a property of a prepared plan: use_plan=True")
         # relinearise=True: SURVEY.md 8f-2 -- the reduced model is re-derived at the CURRENT state on every call (the
@@ -957,7 +988,7 @@ class F16Batch:
         if use_plan:
             if relinearise or settings or weights or model is not self.ssr or period is not None:
                 raise ValueError("a prepared plan fixes the model, the period, the QP settings and the weights (prepare_MPC)")
-            self._frozen_plan(hzn, ctrl_every)
+            self._frozen_plan(hzn, ctrl_every, self._KEEP_SOFT if soft is None else soft)
             self._check(self.lib.f16_mpc_plan_solve_w(self._plan, _vp(self._x), _vp(dem), _vp(xr), _vp(ucmd), _vp(useq), _vp(info),
                                                       _vp(st), self._stream))
         else:
@@ -976,7 +1007,7 @@ class F16Batch:
     calc_MPC_action = _calc_MPC_action
 
     def rollout_MPC(self, nsteps, p_dem, q_dem, r_dem, hzn, traj_every=None, return_info=False, hold_command=False,
-                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None, dem_every=None, method="euler"):
+                    relinearise=False, eps=1e-5, ctrl_every=1, model_every=None, dem_every=None, method="euler", soft=None):
         """The reference's closed MPC loop (test_env.py:480-495; BASELINE config 5) as ONE launch (C-ABI f16_rollout_mpc): per step
         `cmd = _calc_MPC_action(p_dem, q_dem, r_dem, hzn); u.values[1:] = cmd; step(u.values)` from the frozen reduced model
         (env.py:49-60) with OSQP's default settings (every solve cold, as the reference's -- or warm from the step before when the plan was
@@ -1003,7 +1034,9 @@ class F16Batch:
         c // dem_every (default 1; S >= ceil(control steps / dem_every)), with relinearise and ctrl_every alike.  The demand of a control
         step is held over that step's whole horizon, so the call equals one call per row.  A 2-D p_dem with q_dem is None and
         r_dem is None stays a ready [3, B] block of constant demands.  dem_every without a history, too few rows and
-        dem_every < 1 raise ValueError.  method: "euler" only -- the loop's plant step is the Euler step; "rk4" raises ValueError."""
+        dem_every < 1 raise ValueError.  method: "euler" only -- the loop's plant step is the Euler step; "rk4" raises ValueError.
+        soft: the plan's soft state rows (prepare_MPC); the plan is prepared, or prepared again, when it has other ones.  A call that
+        does not name it runs with whatever the plan has."""
         _lib.integrator(method, rk4=False)
         nsteps, hold = int(nsteps), int(ctrl_every)
         if hold < 1 or nsteps % hold:      # (argument checks first: they need no GPU)
@@ -1028,17 +1061,21 @@ class F16Batch:
             if model_every < 1 or (relinearise and nctrl % model_every):
                 raise ValueError(f"the control steps ({nctrl}) must be a multiple of model_every ({model_every}) >= 1")
         dem = self._demands(p_dem, q_dem, r_dem) if dem_seq is None else dem_seq
-        return self._rollout_mpc_call(hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command)
+        return self._rollout_mpc_call(hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command,
+                                      self._KEEP_SOFT if soft is None else soft)
 
-    def _rollout_mpc_call(self, hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command):
+    def _rollout_mpc_call(self, hzn, nctrl, hold, dem, dem_every, traj_every, model_every, relinearise, eps, return_info, hold_command,
+                          soft=_KEEP_SOFT):
         """rollout_MPC behind its argument checks: the plan, the outputs, the ONE call into the library.  nctrl control steps of `hold`
         plant steps; dem [3,B], or [S,3,B] with dem_every control steps per row; the narrowest entry point that can run the loop."""
         sched, nsteps = dem_every is not None, nctrl * hold
         wide = sched or hold > 1      # the _hold / _sched parameter lists: nctrl, hold and the plant's dt beside the oldest calls' own
         if not relinearise:
-            self._frozen_plan(hzn, hold)
+            self._frozen_plan(hzn, hold, soft)
         elif getattr(self, "_plan", None) is None or (self._plan_hzn, self._plan_ctrl_every) != (int(hzn), hold):
-            self.prepare_MPC(hzn, ctrl_every=hold)
+            self.prepare_MPC(hzn, ctrl_every=hold, soft=None if soft is self._KEEP_SOFT else soft)
+        elif soft is not self._KEEP_SOFT and self._soft_rows(soft) != self._soft_rows(self._plan_args.get("soft")):
+            self.prepare_MPC(hzn, ctrl_every=hold, **dict(self._plan_args, soft=soft))
         if (relinearise or wide) and not self._plan_default_settings:
             raise ValueError("relinearise=True, ctrl_every > 1 and demand histories need a plan with equilibrated solves (scaling > 0)")
         k = int(traj_every or 1)

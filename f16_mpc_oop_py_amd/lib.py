@@ -29,6 +29,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 F16_ST = dict(ALPHA1=1, ALPHA2=2, BETA=4, EL=8, ENVELOPE=16, NONFINITE=32, QP_MAXITER=64, QP_INFEASIBLE=128)
 F16_ST_ENV_STATE = lambda k: 1 << (8 + k)      # with ENVELOPE: state k was outside its box (env.py:117-124)
 F16_ST_LOOP_STALL = 1 << 26                    # f16_rollout_mpc gave up waiting for the aircraft's previous step (a guard; never observed)
+F16_ST_QP_SOFT_ACTIVE = 1 << 27                # f16_mpc_plan_soft_rows: the returned solve has a soft state row outside its [l, u]
 F16_FLAG_FIX_CLR = 1
 F16_FLAG_NO_ENVELOPE = 2
 F16_FLAG_ONE_LANE = 4          # rollouts: the one-lane-per-aircraft kernel whatever the batch size (results independent of B)
@@ -323,6 +324,8 @@ def load():
             L.f16_rollout_mpc_relin_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, d, d, d, i, u, vp]
             L.f16_rollout_lqr_relin_sched.argtypes = [vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, i, i, u, d, d, d, i, u, vp]
         L.f16_mpc_plan_warm_start.argtypes = [vp, i]
+        if hasattr(L, "f16_mpc_plan_soft_rows"):    # (absent from an older library loaded through F16HIP_SO for an A/B run)
+            L.f16_mpc_plan_soft_rows.argtypes = [vp, vp]
         L.f16_mpc_plan_destroy.argtypes = [vp]
         L.f16_mpc_plan_destroy.restype = None
     _LIB = L

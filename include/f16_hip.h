@@ -54,6 +54,7 @@ typedef struct f16_ctx f16_ctx;
 #define F16_ST_QP_INFEASIBLE 128 /* OSQP primal-infeasibility certificate met: command = NaN  */
 #define F16_ST_LOOP_STALL (1 << 26) /* f16_rollout_mpc: a wavefront gave up waiting (tens of seconds) for the previous step of this
                                        aircraft and went on regardless -- a guard that lets the grid drain; never observed          */
+#define F16_ST_QP_SOFT_ACTIVE (1 << 27) /* f16_mpc_plan_soft_rows: the returned solve has a soft state row outside its [l, u]        */
 
 /* behaviour flags */
 #define F16_FLAG_FIX_CLR 1u      /* use the real CLr table (reference never loads it: hifi_F16_AeroData.c:964-972) */
@@ -670,6 +671,20 @@ int f16_mpc_plan_solve_w(f16_mpc_plan *plan, const double *x, const double *dem,
  * results then differ from the cold start within the termination tolerance).  Switching it on or off forgets the
  * stored solution; a solve that did not converge is not reused. */
 int f16_mpc_plan_warm_start(f16_mpc_plan *plan, int on);
+/* Optional: SOFT STATE ROWS.  h_w9 (host): nine penalty weights in MPC-state order (phi, theta, alpha, beta, p, q, r, lf1, lf2).  A
+ * state row i with w_i > 0 is no constraint any more: every solve on the plan minimises
+ *     1/2 u'Pu + q'u + sum over the soft rows of (w_i / 2) dist(a_i'u, [l_i, u_i])^2     subject to the other rows,
+ * so a prediction that leaves the state box no longer makes the QP infeasible.  No slack variables: in the ADMM iteration the z-update
+ * of a soft row is v = zr + y / rho_i, zc = clip(v, l, u), z = zc + kappa_i (v - zc), kappa_i = rho_i / (rho_i + c w_i / E_i^2); the
+ * primal-infeasibility certificate treats it as a row without bounds; everything else is the hard solve's.  Command and rate rows stay
+ * hard, and they alone can still make a QP infeasible (NaN command, F16_ST_QP_INFEASIBLE, F16_FLAG_HOLD_COMMAND as before).
+ * F16_ST_QP_SOFT_ACTIVE: the z of some soft row of the returned (not infeasible) solve lies outside its [l, u]; sticky in the loops.
+ * The penalty is quadratic and therefore inexact: an active soft row is violated slightly even when the hard QP is feasible.
+ * NULL or all zeros switches soft rows off; the plan then is bit for bit what it was.  F16_EINVAL: a negative, NaN or infinite weight; a
+ * positive weight on phi, theta or lf1 (no bounds); a plan the one-wavefront solver does not serve (hzn > 30, scaling = 0).  Switching
+ * forgets a stored warm-start solution.  Honoured by f16_mpc_plan_solve(_w) and the six f16_rollout_mpc* calls (a re-linearised call
+ * keeps the weights); their "equals the host loop" contracts hold unchanged, with the softened f16_mpc_plan_solve in the host loop. */
+int f16_mpc_plan_soft_rows(f16_mpc_plan *plan, const double *h_w9);
 void f16_mpc_plan_destroy(f16_mpc_plan *plan);      /* waits for the plan's own stream only */
 
 /* utils.py:21-167 setup_OSQP alone for aircraft b (tests): h_P[n*n] h_q[n] h_A[(m rows)*n] h_l h_u on the
