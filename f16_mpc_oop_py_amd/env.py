@@ -170,12 +170,20 @@ class F16Batch:
         return out, st
 
     # ------------------------------------------------------------------ env.py:65-103
-    def _calc_xdot(self, x=None, u=None):
-        """xdot [B,18] for states x [B,18] and inputs u [B,4] (defaults: resident x.values/u.values)."""
+    def _calc_xdot(self, x=None, u=None, wind=None, gust=None):
+        """xdot [B,18] for states x [B,18] and inputs u [B,4] (defaults: resident x.values/u.values).
+        wind ([3] or [B,3]: velocity of the air mass over the ground, north / east / down, ft/s) and gust ([3] or [B,3]: gust velocity
+        in body axes, ft/s) evaluate the derivative in moving air (f16_xdot_wind_batch); without them the call is what it always was."""
         xs = self._x if x is None else self._soa(x, 18)
         us = self._u if u is None else self._soa(u, 4)
         out = torch.empty_like(xs)
         st = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        if wind is not None or gust is not None:
+            ws, gs = (None if v is None else self._soa(v, 3) for v in (wind, gust))
+            self._check(self.lib.f16_xdot_wind_batch(self.ctx.handle, _vp(xs), _vp(us), _vp(ws), _vp(gs), _vp(out), _vp(st), self.B, self.B,
+                                                     self.xcg, self.fi_flag, self.flags, self._stream))
+            self.last_status = st
+            return out.t()
         self._check(self.lib.f16_xdot_batch(self.ctx.handle, _vp(xs), _vp(us), _vp(out), _vp(st), self.B, self.B,
                                             self.xcg, self.fi_flag, self.flags, self._stream))
         self.last_status = st
@@ -217,7 +225,39 @@ class F16Batch:
         four stages of a step) -- for a step coarser than the reference's 1 ms, where Euler is no longer accurate."""
         return self._rollout_call(self._u if action is None else self._soa(action, 4), nsteps, traj_every, method=_lib.integrator(method))
 
-    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER):
+    def _air(self, wind, gusts, gust_every, nsteps):
+        """The `wind=` / `gusts=` / `gust_every=` keywords of the rollouts -> None for still air, else (lib.Wind, the tensors it points
+        at, the GustModel or None).  wind: [3] or [B, 3], ft/s north / east / down.  gusts: a [Sg, B, 3] array of body-axis gust
+        velocities, step t reading row t // gust_every (default 1; Sg >= ceil(nsteps / gust_every)), or a wind.GustModel for
+        generation inside the kernel.  ValueError for anything else: argument checks, no GPU call."""
+        from .wind import GustModel
+        if wind is None and gusts is None:
+            if gust_every is not None:
+                raise ValueError("gust_every goes with a gusts array")
+            return None
+        air, keep, model = _lib.Wind(), [], None
+        if wind is not None:
+            keep.append(self._soa(wind, 3))
+            air.wind_ned = keep[-1].data_ptr()
+        if isinstance(gusts, GustModel):
+            if gust_every is not None:
+                raise ValueError("a GustModel carries its own row period (every=); gust_every goes with a gusts array")
+            model = gusts
+            keep += list(model.device_state(self.B, self.dt, self.device))
+            air.ga, air.gb, air.gstate = (t.data_ptr() for t in keep[-3:])
+            air.gust_hold, air.seed, air.row0 = model.every, model.seed, model.row
+        elif gusts is not None:
+            g = gusts if isinstance(gusts, torch.Tensor) else torch.as_tensor(np.asarray(gusts, dtype=np.float64))
+            k = 1 if gust_every is None else int(gust_every)
+            if g.dim() != 3 or tuple(g.shape[1:]) != (self.B, 3):
+                raise ValueError(f"gusts must be [Sg, {self.B}, 3] or a wind.GustModel, not {tuple(g.shape)}")
+            if k < 1 or (int(nsteps) + k - 1) // k > g.shape[0]:
+                raise ValueError(f"{nsteps} steps with gust_every {k} (>= 1) need {(max(int(nsteps), 0) + max(k, 1) - 1) // max(k, 1)} gust rows; gusts: {g.shape[0]}")
+            keep.append(g.to(device=self.device, dtype=torch.float64).permute(0, 2, 1).contiguous())
+            air.gust_seq, air.gust_hold = keep[-1].data_ptr(), k
+        return air, keep, model
+
+    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER, air=None):
         """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
         into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
         around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values.  method F16_INT_RK4:
@@ -225,6 +265,13 @@ class F16Batch:
         traj = self._samples(nsteps, traj_every)
         # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
         name, law, u_out = ("f16_rollout", (), ()) if K is None else ("f16_rollout_lqr", (_vp(K), _vp(dem)), (_vp(self._u),))
+        if air is not None:      # (_air) the _wind entry points: the scheduled parameter list with the air behind the schedule
+            self._check(getattr(self.lib, name + "_wind")(self.ctx.handle, _vp(self._x), _vp(u), *law, ctypes.byref(air[0]), _vp(traj), *u_out,
+                                                          _vp(self.status), self.B, self.B, int(nsteps), max(int(nsteps), 1) if hold is None else hold,
+                                                          int(traj_every or 1), self.dt, self.xcg, self.fi_flag, int(method), self.flags, self._stream))
+            if air[2] is not None:
+                air[2].advance(nsteps)
+            return traj
         rule = ()
         if method != _lib.F16_INT_EULER:
             name, held, rule = name + "_rk", (max(int(nsteps), 1) if hold is None else hold,), (int(method),)
@@ -235,14 +282,15 @@ class F16Batch:
                                             self.flags, self._stream))
         return traj
 
-    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler"):
+    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler", wind=None, gusts=None, gust_every=None):
         """The reference's call pattern `u.values = action; step(u.values)` with an action that changes during the run
         (env.py:105-130; the doublets of Nguyen_m/runF16Sim.m) in ONE launch (C-ABI f16_rollout_sched): step t takes
         actions[t // hold], a zero-order hold.  actions: [S, B, 4] (numpy or torch), or a state-major [S, 4, B] fp64 tensor
         already on the device, which is taken as it is, without a copy (for B == 4 a 3-D device tensor is read as [S, B, 4];
         pass a host array or a non-contiguous view to say otherwise).  nsteps defaults to S * hold and needs
         S >= ceil(nsteps / hold) rows.  Returns what `rollout` returns; u.values ends up holding the last row used, as the
-        reference's caller leaves it.  method="rk4": Runge-Kutta steps, each row held over the stages of its steps (f16_rollout_rk)."""
+        reference's caller leaves it.  method="rk4": Runge-Kutta steps, each row held over the stages of its steps (f16_rollout_rk).
+        wind= / gusts= / gust_every= (see _air): the same rollout in steady wind and gusts (f16_rollout_wind), both methods."""
         method = _lib.integrator(method)
         t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
         if t.dim() != 3:
@@ -255,7 +303,7 @@ class F16Batch:
             raise ValueError(f"actions must be [S, {self.B}, 4] or a contiguous fp64 [S, 4, {self.B}] tensor on {self.device}, "
                              f"not {tuple(t.shape)} ({t.dtype}, {t.device})")
         hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
-        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold, method=method)
+        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold, method=method, air=self._air(wind, gusts, gust_every, nsteps))
         self._u.copy_(seq[(nsteps - 1) // hold])
         return traj
 
@@ -685,7 +733,8 @@ class F16Batch:
         return seq.contiguous(), k
 
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
-                    R=None, hold=None, method="euler", schedule=None, gains_every=1, return_info=False):
+                    R=None, hold=None, method="euler", schedule=None, gains_every=1, return_info=False, wind=None, gusts=None,
+                    gust_every=None):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -709,7 +758,12 @@ class F16Batch:
         in the gain table at the altitude and airspeed of the state at the start of every k-th step and held in between, in one
         launch of f16_rollout_lqr_gs, for both methods; the thrust command is held.  Not combined with K, linear=True or
         relinearise=True, and gains_every >= 1 (ValueError).  return_info=True (with a schedule) returns (traj, info) with
-        info["gs_out"] [B]: at how many gain updates the aircraft was outside the table's grid (the edge cell is extended flat there)."""
+        info["gs_out"] [B]: at how many gain updates the aircraft was outside the table's grid (the edge cell is extended flat there).
+        wind= / gusts= / gust_every= (see _air): the frozen-gain nonlinear loop in steady wind and gusts (f16_rollout_lqr_wind), both
+        methods -- the disturbance-rejection loop; the controller reads the state, not the air data.  Not combined with linear=True,
+        relinearise=True or schedule= (ValueError)."""
+        if (wind is not None or gusts is not None) and (linear or relinearise or schedule is not None):
+            raise ValueError("wind= / gusts= run on the nonlinear loop with a fixed gain (not with linear=True, relinearise=True or schedule=)")
         if schedule is not None:
             if K is not None or linear or relinearise:
                 raise ValueError("schedule= takes the gain from the table: not combined with K, linear=True or relinearise=True")
@@ -766,7 +820,8 @@ class F16Batch:
             u0s = torch.cat((self._u[0:1], self._u_init[1:4]), 0).contiguous()
         else:
             u0s = self._soa(u0, 4)
-        return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq, method=method)
+        return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq, method=method,
+                                  air=self._air(wind, gusts, gust_every, nsteps))
 
     def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
                           hold=None):

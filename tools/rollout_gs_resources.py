@@ -26,12 +26,12 @@ WIDTHS = (5, 5, 5, 15, 11, 11, 11, 8)
 SRC = os.path.join("f16_mpc_oop_py_amd", "csrc", "f16_dynamics.hip")
 
 
-def assembly(root):
-    """{function symbol: [instruction lines]} of f16_dynamics.hip under `root`"""
+def assembly(root, src=SRC):
+    """{function symbol: [instruction lines]} of `src` (default: f16_dynamics.hip) under `root`"""
     flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "dyn.s")
-        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(root, SRC)],
+        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(root, src)],
                        capture_output=True, text=True, check=True)
         text = open(out).read()
     symbols = set(re.findall(r"^\s*\.type\s+([\w.$]+),@function", text, re.M))
