@@ -750,13 +750,17 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // otherwise move that arithmetic behind barrier B and contract it differently.  GROUPS = 2 keeps one shared loop (same text).
 // GROUPS = 2 (4096 < B <= 8192): two independent 16-aircraft groups per workgroup share the LDS table image, one role
 // wave of each on every SIMD -- the two dependency chains interleave.
-// GROUPS = 1 takes the constants of its sin/cos pair and of the atmosphere's exp / log from SCALAR registers: each role loads
-// its own from QUAD_K (constant memory, f16_plant.hpp) at the top of its part of a step and uses them as the scalar operand of
-// its FMAs.  (The loads were meant to land while the role waits for its LDS reads; in the ISA they are issued BEHIND that wait --
-// wave 2: behind the sample block, wave 3 and wave 0's psi: with the wait for them on the next instruction.  DESIGN.md.)  As literals they cost the
-// trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28 vector registers for
-// the sin/cos table; kept in scalar registers for the whole loop (43 doubles) they push loop masks out into lane moves.
-// Same operations, same operands, same order.
+// GROUPS = 1 takes the constants of its sin/cos pair and of the atmosphere's exp / log from REGISTERS THAT HOLD THEM FOR THE WHOLE
+// LAUNCH: each role loads its own table from QUAD_K (constant memory, f16_plant.hpp) once, in front of its own step loop
+// (f16_quad_steps.inc), and no step loads it again.  Waves 0 (psi) and 3 (atmosphere) keep theirs in scalar registers, the
+// constant the scalar operand of a three-address FMA; wave 2 (trigonometry) keeps its 21 doubles in lane-uniform vector registers
+// -- its loop's lane masks and sample scalars leave no room for 42 scalar registers -- and issues the same FMA with three vector
+// operands.  (Loaded at the top of a role's part of every step, as before, the loads were issued BEHIND the role's wait for its
+// LDS reads and the first multiply waited for them: 228 / 625 / 135 cycles per step on waves 2 / 3 / 0, DESIGN.md.)  As literals
+// the constants cost the trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28
+// vector registers for the sin/cos table.  Same operations, same operands, same order.
+// Wave 2 publishes x[0..5] and tests x[2] where they become final, behind barrier B, under the wait for the totals; between the
+// last Euler update and barrier A it writes x[6..8] and its envelope flag only.
 template <int GROUPS, bool LQR = false, bool SCHED = false>
 __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a) {
   constexpr int NA = 16 * GROUPS;
@@ -813,11 +817,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
       ra.init(a, LQR ? 3 : 4, a.out + b, rs * a.ld, role == 3);
       ra.settle();
     }
-    if (G1 && role == 0 && s == 0) {                       // sin / cos of the first step's psi (the loop's first barrier publishes it)
-      double sp, cp;
-      F16_SINCOS_K(reloaded(QUAD_K.sc), x[5], &sp, &cp);    // (the form of the loop: on a NaN psi the two differ in the sign of the NaN)
-      xpsi[1][ac] = sp; xpsi[2][ac] = cp;
-    }
+    // (GROUPS = 1: wave 0 evaluates sin / cos of the first step's psi in front of its own loop, with the table it loads there)
 #ifdef F16_EXP_STAMPQ
     unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, t0 = __builtin_amdgcn_s_memtime();
     // -DF16_EXP_STAMPQ (or =1): every stamp waits for ALL counters, wave 2's sample stores included.  -DF16_EXP_STAMPQ=2: for the
@@ -829,14 +829,8 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
 #define QSTAMP_WAIT 0
 #endif
 #define QSTAMP(acc) { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); unsigned long long t1 = __builtin_amdgcn_s_memtime(); acc += t1 - t0; t0 = t1; }
-    // the wait for a role's QUAD_K loads: QK_BEGIN in front of reloaded() (LDS reads and earlier scalar loads have landed), QK_END behind it
-    unsigned long long tK = 0, tk0 = 0;
-#define QK_BEGIN { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); tk0 = __builtin_amdgcn_s_memtime(); }
-#define QK_END { __builtin_amdgcn_s_waitcnt(QSTAMP_WAIT); tK += __builtin_amdgcn_s_memtime() - tk0; }
 #else
 #define QSTAMP(acc)
-#define QK_BEGIN
-#define QK_END
 #endif
     // The step loop (f16_quad_steps.inc).  GROUPS = 1: one copy per role behind a scalar switch; GROUPS = 2: one shared loop, as
     // before (four loops spill more there).
@@ -868,7 +862,6 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
       double *d = a.traj + 18 * a.ld * 2 + role * 4;
       d[0] = (double)tD; d[1] = (double)tA; d[2] = (double)tB; d[3] = (double)tC;
       a.traj[18 * a.ld * 2 + a.ld + role] = (double)tstage;   // (state row 1 of the same sample; once per launch, not per step)
-      a.traj[18 * a.ld * 2 + a.ld + 4 + role] = (double)tK;
     }
 #endif
     // ---- write the final state back (owners), flags

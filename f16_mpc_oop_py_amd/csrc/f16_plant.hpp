@@ -71,6 +71,31 @@ F16_DEV double fma_svv(double a, double b, double c) {        // a * b + c, a un
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "s"(a), "v"(b), "v"(c));
   return d;
 }
+F16_DEV double fma_vvv(double a, double b, double c) {        // the same instruction, same operand order, the uniform value in a vector register
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+// Where a caller of exp_k / log_k / sincos_bf_k holds the table (the operand class): KScalar -- scalar registers, the constant the
+// scalar operand of the FMA; KVector -- lane-uniform vector registers (a role loop that has no scalar registers to spare keeps its
+// table there for the whole launch: the FMA then issues with three vector operands, 6.1 cycles against 4.6 at one wave per SIMD).
+struct KScalar {
+  static F16_DEV double vvk(double a, double b, double k) { return fma_vvs(a, b, k); }
+  static F16_DEV double kvv(double k, double b, double c) { return fma_svv(k, b, c); }
+};
+struct KVector {
+  static F16_DEV double vvk(double a, double b, double k) { return fma_vvv(a, b, k); }
+  static F16_DEV double kvv(double k, double b, double c) { return fma_vvv(k, b, c); }
+};
+// a value held in a vector register from here on: the copy is made here, once, and not in front of every use (a table kept across a
+// loop: the Horner start coefficients, which are vector operands in either class; every entry under KVector)
+F16_DEV void in_vgpr(double &x) { asm volatile("" : "+v"(x)); }
+template <typename T>
+F16_DEV void table_in_vgprs(T &t) {
+  double *d = reinterpret_cast<double *>(&t);
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / sizeof(double); ++i) in_vgpr(d[i]);
+}
 
 // ---- exp(0.14 log tfac) of F16_FAST_POW with its constants as uniform values
 // The device library's exp and log are inlined from bitcode, so their literals cannot be redirected; in the quad rollout they
@@ -94,6 +119,7 @@ constexpr PowK POW_K = {
     {1.53670161652585818e-01, 1.52503063567000663e-01, 1.81863527724766383e-01, 2.22221384831011309e-01, 2.85714293974435540e-01,
      3.99999999961319630e-01, 6.66666666666728247e-01}};
 
+template <typename OP = KScalar>
 F16_DEV double log_k(const PowK &K, double x) {
   const double m = __builtin_amdgcn_frexp_mant(x);
   const bool lo = m < K.two_thirds;
@@ -115,9 +141,9 @@ F16_DEV double log_k(const PowK &K, double x) {
   const double h = fma(r, d32, q);                         // quotient, high part
   const double l = fma(r, d32, -fma(-ym1, r, h));          // low part
   const double z = h * h;
-  double c = fma_vvs(z, K.L[0], K.L[1]);
+  double c = OP::vvk(z, K.L[0], K.L[1]);
 #pragma unroll
-  for (int k = 2; k < 7; ++k) c = fma_vvs(z, c, K.L[k]);
+  for (int k = 2; k < 7; ++k) c = OP::vvk(z, c, K.L[k]);
   const double a44 = __builtin_ldexp(h, 1), a45 = __builtin_ldexp(l, 1);
   const double t46 = h * z;
   const double u48 = fma(t46, c, a44);
@@ -128,9 +154,9 @@ F16_DEV double log_k(const PowK &K, double x) {
   // + e ln 2 in two parts
   const double f = (double)e;
   const double g56n = f * K.nln2_hi;
-  const double g59 = fma_svv(K.ln2_lo, f, fma_svv(K.ln2_hi, f, g56n));
-  const double g60 = fma_svv(K.ln2_hi, f, g59);
-  const double g62 = g59 - fma_svv(K.nln2_hi, f, g60);
+  const double g59 = OP::kvv(K.ln2_lo, f, OP::kvv(K.ln2_hi, f, g56n));
+  const double g60 = OP::kvv(K.ln2_hi, f, g59);
+  const double g62 = g59 - OP::kvv(K.nln2_hi, f, g60);
   const double w63 = g60 + u52;
   const double w64 = w63 - g60;
   const double w68 = (u52 - w64) + (g60 - (w63 - w64));
@@ -145,12 +171,13 @@ F16_DEV double log_k(const PowK &K, double x) {
   return x == 0.0 ? -__builtin_inf() : res;
 }
 
+template <typename OP = KScalar>
 F16_DEV double exp_k(const PowK &K, double x) {
   const double n = rint(x * K.log2e);
-  const double r = fma_svv(K.nln2_lo, n, fma_svv(K.nln2_hi, n, x));      // (as the library's fma(-n, ln2, x) compiles: sign on the constant)
-  double c = fma_vvs(r, K.E[0], K.E[1]);
+  const double r = OP::kvv(K.nln2_lo, n, OP::kvv(K.nln2_hi, n, x));      // (as the library's fma(-n, ln2, x) compiles: sign on the constant)
+  double c = OP::vvk(r, K.E[0], K.E[1]);
 #pragma unroll
-  for (int k = 2; k < 10; ++k) c = fma_vvs(r, c, K.E[k]);
+  for (int k = 2; k < 10; ++k) c = OP::vvk(r, c, K.E[k]);
   c = fma(r, c, 1.0);
   c = fma(r, c, 1.0);
   double res = __builtin_ldexp(c, (int)n);
@@ -201,7 +228,8 @@ constexpr SinCosK SINCOS_K = {
 // Both tables as ONE object in constant memory, for code that wants them in scalar registers.  Read at a constant offset the
 // values fold back into literals; reloaded() hides the address (passed through a scalar register the compiler cannot see through), so
 // that the values are LOADED -- by scalar loads, the address being uniform -- where the call stands, on every pass through it.
-// The scalar unit only reads here.
+// The quad rollout calls it once per launch, in front of each role's step loop (f16_quad_steps.inc), and keeps the table in
+// registers across the loop: no step loads it.  The scalar unit only reads here.
 struct QuadK { SinCosK sc; PowK pw; };
 static __constant__ const QuadK QUAD_K = {SINCOS_K, POW_K};
 template <typename T>
@@ -252,25 +280,28 @@ F16_DEV void sincos_bf(double x, double *sn, double *cs) {
 // 64-bit register move in front of every Horner step (the compiler prefers the two-address v_fmac_f64) and 28 vector registers
 // for the table; an fp64 FMA whose addend is the scalar operand needs neither and issues faster (4.6 against 6.1 cycles at
 // one wave per SIMD).  The FMA is pinned to its three-address form: it is the plain vector FMA, nothing else.
+template <typename OP = KScalar>
 F16_DEV void sincos_bf_k(const SinCosK &K, double x, double *sn, double *cs) {
   const double n = rint(x * K.two_over_pi);
   // (operand for operand what the compiler makes of fma(-n, C, r) with a literal C: (-C) n + r, the sign on the constant --
   //  on a NaN argument the sign of the result follows the operand that carries it)
-  double r = fma_svv(K.npio2[0], n, x);
-  r = fma_svv(K.npio2[1], n, r);
-  r = fma_svv(K.npio2[2], n, r);
+  double r = OP::kvv(K.npio2[0], n, x);
+  r = OP::kvv(K.npio2[1], n, r);
+  r = OP::kvv(K.npio2[2], n, r);
   const double z = r * r;
   double p = K.S[7], q = K.C[8];
 #pragma unroll
-  for (int k = 6; k >= 0; --k) p = fma_vvs(p, z, K.S[k]);
+  for (int k = 6; k >= 0; --k) p = OP::vvk(p, z, K.S[k]);
 #pragma unroll
-  for (int k = 7; k >= 0; --k) q = fma_vvs(q, z, K.C[k]);
+  for (int k = 7; k >= 0; --k) q = OP::vvk(q, z, K.C[k]);
   const double s0 = fma(r * z, p, r), c0 = fma(z, q, 1.0);
   sincos_quadrant(n, s0, c0, sn, cs);
 }
 #define F16_SINCOS(x, s, c) sincos_bf(x, s, c)
 #define F16_SINCOS_K(K, x, s, c) sincos_bf_k(K, x, s, c)
+#define F16_SINCOS_KC(OP, K, x, s, c) sincos_bf_k<OP>(K, x, s, c)      // the table in the registers of operand class OP
 #else
+#define F16_SINCOS_KC(OP, K, x, s, c) sincos(x, s, c)
 #define F16_SINCOS(x, s, c) sincos(x, s, c)
 #define F16_SINCOS_K(K, x, s, c) sincos(x, s, c)
 #endif

@@ -3,14 +3,60 @@
 // below is resolved then, and that copy keeps the statements, the published states and the loop-carried registers of its role
 // alone), the wave's role index itself in the shared loop (GROUPS = 2).  Every copy executes the same barriers: A and B per step,
 // A alone on the extra trip.  Text, not a function: the shared loop then compiles exactly as it did inside the kernel.
+// GROUPS = 1, in front of a role's loop: the role's constants (QUAD_K, f16_plant.hpp) are loaded HERE, once per launch and group of
+// aircraft, and stay in registers across the loop -- wave 2 and wave 0 the sin/cos table, wave 3 the exp / log table; no step
+// loads them again.  Wave 0 evaluates the first step's psi with that table (the form of the loop: on a NaN psi the literal form
+// differs in the sign of the NaN, and a continued rollout must give the bits of one launch).  Wave 2 publishes x[0..5] and tests
+// x[2] for the first trip; from then on it does both where these states become final, behind barrier B (below).
+    [[maybe_unused]] SinCosK ksc = {};
+    [[maybe_unused]] PowK kpw = {};
+    [[maybe_unused]] bool env_h = false;                   // wave 2: x[2] outside its box, tested where x[2] was last advanced
+    if constexpr (G1) {
+      if (wave == 0 || wave == 2) ksc = reloaded(QUAD_K.sc);
+      if (wave == 3) kpw = reloaded(QUAD_K.pw);
+      // operand class (f16_plant.hpp): waves 0 and 3 keep the table in scalar registers (KScalar) and only the two Horner start
+      // coefficients, vector operands of their FMA, in vector registers; wave 2's loop has no scalar registers for 42 more (its lane
+      // masks and the sample's scalars went out into lane moves), so its whole table stays in lane-uniform vector registers (KVector)
+      if (wave == 2) table_in_vgprs(ksc);
+      if (wave == 0) { in_vgpr(ksc.S[7]); in_vgpr(ksc.C[8]); }
+      if (wave == 3) { in_vgpr(kpw.E[0]); in_vgpr(kpw.L[0]); }
+      if (wave == 0 && s == 0) {                           // sin / cos of the first step's psi (the loop's first barrier publishes it)
+        double sp, cp;
+        F16_SINCOS_K(ksc, x[5], &sp, &cp);
+        xpsi[1][ac] = sp; xpsi[2][ac] = cp;
+      }
+      if (wave == 2) {
+        env_h = envchk && (x[2] < 0 || x[2] > 100000);
+        if (s == 0) {
+#pragma unroll
+          for (int k = 0; k < 6; ++k) xs[k][ac] = x[k];
+        }
+      }
+      // The states a role neither owns nor reads are dead from here on: the epilogue writes back a role's own states only, but it
+      // stands behind the join of the four loops, where the compiler no longer knows the role, and kept all 18 in registers across
+      // every role's loop.  (Wave 3's loop is left alone, and so are the commands and LQR rows it owns: clearing those for the other
+      // roles moved two fp64 canonicalisations of wave 3's out of its loop -- the same values, but not the same instruction sequence.)
+      if (wave != 3) {
+#pragma unroll
+        for (int k = 0; k < 18; ++k)
+          if (!(wave == 2 ? k < 9 : (wave == 1 && k >= 9 && k < 12))) x[k] = 0;
+      }
+    }
     for (int t = 0; t <= a.nsteps; ++t) {                  // the extra trip only publishes + stores the final sample
       // ---- step start: envelope test on the owned states (env.py:117-124), publish them
       if (wave == 2) {
-        xenv[0][ac] = envchk && (x[2] < 0 || x[2] > 100000 || x[6] < 0 || x[6] > 900 || x[7] < -20. || x[7] > 90 ||
-                                 x[8] < -30. || x[8] > 30);
-        if (s == 0) {
+        if constexpr (G1) {
+          // x[0..5] and the x[2] test were published behind barrier B of the last step (in front of the loop for the first trip):
+          // what stands between the last Euler update and barrier A is x[6..8], one state per sub-lane (all four hold the same x), and the flag
+          xenv[0][ac] = env_h | (envchk & ((x[6] < 0) | (x[6] > 900) | (x[7] < -20.) | (x[7] > 90) | (x[8] < -30.) | (x[8] > 30)));
+          xs[6 + (s < 3 ? s : 2)][ac] = s == 0 ? x[6] : (s == 1 ? x[7] : x[8]);   // (sub-lanes 2 and 3 both write x[8]: no lane mask)
+        } else {
+          xenv[0][ac] = envchk && (x[2] < 0 || x[2] > 100000 || x[6] < 0 || x[6] > 900 || x[7] < -20. || x[7] > 90 ||
+                                   x[8] < -30. || x[8] > 30);
+          if (s == 0) {
 #pragma unroll
-          for (int k = 0; k < 9; ++k) xs[k][ac] = x[k];
+            for (int k = 0; k < 9; ++k) xs[k][ac] = x[k];
+          }
         }
       } else if (wave == 1) {
         xenv[1][ac] = envchk && (x[9] < -300 || x[9] > 300 || x[10] < -100 || x[10] > 100 || x[11] < -50 || x[11] > 50);
@@ -104,12 +150,8 @@
         // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
         const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
         double sn, cs, sb, s_psi, c_psi;
-        if constexpr (G1) {
-          QK_BEGIN
-          const auto ksc = reloaded(QUAD_K.sc);
-          QK_END
-          F16_SINCOS_K(ksc, ang, &sn, &cs);
-        } else F16_SINCOS(ang, &sn, &cs);
+        if constexpr (G1) F16_SINCOS_KC(KVector, ksc, ang, &sn, &cs);   // (the table loaded in front of the loop, into vector registers)
+        else F16_SINCOS(ang, &sn, &cs);
         // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
         //  changes x[1] in the last place)
         if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
@@ -163,12 +205,9 @@
         if (vt <= 0.01) vt = 0.01;
         double mach, qbar, ps;
         double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
-        if constexpr (G1) {
-          QK_BEGIN
-          const PowK pk = reloaded(QUAD_K.pw);
-          QK_END
-          atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(pk, 0.14 * log_k(pk, tfac)); });
-        } else
+        if constexpr (G1)                                  // (the table loaded in front of the loop)
+          atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(kpw, 0.14 * log_k(kpw, tfac)); });
+        else
           atmos_dev(xa[2], vt, mach, qbar, ps);
         if (s == 0) { xt[6][ac] = qbar; xt[7][ac] = ps; }
         if (live) {
@@ -211,9 +250,28 @@
       QSTAMP(tC)
       // ---- second half: force equations on wave 2 || moment equations on wave 1
       if (wave == 2) {
+        int sx = 0;                                        // the table waves' status bits and the totals this wave uses, as read from LDS
+        double t0_ = 0, t1_ = 0, t3_ = 0, t8_ = 0, t6_ = 0;
+        if constexpr (G1) {
+          // x[0..5] were advanced in the first half and are final: publish them and test x[2] HERE, under the wait for the totals,
+          // not behind the second half.  Nobody reads xs between barrier B and the next barrier A -- the step inputs and the sample
+          // are read behind A, the second halves read xt / xst (waves 1, 2) and xpsi (wave 0) -- and every read of the first half
+          // has landed before B.  A frozen aircraft publishes the values it was frozen with.
+          // The second half's own reads are issued first (whether or not the aircraft is live), the six writes behind them: the
+          // writes take issue slots under the wait for the reads.
+          sx = xst[0][ac] | xst[1][ac];
+          t0_ = xt[0][ac]; t1_ = xt[1][ac]; t3_ = xt[3][ac]; t8_ = xt[8][ac]; t6_ = xt[6][ac];
+          __builtin_amdgcn_sched_barrier(0);               // every read above, every write below
+          env_h = envchk & ((x[2] < 0) | (x[2] > 100000));   // (no short cut: two compares cost less than a jump round them)
+          if (s == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) xs[k][ac] = x[k];
+          }
+        }
         if (live) {
-          st |= xst[0][ac] | xst[1][ac];
-          const double Cx = xt[0][ac], Cz = xt[1][ac], Cy = xt[3][ac] + xt[8][ac], qbar = xt[6][ac];
+          if constexpr (!G1) { sx = xst[0][ac] | xst[1][ac]; t0_ = xt[0][ac]; t1_ = xt[1][ac]; t3_ = xt[3][ac]; t8_ = xt[8][ac]; t6_ = xt[6][ac]; }
+          st |= sx;
+          const double Cx = t0_, Cz = t1_, Cy = t3_ + t8_, qbar = t6_;
           const double m = 636.94, S = 300.0;
           const double qsm = F16_DIVC(qbar * S, m);
           const double Udot = fu0 + qsm * Cx;                                                          // :383-387
@@ -246,9 +304,6 @@
         }
       } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
         double sp, cp;
-        QK_BEGIN
-        const auto ksc = reloaded(QUAD_K.sc);
-        QK_END
         F16_SINCOS_K(ksc, xpsi[0][ac], &sp, &cp);
         xpsi[1][ac] = sp; xpsi[2][ac] = cp;
       }

@@ -17,5 +17,4 @@ d = traj[2].reshape(-1)[:16].cpu().numpy().reshape(4, 4) / T
 np.set_printoptions(linewidth=200, precision=0, suppress=True)
 print("cycles per step; rows = waves (long, lat, trig/forces, atmos/act); cols = second half+publish, barrier A, first half, barrier B")
 print(d, d.sum(1))
-print("cycles per step between the issue of a role's QUAD_K loads and their arrival, per wave:", traj[2].reshape(-1)[B + 4:B + 8].cpu().numpy() / T)
 print("cycles from kernel entry to the first barrier (table staging), per wave:", traj[2].reshape(-1)[B:B + 4].cpu().numpy())
