@@ -232,6 +232,10 @@ __device__ __forceinline__ int dare_sda_wave(const double *A0, const double *Bm,
     A = An; At = Atn;
     if (dmax <= 1e-16 * hmax) { ++it; break; }
   }
+  // A solution that is not finite has not converged, whatever the stop rule made of it: the maxima above are built with fmax, which
+  // drops NaN (an all-NaN step gives 0 <= 0), and an overflowed H gives inf <= 1e-16 inf.  Tested once here, after the loop, so the
+  // doubling itself and every finite result stay as they were.  (Rows 12..15 and the columns beyond 8 of the tile are zero.)
+  if (__any(!(isfinite(H[0]) && isfinite(H[1]) && isfinite(H[2])))) it = 60;
   // X = (H + H') / 2 through LDS (the caller wants it there)
   double *Xt = scr;
 #pragma unroll

@@ -509,7 +509,9 @@ int f16_linearise_full_batch(f16_ctx *ctx, const double *x, const double *u, dou
 int f16_c2d_full_batch(f16_ctx *ctx, const double *Ac, const double *Bc, double *Ad, double *Bd,
                        long B, long ld, double dt, void *stream);
 /* utils.py:219-245 dlqr with Q = Cd'Cd, R = I3 (env.py:353-356): K[27][ld] = -dlqr (3x9 row-major),
- * Pare[81][ld] = DARE solution (may be NULL). */
+ * Pare[81][ld] = DARE solution (may be NULL).  status[ld] (may be NULL; OR-ed into): F16_ST_QP_MAXITER when the DARE has not
+ * converged within its 60 doublings, and whenever its solution is not finite (a NaN or overflowing model), however few doublings
+ * that took; Pare and K are then the last iterate and the gain formed from it. */
 int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, const double *Cd, double *K, double *Pare,
                   int32_t *status, long B, long ld, void *stream);
 /* env.py:373-424 _calc_MPC_action for B aircraft: per aircraft (Ad,Bd,Cd) + current state x[18][ld]

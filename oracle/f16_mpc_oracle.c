@@ -47,6 +47,15 @@ static void matmul(const double *A, const double *B, double *C, int m, int k, in
       C[i * n + j] = s;
     }
 }
+/* C = A B with the dot products accumulated in long double: one rounding per entry (the DARE doubling below) */
+static void matmul_l(const double *A, const double *B, double *C, int m, int k, int n) {
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < n; ++j) {
+      long double s = 0.0L;
+      for (int p = 0; p < k; ++p) s += (long double)A[i * k + p] * B[p * n + j];
+      C[i * n + j] = (double)s;
+    }
+}
 /* in-place inverse by Gauss-Jordan with partial pivoting; returns 0 on success */
 static int invert(double *M, int n) {
   double *W = (double *)malloc(sizeof(double) * n * 2 * n);
@@ -133,26 +142,29 @@ int f16o_dare(const double *A0, const double *B, const double *Q, int n, int ni,
     }
   int it = 0, rc = 0;
   for (; it < 60; ++it) {
-    matmul(G, H, W, n, n, n);
+    matmul_l(G, H, W, n, n, n);
     for (int i = 0; i < n; ++i) W[i * n + i] += 1.0;
     if (invert(W, n)) { rc = -1; break; }
-    matmul(A, W, T1, n, n, n);                 /* A W */
-    matmul(T1, G, T2, n, n, n);                /* A W G */
+    matmul_l(A, W, T1, n, n, n);                 /* A W */
+    matmul_l(T1, G, T2, n, n, n);                /* A W G */
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j) At[i * n + j] = A[j * n + i];
-    matmul(T2, At, T3, n, n, n);               /* A W G A' */
+    matmul_l(T2, At, T3, n, n, n);               /* A W G A' */
     for (int e = 0; e < nn; ++e) G[e] += T3[e];
-    matmul(H, W, T2, n, n, n);                 /* H W */
-    matmul(T2, A, T3, n, n, n);                /* H W A */
-    matmul(At, T3, T4, n, n, n);               /* A' H W A */
+    matmul_l(H, W, T2, n, n, n);                 /* H W */
+    matmul_l(T2, A, T3, n, n, n);                /* H W A */
+    matmul_l(At, T3, T4, n, n, n);               /* A' H W A */
     double dm = 0.0, hm = 0.0;
     for (int e = 0; e < nn; ++e) { H[e] += T4[e]; dm = dmax(dm, fabs(T4[e])); hm = dmax(hm, fabs(H[e])); }
-    matmul(T1, A, T2, n, n, n);                /* A W A */
+    matmul_l(T1, A, T2, n, n, n);                /* A W A */
     memcpy(A, T2, sizeof(double) * nn);
     if (dm <= 1e-16 * hm) { ++it; break; }
   }
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) X[i * n + j] = 0.5 * (H[i * n + j] + H[j * n + i]);
+  /* a solution that is not finite has not converged, whatever the stop rule made of its NaN or inf (dare_sda_wave's rule) */
+  for (int e = 0; e < nn; ++e)
+    if (!isfinite(X[e])) it = 60;
   free(w);
   return rc ? rc : (it >= 60 ? 1 : 0);
 }

@@ -187,10 +187,14 @@ class COracle:
         self.lib.f16o_c2d(self._p(A), self._p(B), ns, ni, dt, self._p(Ad), self._p(Bd))
         return Ad, Bd
 
-    def dare(self, A, B, Q):
+    def dare(self, A, B, Q, return_status=False):
+        """R = I.  return_status: -> (X, rc) with rc 1 = not converged within 60 doublings or not finite, -1 = singular I + G H;
+        otherwise anything but 0 is an error."""
         A, B, Q = (np.ascontiguousarray(a, dtype=np.float64) for a in (A, B, Q))
         X = np.zeros_like(A)
         rc = self.lib.f16o_dare(self._p(A), self._p(B), self._p(Q), A.shape[0], B.shape[1], self._p(X))
+        if return_status:
+            return X, rc
         assert rc == 0, rc
         return X
 
@@ -294,10 +298,51 @@ def c2d(A, B, C, D, dt):
     return cont2discrete((A, B, C, D), dt)[0:4]
 
 
-def dlqr(A, B, Q, R):
-    """utils.py:219-245."""
+def _dlyap_smith(Ak, S):
+    """X = Ak' X Ak + S = sum_i Ak'^i S Ak^i by squaring: a sum of positive semidefinite terms, no cancellation"""
+    X, M = S.copy(), Ak.copy()
+    for _ in range(64):
+        dX = M.T @ X @ M
+        X = X + dX
+        M = M @ M
+        if not np.abs(dX).max() > 1e-21 * np.abs(X).max():
+            break
+    return (X + X.T) / 2
+
+
+def _solve_small(S, Y):
+    """S^-1 Y by Gauss-Jordan with partial pivoting in the arrays' own precision (numpy.linalg takes no long double)"""
+    S, Y = np.array(S), np.array(Y)
+    n = len(S)
+    for p in range(n):
+        q = p + int(np.argmax(np.abs(S[p:, p])))
+        if q != p:
+            S[[p, q]], Y[[p, q]] = S[[q, p]], Y[[q, p]]
+        d = S[p, p]
+        S[p], Y[p] = S[p] / d, Y[p] / d
+        for i in range(n):
+            if i != p:
+                f = S[i, p]
+                S[i], Y[i] = S[i] - f * S[p], Y[i] - f * Y[p]
+    return Y
+
+
+def dlqr(A, B, Q, R, polish=0):
+    """utils.py:219-245.  polish=0 (the default) is the reference's own arithmetic, scipy's Schur-based solve_discrete_are, and
+    reproduces the gains the reference stored to 1e-12 (tests/test_oracle_vs_golden.py).  On these models that is 1e-11 (R = I) to
+    6e-8 (R = 1e4 I) from the true solution (fixture G19, profiles/control_mp_errors.txt) -- three decades less accurate than the
+    kernel.  `polish` Newton-Kleinman steps (gain of the current X, then the Lyapunov equation of its closed loop by Smith
+    squaring), taken in long double, bring the gain to within an fp64 rounding of the true one (measured: <= 1e-15 of max|K| with
+    the 80-bit long double of x86): polish=2 where the gain is to JUDGE a solver rather than restate scipy."""
+    A, B, Q, R = (np.asarray(a, dtype=np.float64) for a in (A, B, Q, R))
     P = np.array(scipy.linalg.solve_discrete_are(A, B, Q, R))
-    return np.array(scipy.linalg.inv(B.T @ P @ B + R) @ (B.T @ P @ A))
+    if polish <= 0:
+        return np.array(scipy.linalg.inv(B.T @ P @ B + R) @ (B.T @ P @ A))
+    A, B, Q, R, P = (np.asarray(a, dtype=np.longdouble) for a in (A, B, Q, R, P))
+    for _ in range(polish):
+        K = _solve_small(B.T @ P @ B + R, B.T @ P @ A)
+        P = _dlyap_smith(A - B @ K, Q + K.T @ R @ K)
+    return np.asarray(_solve_small(B.T @ P @ B + R, B.T @ P @ A), dtype=np.float64)
 
 
 def calc_MC(A, B, dt, hzn):
