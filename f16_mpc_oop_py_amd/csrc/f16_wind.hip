@@ -18,21 +18,12 @@
 #include "f16_plant.hpp"
 #include "f16_rollout_common.hpp"
 #include "f16_wind.hpp"
+#include "f16_wind_lanes.hpp"
 
 namespace f16 {
 
 struct XdotWindArgs : DynArgs {
   const double *wind, *gust;   // [3][ld] each, or null (= 0)
-};
-
-// The rollouts: the scheduled argument block (u_seq, or under the LQR law dem_seq, behind SchedArgs) and the air.
-struct WindArgs : SchedArgs {
-  const double *wind;          // [3][ld] or null (= 0): constant over the launch
-  const double *gseq;          // [grows][3][ld] or null: step t reads row t / ghold
-  const double *ga, *gb;       // [3][ld] or null: the gust rows are generated in place (gust_row), row r from counter word row0 + r
-  double *gstate;              // [3][ld] with ga: the row before row0 in, the last row of the launch out
-  int ghold, grows;
-  uint32_t key0, key1, row0;
 };
 
 template <int BLOCK>
@@ -55,125 +46,7 @@ __global__ __launch_bounds__(BLOCK) void k_xdot_wind(XdotWindArgs a) {
   }
 }
 
-// The lane loop of both rollout kernels: rollout_lanes<..., SCHED = true> of f16_dynamics.hip (envelope freeze, sticky status bits,
-// trajectory samples, u_out, the command / demand schedule through RowAhead) with the air added.  EXACT: the step through the
-// out-of-line wind_step_exact on the table image in global memory (T = a.tab) instead of the inlined step on the LDS image.
-// ws[0..2]: the wind, ws[3..5]: the gust row in use, read from the slots where an evaluation uses them.  gw: with a gust_seq the NEXT
-// row, loaded when the current one is installed -- ghold >= 1 whole steps before its first use, as RowAhead does it.  With in-place
-// generation the row in use is the generator's state and the lane's a[3], b[3] are re-read (L2) at the row change: the generation
-// sits there, not in the step, and six more doubles held across the Runge-Kutta step would not stay in registers.
-template <int BLOCK, bool LQR, int STAGES, bool EXACT>
-__device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, double (*us)[BLOCK], double (*kq)[BLOCK], double (*ws)[BLOCK]) {
-  const bool gen = a.ga != nullptr;
-  SchedArgs g = a;                   // the gust rows seen as a schedule of three values per row
-  g.seq = a.gseq ? a.gseq : a.out; g.hold = a.ghold; g.nrows = a.grows;
-  for (long b = (long)blockIdx.x * BLOCK + threadIdx.x; b < a.B; b += (long)gridDim.x * BLOCK) {
-    double x[18];
-#pragma unroll
-    for (int k = 0; k < 18; ++k) x[k] = a.out[k * a.ld + b];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) us[k][threadIdx.x] = a.u[k * a.ld + b];
-    double ul[3] = {us[1][threadIdx.x], us[2][threadIdx.x], us[3][threadIdx.x]};   // (u_out of an aircraft that never steps: u0)
-    if (LQR) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) kq[3 * i + j][threadIdx.x] = a.K[(9 * i + 4 + j) * a.ld + b];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) kq[9 + j][threadIdx.x] = a.dem[j * a.ld + b];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ws[k][threadIdx.x] = a.wind ? a.wind[k * a.ld + b] : 0.0;
-    double gw[3] = {0, 0, 0};
-    uint32_t grow = a.row0;
-    RowAhead<3, false> rg;
-    rg.init(g, 3, a.out + b);
-    if (gen) {
-      const Gust3 r = gust_row(grow, (uint32_t)b, a.key0, a.key1, a.ga[b], a.ga[a.ld + b], a.ga[2 * a.ld + b], a.gb[b], a.gb[a.ld + b],
-                               a.gb[2 * a.ld + b], a.gstate[b], a.gstate[a.ld + b], a.gstate[2 * a.ld + b]);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ws[3 + k][threadIdx.x] = r.v[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) ws[3 + k][threadIdx.x] = a.gseq ? a.gseq[k * a.ld + b] : 0.0;
-      if (rg.rows > 0) rg.load(gw, a.out + b, rg.rel, a.ld);
-    }
-    int st = a.status ? a.status[b] : 0;
-    double *tr = a.traj ? a.traj + b : nullptr;
-    int until_store = a.traj_every;
-    constexpr int NR = LQR ? 3 : 4;
-    RowAhead<NR> ra;
-    ra.init(a, NR, a.out + b);
-    ra.settle();
-    for (int t = 0; t < a.nsteps; ++t) {
-      // env.py:117-124 on the state, i.e. on the GROUND triple: the reference exit()s; here the aircraft is frozen and flagged
-      if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(x)) st |= ST_ENVELOPE;
-      if (!(st & ST_ENVELOPE)) {
-        double u[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = us[k][threadIdx.x];
-        if (LQR) {   // the controller reads the state, not the air data
-          const double e0 = kq[9][threadIdx.x] - x[9], e1 = kq[10][threadIdx.x] - x[10], e2 = kq[11][threadIdx.x] - x[11];
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-            ul[i] = u[1 + i] = lqr_action(kq[3 * i][threadIdx.x], kq[3 * i + 1][threadIdx.x], kq[3 * i + 2][threadIdx.x], e0, e1, e2, u[1 + i]);
-        }
-        if constexpr (EXACT) {
-          double w[6];
-#pragma unroll
-          for (int k = 0; k < 6; ++k) w[k] = ws[k][threadIdx.x];
-          wind_step_exact<STAGES>(T, a.lofi, x, u, w, a.dt, a.xcg, a.fi, a.flags, &st);
-        } else {
-          wind_step<STAGES, -1>(T, a.lofi, x, u, [&](int k) { return ws[k][threadIdx.x]; }, a.dt, a.xcg, a.fi, a.flags, st);
-        }
-      }
-      if (tr && --until_store == 0) {
-        until_store = a.traj_every;
-#pragma unroll
-        for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
-        tr += 18 * a.ld;
-      }
-      if (ra.due(a, NR)) {
-        double r[NR];
-        ra.take(a, NR, r, a.out + b);
-#pragma unroll
-        for (int k = 0; k < NR; ++k) (LQR ? kq[9 + k] : us[k])[threadIdx.x] = r[k];
-        if (LQR) { ul[0] = us[1][threadIdx.x]; ul[1] = us[2][threadIdx.x]; ul[2] = us[3][threadIdx.x]; }   // (as a new launch: u0 until it steps)
-      }
-      if (rg.due(g, 3)) {            // a new gust row from the next step on, for frozen aircraft too (the generator does not stop)
-        if (LQR) { ul[0] = us[1][threadIdx.x]; ul[1] = us[2][threadIdx.x]; ul[2] = us[3][threadIdx.x]; }   // (a segment start, as above)
-        if (gen) {
-          const Gust3 r = gust_row(++grow, (uint32_t)b, a.key0, a.key1, a.ga[b], a.ga[a.ld + b], a.ga[2 * a.ld + b], a.gb[b], a.gb[a.ld + b],
-                                   a.gb[2 * a.ld + b], ws[3][threadIdx.x], ws[4][threadIdx.x], ws[5][threadIdx.x]);
-#pragma unroll
-          for (int k = 0; k < 3; ++k) ws[3 + k][threadIdx.x] = r.v[k];
-        } else {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) ws[3 + k][threadIdx.x] = gw[k];
-          if (rg.rows > 0) rg.load(gw, a.out + b, rg.rel, a.ld);
-        }
-      }
-    }
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < 18; ++k) finite = finite && isfinite(x[k]);
-    if (!finite) st |= ST_NONFINITE;
-    if (st & ST_ENVELOPE) st |= envelope_state_bits(x);
-#pragma unroll
-    for (int k = 0; k < 18; ++k) a.out[k * a.ld + b] = x[k];
-    if (a.status) a.status[b] = st;
-    if (LQR && a.u_out) {
-      a.u_out[b] = us[0][threadIdx.x];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) a.u_out[(1 + i) * a.ld + b] = ul[i];
-    }
-    if (gen) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.gstate[k * a.ld + b] = ws[3 + k][threadIdx.x];
-    }
-  }
-}
-
+// The rollout kernels: the lane loop is wind_lanes of f16_wind_lanes.hpp, shared with the ensemble twins of f16_wind_ens.hip.
 template <int BLOCK, bool LQR, int STAGES>
 __global__ __launch_bounds__(BLOCK) void k_rollout_wind(WindArgs a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
@@ -221,31 +94,16 @@ __global__ __launch_bounds__(64) void k_gust_sample(GustArgs a) {
 
 static bool still_air(const f16_wind *w) { return !w || (!w->wind_ned && !w->gust_seq && !w->ga && !w->gb && !w->gstate); }
 
-// The launch rules of the wind rollouts: F16_FLAG_ONE_LANE -> k_rollout_wind_exact; else the geometry of the one-lane-per-aircraft
-// kernels with the 256-lane ceiling of the Runge-Kutta rollouts -- never a role-wave kernel, never 512 lanes.
+// The launch rules of the wind rollouts (f16_wind_lanes.hpp: wind_check, wind_args, wind_geometry): F16_FLAG_ONE_LANE ->
+// k_rollout_wind_exact; else k_rollout_wind at 64 / 128 / 256 lanes.
 template <bool LQR>
 static int wind_rollout(f16_ctx *ctx, const char *missing, double *x, const double *u, const double *K, const double *seq, const f16_wind *w,
                         double *traj, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
                         double xcg, int fi_flag, int method, unsigned flags, void *stream) {
-  // the sibling's checks in the sibling's order (f16_dynamics.hip: plant_rollout), then the wind fields
-  if (!seq || (LQR && !K)) return set_error(F16_EINVAL, missing);
-  if (int rc = check_rollout(ctx, x, u, traj, B, ld, nsteps, traj_every)) return rc;
-  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
-  if (method != F16_INT_EULER && method != F16_INT_RK4) return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
-  if (w->gust_seq && w->ga) return set_error(F16_EINVAL, "gust_seq and ga are both given: the gust rows are either read or generated");
-  if ((w->ga != nullptr) != (w->gb != nullptr) || (w->ga != nullptr) != (w->gstate != nullptr))
-    return set_error(F16_EINVAL, "ga, gb and gstate go together");
-  if ((w->gust_seq || w->ga) && w->gust_hold < 1) return set_error(F16_EINVAL, "gust_hold must be >= 1");
+  if (int rc = wind_check(ctx, LQR, missing, x, u, K, seq, w, traj, B, ld, nsteps, hold, traj_every, method)) return rc;
   if (B == 0 || nsteps == 0) return F16_OK;
-  WindArgs a = base_args<WindArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
-  a.u = u; a.out = x; a.traj = traj;
-  a.nsteps = nsteps; a.traj_every = traj ? traj_every : nsteps + 1; a.dt = dt;
-  a.K = K; a.dem = LQR ? seq : nullptr; a.u_out = u_out;
-  a.seq = seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
-  const bool gusts = w->gust_seq || w->ga;
-  a.wind = w->wind_ned; a.gseq = w->gust_seq; a.ga = w->ga; a.gb = w->gb; a.gstate = w->gstate;
-  a.ghold = gusts ? w->gust_hold : nsteps; a.grows = (nsteps - 1) / a.ghold + 1;
-  a.key0 = (uint32_t)(w->seed & 0xffffffffu); a.key1 = (uint32_t)(w->seed >> 32); a.row0 = w->row0;
+  const WindArgs a = wind_args(ctx, LQR, x, u, K, seq, w, traj, u_out, status, B, ld, nsteps, hold, traj ? traj_every : nsteps + 1, dt, xcg,
+                               fi_flag, flags);
   const hipStream_t st = (hipStream_t)stream;
   const bool rk4 = method == F16_INT_RK4;
   if (flags & F16_FLAG_ONE_LANE) {
@@ -255,12 +113,7 @@ static int wind_rollout(f16_ctx *ctx, const char *missing, double *x, const doub
     else hipLaunchKernelGGL((k_rollout_wind_exact<LQR, 1>), grid, dim3(64), 0, st, a);
     return hip_check(hipGetLastError(), "f16_rollout_wind launch");
   }
-  Geometry g = geometry(B, fi_flag);
-  if (g.block == 512) {
-    g.block = 256;
-    const long blocks = (B + 255) / 256;
-    g.grid = (int)(blocks < 256 ? blocks : 256);
-  }
+  const Geometry g = wind_geometry(B, fi_flag);
   by_block(g, [&](auto block) {
     constexpr int BLOCK = decltype(block)::value;
     if constexpr (BLOCK <= 256) {

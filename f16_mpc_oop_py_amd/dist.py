@@ -5,6 +5,8 @@ contiguously -- rank g owns aircraft [g*B/W, (g+1)*B/W) -- tables and constants 
 no exchange inside the time loop.  The only data-path collective is the all-gather that collates the per-rank
 trajectory shards [T,18,B/W] (RCCL `ncclAllGather` over xGMI through torch.distributed's "nccl" backend; "gloo"
 on CPU tensors for the host-logic tests).  Scalars (max-over-ranks time, OR of status words) use all-reduce.
+Where the ensemble statistics of a rollout are wanted instead of its states (F16Batch.rollout_schedule(..., ensemble=group)),
+`merge_ensembles` gathers the five small moment tensors in place of the trajectories.
 """
 import os
 
@@ -112,6 +114,33 @@ def all_gather_trajectories(traj_local, total=None, layout="flat", chunk_bytes=1
         dist.all_gather_into_tensor(r.view(-1), src[t0:t0 + n].reshape(-1))
         out4[t0:t0 + n].copy_(r.permute(1, 2, 0, 3))
     return out if total is None else out[..., :total]
+
+
+def merge_ensembles(ens):
+    """The ensemble statistics of the whole batch from the per-rank ones (ensemble.Ensemble, the same [S, G] on every rank: group g
+    of every rank is a part of the global group g): ONE all-gather per tensor of the five small ones -- count [S, G], mean, m2, min,
+    max [S, G, 18] -- instead of the trajectories, then on every rank the groups of equal index folded in rank order with
+    ensemble.combine.  Returns an Ensemble of numpy arrays, the same on every rank.
+    The result is deterministic: the same ranks in the same order give the same bits.  It is NOT the single-device bits of the
+    whole batch: Chan's update is not associative, and folding per-rank partial folds is another order of the same operations (the
+    two agree to the rounding of the update; tests/test_dist_ensemble_gloo.py holds them to the bound of the rule's error analysis)."""
+    import numpy as np
+
+    from .ensemble import Ensemble, combine
+    parts = [t if isinstance(t, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(t)) for t in ens.parts()]
+    if not group_active():
+        return Ensemble(*(t.detach().cpu().numpy() for t in parts), group=ens.group)
+    W, gathered = world_size(), []
+    on = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    for t in parts:
+        src = t.detach().to(on).contiguous()
+        recv = torch.empty((W,) + tuple(src.shape), dtype=src.dtype, device=src.device)
+        dist.all_gather_into_tensor(recv.view(-1), src.view(-1))
+        gathered.append(recv.cpu().numpy())
+    acc = tuple(g[0] for g in gathered)
+    for r in range(1, W):
+        acc = combine(acc, tuple(g[r] for g in gathered))
+    return Ensemble(*acc, group=ens.group)
 
 
 def max_over_ranks(value, device=None):

@@ -257,14 +257,47 @@ class F16Batch:
             air.gust_seq, air.gust_hold = keep[-1].data_ptr(), k
         return air, keep, model
 
-    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER, air=None):
+    def _ensemble_buffers(self, group, samples):
+        """The `ensemble=` keyword -> (lib.Ens, the tensors it points at, the Ensemble the call fills): group = aircraft per group (a
+        multiple of 64; True: the whole batch as one group), `samples` samples.  The result tensors are [S, 18, G] on the device, as
+        the library writes them, seen as [S, G, 18]."""
+        from .ensemble import Ensemble, group_size
+        group = group_size(group, self.B)
+        G = (self.B + group - 1) // group
+        work = torch.empty(max(int(self.lib.f16_ens_work_doubles(self.B, samples)), 1), dtype=torch.float64, device=self.device)
+        count = torch.zeros((samples, G), dtype=torch.int32, device=self.device)
+        mean, m2, mn, mx = (torch.zeros((samples, 18, G), dtype=torch.float64, device=self.device) for _ in range(4))
+        e = _lib.Ens()
+        e.work, e.group, e.ldg, e.count = work.data_ptr(), group, G, count.data_ptr()
+        e.mean, e.m2, e.min, e.max = (t.data_ptr() for t in (mean, m2, mn, mx))
+        return e, (work, count, mean, m2, mn, mx), Ensemble(count, *(t.permute(0, 2, 1) for t in (mean, m2, mn, mx)), group=group)
+
+    def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER, air=None, ensemble=None,
+                      keep_traj=False):
         """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
         into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
         around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values.  method F16_INT_RK4:
-        the _rk entry points, which are scheduled ones -- a constant input is one row held for every step."""
-        traj = self._samples(nsteps, traj_every)
+        the _rk entry points, which are scheduled ones -- a constant input is one row held for every step.  ensemble (aircraft per
+        group, or True): the _wind_ens entry points, which return the statistics of the samples (an ensemble.Ensemble; with
+        keep_traj the samples too); with ensemble=None the call is the one it was."""
+        if ensemble is None and keep_traj:
+            raise ValueError("keep_traj goes with ensemble=")
+        every = int(traj_every or 1) if ensemble is not None else traj_every      # with ensemble= the sample period: every step by default
+        traj = self._samples(nsteps, every) if ensemble is None or keep_traj else None
         # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
         name, law, u_out = ("f16_rollout", (), ()) if K is None else ("f16_rollout_lqr", (_vp(K), _vp(dem)), (_vp(self._u),))
+        if ensemble is not None:  # the _wind_ens entry points: the _wind list with the f16_ens behind traj; no air = zero air through them
+            if every < 1 or int(nsteps) % every:
+                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every}), the sample period of the ensemble")
+            e, keep, result = self._ensemble_buffers(ensemble, int(nsteps) // every)
+            self._check(getattr(self.lib, name + "_wind_ens")(self.ctx.handle, _vp(self._x), _vp(u), *law, None if air is None else ctypes.byref(air[0]),
+                                                              _vp(traj), ctypes.byref(e), *u_out, _vp(self.status), self.B, self.B, int(nsteps),
+                                                              max(int(nsteps), 1) if hold is None else hold, every, self.dt, self.xcg,
+                                                              self.fi_flag, int(method), self.flags, self._stream))
+            result._keep = keep      # (the workspace lives as long as the result: the launches may still be running)
+            if air is not None and air[2] is not None:
+                air[2].advance(nsteps)
+            return (traj, result) if keep_traj else result
         if air is not None:      # (_air) the _wind entry points: the scheduled parameter list with the air behind the schedule
             self._check(getattr(self.lib, name + "_wind")(self.ctx.handle, _vp(self._x), _vp(u), *law, ctypes.byref(air[0]), _vp(traj), *u_out,
                                                           _vp(self.status), self.B, self.B, int(nsteps), max(int(nsteps), 1) if hold is None else hold,
@@ -282,7 +315,8 @@ class F16Batch:
                                             self.flags, self._stream))
         return traj
 
-    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler", wind=None, gusts=None, gust_every=None):
+    def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler", wind=None, gusts=None, gust_every=None,
+                         ensemble=None, keep_traj=False):
         """The reference's call pattern `u.values = action; step(u.values)` with an action that changes during the run
         (env.py:105-130; the doublets of Nguyen_m/runF16Sim.m) in ONE launch (C-ABI f16_rollout_sched): step t takes
         actions[t // hold], a zero-order hold.  actions: [S, B, 4] (numpy or torch), or a state-major [S, 4, B] fp64 tensor
@@ -290,7 +324,11 @@ class F16Batch:
         pass a host array or a non-contiguous view to say otherwise).  nsteps defaults to S * hold and needs
         S >= ceil(nsteps / hold) rows.  Returns what `rollout` returns; u.values ends up holding the last row used, as the
         reference's caller leaves it.  method="rk4": Runge-Kutta steps, each row held over the stages of its steps (f16_rollout_rk).
-        wind= / gusts= / gust_every= (see _air): the same rollout in steady wind and gusts (f16_rollout_wind), both methods."""
+        wind= / gusts= / gust_every= (see _air): the same rollout in steady wind and gusts (f16_rollout_wind), both methods.
+        ensemble=group (a multiple of 64, or True for the whole batch as one group): instead of the samples, their statistics over the
+        aircraft of each group -- count, mean, M2, min, max per sample and state, formed inside the launch (f16_rollout_wind_ens;
+        ensemble.py).  traj_every is then the sample period (default: every step); returns an ensemble.Ensemble, or (traj, Ensemble)
+        with keep_traj=True.  Without wind= / gusts= the flight is in zero air through the wind kernels."""
         method = _lib.integrator(method)
         t = actions if isinstance(actions, torch.Tensor) else torch.as_tensor(np.asarray(actions, dtype=np.float64))
         if t.dim() != 3:
@@ -303,7 +341,8 @@ class F16Batch:
             raise ValueError(f"actions must be [S, {self.B}, 4] or a contiguous fp64 [S, 4, {self.B}] tensor on {self.device}, "
                              f"not {tuple(t.shape)} ({t.dtype}, {t.device})")
         hold, nsteps = self._schedule_steps(hold, nsteps, seq.shape[0], "actions")
-        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold, method=method, air=self._air(wind, gusts, gust_every, nsteps))
+        traj = self._rollout_call(seq, nsteps, traj_every, hold=hold, method=method, air=self._air(wind, gusts, gust_every, nsteps),
+                                  ensemble=ensemble, keep_traj=keep_traj)
         self._u.copy_(seq[(nsteps - 1) // hold])
         return traj
 
@@ -734,7 +773,7 @@ class F16Batch:
 
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
                     R=None, hold=None, method="euler", schedule=None, gains_every=1, return_info=False, wind=None, gusts=None,
-                    gust_every=None):
+                    gust_every=None, ensemble=None, keep_traj=False):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -761,7 +800,12 @@ class F16Batch:
         info["gs_out"] [B]: at how many gain updates the aircraft was outside the table's grid (the edge cell is extended flat there).
         wind= / gusts= / gust_every= (see _air): the frozen-gain nonlinear loop in steady wind and gusts (f16_rollout_lqr_wind), both
         methods -- the disturbance-rejection loop; the controller reads the state, not the air data.  Not combined with linear=True,
-        relinearise=True or schedule= (ValueError)."""
+        relinearise=True or schedule= (ValueError).
+        ensemble=group / keep_traj= (see rollout_schedule): the statistics of the samples over the aircraft of each group instead of the
+        samples (f16_rollout_lqr_wind_ens), on the same frozen-gain nonlinear loop, with or without wind= / gusts=; not combined
+        with linear=True, relinearise=True or schedule= (ValueError)."""
+        if (ensemble is not None or keep_traj) and (linear or relinearise or schedule is not None):
+            raise ValueError("ensemble= runs on the nonlinear loop with a fixed gain (not with linear=True, relinearise=True or schedule=)")
         if (wind is not None or gusts is not None) and (linear or relinearise or schedule is not None):
             raise ValueError("wind= / gusts= run on the nonlinear loop with a fixed gain (not with linear=True, relinearise=True or schedule=)")
         if schedule is not None:
@@ -821,7 +865,7 @@ class F16Batch:
         else:
             u0s = self._soa(u0, 4)
         return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq, method=method,
-                                  air=self._air(wind, gusts, gust_every, nsteps))
+                                  air=self._air(wind, gusts, gust_every, nsteps), ensemble=ensemble, keep_traj=keep_traj)
 
     def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
                           hold=None):

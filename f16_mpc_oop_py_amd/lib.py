@@ -11,7 +11,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("F16HIP_SO", os.path.join(HERE, "libf16hip.so"))   # override only for A/B experiments
-SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_mppi.hip", "f16_wind.hip", "f16_debug.hip", "f16_tables.cpp"]
+SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_mppi.hip", "f16_wind.hip", "f16_wind_ens.hip", "f16_debug.hip", "f16_tables.cpp"]
 # the expression-exact (F16_STRICT) build of the plant alone: checker-side evidence that the device lookups and the plant
 # reproduce the reference bit for bit where no libm call is involved (tests/test_gpu_dynamics.py); never used by the product
 STRICT_SO_PATH = os.path.join(HERE, "libf16hip_strict.so")
@@ -84,6 +84,12 @@ class Wind(ctypes.Structure):
     """include/f16_hip.h `f16_wind`: the air of f16_rollout_wind / f16_rollout_lqr_wind (device pointers; all NULL = still air)."""
     _fields_ = [("wind_ned", ctypes.c_void_p), ("gust_seq", ctypes.c_void_p), ("gust_hold", ctypes.c_int), ("ga", ctypes.c_void_p),
                 ("gb", ctypes.c_void_p), ("gstate", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("row0", ctypes.c_uint32)]
+
+
+class Ens(ctypes.Structure):
+    """include/f16_hip.h `f16_ens`: workspace, grouping and result arrays of the ensemble statistics (device pointers)."""
+    _fields_ = [("work", ctypes.c_void_p), ("group", ctypes.c_long), ("ldg", ctypes.c_long), ("count", ctypes.c_void_p),
+                ("mean", ctypes.c_void_p), ("m2", ctypes.c_void_p), ("min", ctypes.c_void_p), ("max", ctypes.c_void_p)]
 
 
 F16_GS_ENTRIES = 12            # doubles per node of a gain table: K[i][4 + j] at 3 i + j, the trim surface commands at 9 + i
@@ -296,6 +302,13 @@ def load():
         L.f16_rollout_lqr_wind.argtypes = [vp, vp, vp, vp, vp, wd, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
         L.f16_gust_coeffs_host.argtypes = [d3, d3, d, d, d3, d3]
         L.f16_gust_sample.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, vp, i, l, l, vp]
+    if hasattr(L, "f16_rollout_wind_ens"):   # (absent from an older library loaded through F16HIP_SO for an A/B run)
+        wd, ep = ctypes.POINTER(Wind), ctypes.POINTER(Ens)
+        L.f16_ens_work_doubles.argtypes = [l, i]
+        L.f16_ens_work_doubles.restype = l
+        L.f16_rollout_wind_ens.argtypes = [vp, vp, vp, wd, vp, ep, vp, l, l, i, i, i, d, d, i, i, u, vp]
+        L.f16_rollout_lqr_wind_ens.argtypes = [vp, vp, vp, vp, vp, wd, vp, ep, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
+        L.f16_ens_from_traj.argtypes = [vp, vp, i, l, l, u, ep, vp]
     L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
     L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
     L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]

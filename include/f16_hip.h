@@ -465,6 +465,61 @@ int f16_rollout_lqr_wind(f16_ctx *ctx, double *x, const double *u0, const double
 int f16_gust_coeffs_host(const double *sigma, const double *length, double v0, double dt_row, double *a_out, double *b_out);
 int f16_gust_sample(f16_ctx *ctx, const double *ga, const double *gb, double *gstate, uint64_t seed, uint32_t row0, double *g_seq,
                     int nrows, long B, long ld, void *stream);
+/* ENSEMBLE STATISTICS of wind and gust rollouts inside the launch: per sample and per group of aircraft the count, mean, M2 (the sum
+ * of squared deviations from the mean), minimum and maximum of each of the 18 states, formed in registers at the sample point, so
+ * that a gust study stores [S][18][G] moments instead of [S][18][B] states.  The rule below is stated HERE ONCE; the device code
+ * (csrc/f16_ensemble.hpp) and the numpy reference (f16_mpc_oop_py_amd/ensemble.py `ensemble_reference`) follow it operation for
+ * operation, and the results are equal, not close.
+ *   Groups.  Aircraft b belongs to group b / group; group is a multiple of 64, >= 64.  Any B >= 1: G = ceil(B / group), the last
+ *     group may be short.  One wavefront covers the 64 consecutive aircraft from a multiple of 64 on.
+ *   Who contributes.  At sample s an aircraft contributes (m = 1) iff all 18 values of its sample are finite AND, unless
+ *     F16_FLAG_NO_ENVELOPE is set, the sample lies inside the box of env.py:117-124 (what freezes an aircraft) -- a pure function of
+ *     the stored sample.  A frozen or NaN aircraft drops out and count shows the attrition.  Lanes beyond B have m = 0; the padding
+ *     columns of the arrays are never read.
+ *   Per wavefront, lanes l = 0..63, per state row k:   n_w = sum m_l;   s_w = tree(m_l ? x_l : 0.0);   mean_w = s_w / n_w;
+ *     d_l = m_l ? x_l - mean_w : 0.0;   M2_w = tree(d_l * d_l), the product rounded before any add (no FMA contraction);
+ *     min_w, max_w over the contributing lanes;  n_w = 0 gives the record (0, 0.0, 0.0, +inf, -inf).
+ *     tree = the balanced tree over consecutive lanes, v = v[0::2] + v[1::2] six times (an xor-butterfly over 1, 2, 4, 8, 16, 32
+ *     leaves the same bits on every lane).
+ *   Per group.  The group's wave records folded in ascending aircraft order from (n, mean, M2) = (0, 0, 0): a wave with n_w = 0 is
+ *     skipped, the first non-empty wave is taken as it is, after that, every operation rounded on its own,
+ *         N = n + n_w;   delta = mean_w - mean;   mean = mean + delta * (n_w / N);
+ *         M2 = (M2 + M2_w) + (delta * delta) * ((n * n_w) / N);   n = N
+ *     min and max fold by fmin and fmax.  An empty group gives count 0, mean 0, M2 0, min +inf, max -inf.  The sign of a zero minimum
+ *     or maximum is not specified (fmin / fmax of +0 and -0).
+ *   f16_ens: HOST struct, DEVICE pointers.  work: f16_ens_work_doubles(B, S) doubles, S = the number of samples (the wave records:
+ *     73 per wavefront and sample; contents unspecified after the call); group; ldg >= G; count [S][ldg]; mean, m2, min, max
+ *     [S][18][ldg].  Entries g >= G are not written.  f16_ens_work_doubles is host code and needs no context.
+ *   f16_rollout_wind_ens / f16_rollout_lqr_wind_ens: f16_rollout_wind / f16_rollout_lqr_wind with the statistics of the samples the
+ *     call would store, S = nsteps / traj_every; traj_every >= 1 and nsteps % traj_every == 0 are required whether or not traj is
+ *     given, and traj may be NULL (nothing but the statistics leaves the kernel).  Two launches on the stream: the rollout, whose
+ *     wavefronts write their records at every sample point, and a finishing kernel, one lane per (sample, row, group).  Nothing is
+ *     allocated: the calls can be captured into a graph.  A NULL h_wind, or one whose pointers are all NULL, is zero air THROUGH THE
+ *     WIND KERNELS, not a forward to the still-air kernels: the bits are those of f16_rollout_wind with a zero wind_ned.
+ *     Under F16_FLAG_ONE_LANE the final state, status, u_out, gstate and traj are those of the sibling call bit for bit (the step is
+ *     out of line); under default flags they agree to rounding (an inlined step's contraction follows its surroundings).
+ *     F16_EINVAL: what the sibling refuses, in its order; then nsteps % traj_every != 0 or traj_every < 1; a NULL h_ens or a NULL
+ *     member; group < 64 or group % 64 != 0; ldg < G.  B == 0 or nsteps == 0 is a no-op.
+ *   f16_ens_from_traj: the same statistic of a stored trajectory traj[nsamples][18][ld] through the same two device functions -- the
+ *     samples of ANY rollout kernel reduce to the numbers the fused call gives for the same samples.  F16_EINVAL: a NULL ctx or
+ *     traj, B < 0, ld < B, nsamples < 0; then the f16_ens rules above.  B == 0 or nsamples == 0 is a no-op.
+ *   OUT OF SCOPE: twins of the still-air, role-wave, scored, gain-scheduled and MPC kernels (f16_ens_from_traj serves them); the
+ *     plant's output rows; exceedance counts and histograms; groups that are not wave-aligned. */
+long f16_ens_work_doubles(long B, int nsamples);
+typedef struct f16_ens {
+  double *work;
+  long group, ldg;
+  int32_t *count;
+  double *mean, *m2, *min, *max;
+} f16_ens;
+int f16_rollout_wind_ens(f16_ctx *ctx, double *x, const double *u_seq, const f16_wind *h_wind, double *traj, const f16_ens *h_ens,
+                         int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag,
+                         int method, unsigned flags, void *stream);
+int f16_rollout_lqr_wind_ens(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, const f16_wind *h_wind,
+                             double *traj, const f16_ens *h_ens, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
+                             int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
+int f16_ens_from_traj(f16_ctx *ctx, const double *traj, int nsamples, long B, long ld, unsigned flags, const f16_ens *h_ens,
+                      void *stream);
 /* The reference's LINEAR-model closed loops as ONE launch (9-state reduced model, 3 inputs; one lane per aircraft, its matrices in
  * registers):   per step   u = -K (x_ref - x) + u0,   x = Ad x + Bd u
  *   test_env_mk2.py:46-62 `LQR(linear=True)` (what main.py:35 runs): the frozen model ssr.Ad / ssr.Bd under env.py:360-371

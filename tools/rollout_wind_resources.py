@@ -1,4 +1,5 @@
-"""Registers, scratch and LDS of the wind kernels (csrc/f16_wind.hip: k_rollout_wind, k_rollout_wind_exact, k_xdot_wind, k_gust_sample) as
+"""Registers, scratch and LDS of the wind kernels (csrc/f16_wind.hip: k_rollout_wind, k_rollout_wind_exact, k_xdot_wind, k_gust_sample;
+csrc/f16_wind_ens.hip: their ensemble twins k_rollout_wind_ens, k_rollout_wind_exact_ens and k_ens_from_traj, k_ens_finish) as
 the compiler reports them (`hipcc -Rpass-analysis=kernel-resource-usage`, flags of the default build, no GPU needed), beside the
 still-air kernel each rollout kernel is the twin of (k_rollout<BLOCK, -1, LQR, true, false, STAGES> / k_rollout_exact<LQR, true, false,
 STAGES> of csrc/f16_dynamics.hip).  In the same run every rollout kernel of f16_dynamics.hip is held against the parent commit's
@@ -65,7 +66,8 @@ def main():
     rollouts = sorted(n for n in dyn_before if "k_rollout" in n)
     moved = [n for n in rollouts if dyn_before[n] != dyn.get(n)]
     asm_wind = assembly(REPO, os.path.join(CSRC, "f16_wind.hip"))
-    for found, asm in ((wind, asm_wind), (dyn, asm_after)):          # instructions of each kernel's own body, as emitted
+    ens, asm_ens = remarks(REPO, "f16_wind_ens.hip"), assembly(REPO, os.path.join(CSRC, "f16_wind_ens.hip"))
+    for found, asm in ((wind, asm_wind), (dyn, asm_after), (ens, asm_ens)):          # instructions of each kernel's own body, as emitted
         for k in found.values():
             k["instr"] = len(asm.get(k["mangled"], ()))
     changed = [f for f in asm_before if asm_before[f] != asm_after.get(f)]
@@ -108,6 +110,33 @@ def main():
             assert k["LDS Size [bytes/block]"] <= 163840, (name, targs)
             if name != "k_rollout_wind_exact" and k["ScratchSize [bytes/lane]"]:
                 bad.append((name, targs))
+        # the ensemble twins (csrc/f16_wind_ens.hip), each under the kernel of csrc/f16_wind.hip it is the twin of: recorded, not judged
+        erows = []
+        for n, k in ens.items():
+            m = re.match(r"void f16::k_rollout_wind_ens<(\d+), (true|false), (\d+)>\(", n)
+            if m:
+                erows.append(("k_rollout_wind_ens", (int(m.group(1)), m.group(2) == "true", int(m.group(3))), k,
+                              f"void f16::k_rollout_wind<{m.group(1)}, {m.group(2)}, {m.group(3)}>("))
+                continue
+            m = re.match(r"void f16::k_rollout_wind_exact_ens<(true|false), (\d+)>\(", n)
+            if m:
+                erows.append(("k_rollout_wind_exact_ens", (m.group(1) == "true", int(m.group(2))), k,
+                              f"void f16::k_rollout_wind_exact<{m.group(1)}, {m.group(2)}>("))
+                continue
+            m = re.match(r"f16::(k_ens_from_traj|k_ens_finish)\(", n)
+            if m:
+                erows.append((m.group(1), (), k, None))
+        erows.sort(key=lambda r: (r[0], r[1]))
+        assert len([r for r in erows if r[0] == "k_rollout_wind_ens"]) == 12 and len([r for r in erows if r[0] == "k_rollout_wind_exact_ens"]) == 4 \
+            and len(erows) == 18, [r[:2] for r in erows]
+        f.write("\n# the ensemble twins of csrc/f16_wind_ens.hip (the ENS lane loop: the wave's records of every sample formed in registers),\n"
+                "# each above the kernel of csrc/f16_wind.hip it is the twin of (k_rollout_wind_exact_e. = k_rollout_wind_exact_ens); k_ens_from_traj\n"
+                "# and k_ens_finish have none.  Recorded, not judged: k_rollout_wind_ens<*, false, 4> spills 4 vector registers (32 B / lane)\n")
+        for name, targs, k, twin in erows:
+            f.write(line({"k_rollout_wind_exact_ens": "k_rollout_wind_exact_e."}.get(name, name), ", ".join(str(v).lower() for v in targs), k))
+            if twin:
+                f.write(line("  " + twin.split("::")[1].split("<")[0], "(twin)", next(v for n, v in wind.items() if n.startswith(twin))))
+            assert k["LDS Size [bytes/block]"] <= 163840, (name, targs)
         f.write(f"\n# the {len(rollouts)} rollout kernels of csrc/f16_dynamics.hip against the parent commit's sources: SGPR / VGPR / AGPR / scratch / spill /\n"
                 f"# LDS figures that differ: {len(moved)}" + ("" if not moved else " " + " ".join(moved)) + "\n"
                 f"# device assembly of csrc/f16_dynamics.hip against the parent commit, function by function (labels renumbered, comments and\n"
