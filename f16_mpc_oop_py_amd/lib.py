@@ -8,6 +8,8 @@ import ctypes
 import os
 import subprocess
 
+from . import cabi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("F16HIP_SO", os.path.join(HERE, "libf16hip.so"))   # override only for A/B experiments
@@ -26,17 +28,19 @@ else:
     _NUMERICS = ["-ffp-contract=fast", "-DF16_FAST_TAN", "-DF16_FAST_POW", "-DF16_FAST_TRIG", "-DF16_FAST_DIV"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result"] + _NUMERICS
 
-F16_ST = dict(ALPHA1=1, ALPHA2=2, BETA=4, EL=8, ENVELOPE=16, NONFINITE=32, QP_MAXITER=64, QP_INFEASIBLE=128)
+_C = cabi.constants()                          # every value below is the header's `#define`
+F16_ST = {k: _C["F16_ST_" + k] for k in ("ALPHA1", "ALPHA2", "BETA", "EL", "ENVELOPE", "NONFINITE", "QP_MAXITER", "QP_INFEASIBLE")}
 F16_ST_ENV_STATE = lambda k: 1 << (8 + k)      # with ENVELOPE: state k was outside its box (env.py:117-124)
-F16_ST_LOOP_STALL = 1 << 26                    # f16_rollout_mpc gave up waiting for the aircraft's previous step (a guard; never observed)
-F16_ST_QP_SOFT_ACTIVE = 1 << 27                # f16_mpc_plan_soft_rows: the returned solve has a soft state row outside its [l, u]
-F16_FLAG_FIX_CLR = 1
-F16_FLAG_NO_ENVELOPE = 2
-F16_FLAG_ONE_LANE = 4          # rollouts: the one-lane-per-aircraft kernel whatever the batch size (results independent of B)
-F16_FLAG_HOLD_COMMAND = 8      # closed MPC loops: a step without a command (infeasible QP, state not finite) keeps the previous one
-F16_FLAG_NO_CELL_CACHE = 16    # diagnostic: quad rollout re-brackets every step (no cell re-use); results bit-identical either way
-F16_INT_EULER, F16_INT_RK4 = 1, 4      # the step rule of f16_rollout_rk / f16_rollout_lqr_rk / f16_rollout_cost_rk
+F16_ST_LOOP_STALL = _C["F16_ST_LOOP_STALL"]    # f16_rollout_mpc gave up waiting for the aircraft's previous step (a guard; never observed)
+F16_ST_QP_SOFT_ACTIVE = _C["F16_ST_QP_SOFT_ACTIVE"]    # f16_mpc_plan_soft_rows: the returned solve has a soft state row outside its [l, u]
+F16_FLAG_FIX_CLR = _C["F16_FLAG_FIX_CLR"]
+F16_FLAG_NO_ENVELOPE = _C["F16_FLAG_NO_ENVELOPE"]
+F16_FLAG_ONE_LANE = _C["F16_FLAG_ONE_LANE"]            # rollouts: the one-lane-per-aircraft kernel whatever the batch size (results independent of B)
+F16_FLAG_HOLD_COMMAND = _C["F16_FLAG_HOLD_COMMAND"]    # closed MPC loops: a step without a command (infeasible QP, state not finite) keeps the previous one
+F16_FLAG_NO_CELL_CACHE = _C["F16_FLAG_NO_CELL_CACHE"]  # diagnostic: quad rollout re-brackets every step (no cell re-use); results bit-identical either way
+F16_INT_EULER, F16_INT_RK4 = _C["F16_INT_EULER"], _C["F16_INT_RK4"]    # the step rule of f16_rollout_rk / f16_rollout_lqr_rk / f16_rollout_cost_rk
 INTEGRATORS = {"euler": F16_INT_EULER, "rk4": F16_INT_RK4}
+F16_GS_ENTRIES = _C["F16_GS_ENTRIES"]          # doubles per node of a gain table: K[i][4 + j] at 3 i + j, the trim surface commands at 9 + i
 
 
 def integrator(method, rk4=True):
@@ -53,46 +57,37 @@ class F16HipError(RuntimeError):
     pass
 
 
+# The six structs of include/f16_hip.h: cabi.structure gives each class the header's fields and binds it to the C name, so that a
+# parameter declared `const f16_wind *` is a POINTER(Wind).
+@cabi.structure("f16_qp_settings")
 class QPSettings(ctypes.Structure):
-    _fields_ = [("rho", ctypes.c_double), ("sigma", ctypes.c_double), ("alpha", ctypes.c_double),
-                ("eps_abs", ctypes.c_double), ("eps_rel", ctypes.c_double), ("eps_prim_inf", ctypes.c_double),
-                ("max_iter", ctypes.c_int),
-                ("check_every", ctypes.c_int), ("rho_every", ctypes.c_int), ("adaptive_rho", ctypes.c_int),
-                ("scaling", ctypes.c_int)]
+    """include/f16_hip.h `f16_qp_settings`: the ADMM settings of the MPC solves (f16_qp_default_settings fills in OSQP's defaults)."""
 
 
+@cabi.structure("f16_mpc_weights")
 class MPCWeights(ctypes.Structure):
     """include/f16_hip.h `f16_mpc_weights`: the arguments of utils.py:21 setup_OSQP / utils.py:219 dlqr that env.py fills with
     constants."""
-    _fields_ = [("q_from_cd", ctypes.c_int), ("Q", ctypes.c_double * 81), ("R", ctypes.c_double * 9),
-                ("x_lb", ctypes.c_double * 9), ("x_ub", ctypes.c_double * 9), ("u_lb", ctypes.c_double * 3), ("u_ub", ctypes.c_double * 3),
-                ("udot_lb", ctypes.c_double * 3), ("udot_ub", ctypes.c_double * 3)]
 
 
+@cabi.structure("f16_cost_weights")
 class CostWeights(ctypes.Structure):
     """include/f16_hip.h `f16_cost_weights`: the diagonal weights of f16_rollout_cost (22 doubles, all finite and >= 0)."""
-    _fields_ = [("q", ctypes.c_double * 9), ("qf", ctypes.c_double * 9), ("r", ctypes.c_double * 3), ("pen", ctypes.c_double)]
 
 
+@cabi.structure("f16_gain_grid")
 class GainGrid(ctypes.Structure):
     """include/f16_hip.h `f16_gain_grid`: the uniform (altitude, airspeed) grid of a gain schedule (nh, nv >= 2; dh, dv > 0)."""
-    _fields_ = [("h0", ctypes.c_double), ("dh", ctypes.c_double), ("v0", ctypes.c_double), ("dv", ctypes.c_double),
-                ("nh", ctypes.c_int), ("nv", ctypes.c_int)]
 
 
+@cabi.structure("f16_wind")
 class Wind(ctypes.Structure):
     """include/f16_hip.h `f16_wind`: the air of f16_rollout_wind / f16_rollout_lqr_wind (device pointers; all NULL = still air)."""
-    _fields_ = [("wind_ned", ctypes.c_void_p), ("gust_seq", ctypes.c_void_p), ("gust_hold", ctypes.c_int), ("ga", ctypes.c_void_p),
-                ("gb", ctypes.c_void_p), ("gstate", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("row0", ctypes.c_uint32)]
 
 
+@cabi.structure("f16_ens")
 class Ens(ctypes.Structure):
     """include/f16_hip.h `f16_ens`: workspace, grouping and result arrays of the ensemble statistics (device pointers)."""
-    _fields_ = [("work", ctypes.c_void_p), ("group", ctypes.c_long), ("ldg", ctypes.c_long), ("count", ctypes.c_void_p),
-                ("mean", ctypes.c_void_p), ("m2", ctypes.c_void_p), ("min", ctypes.c_void_p), ("max", ctypes.c_void_p)]
-
-
-F16_GS_ENTRIES = 12            # doubles per node of a gain table: K[i][4 + j] at 3 i + j, the trim surface commands at 9 + i
 
 
 def make_cost_weights(q=None, qf=None, r=None, penalty=0.0):
@@ -255,105 +250,7 @@ def load():
     if not os.path.exists(SO_PATH):
         raise F16HipError(f"{SO_PATH} is missing: run `{build_cmd}`")
     L = ctypes.CDLL(SO_PATH)
-    vp, d, i, l, u = ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_long, ctypes.c_uint
-    L.f16_create.argtypes = [ctypes.POINTER(vp), i]
-    L.f16_destroy.argtypes = [vp]
-    L.f16_last_error.restype = ctypes.c_char_p
-    L.f16_table_image_doubles.restype = ctypes.c_size_t
-    L.f16_debug_read_tables.argtypes = [vp, vp]
-    L.f16_table_image_i32_ints.restype = ctypes.c_size_t
-    L.f16_debug_read_tables_i32.argtypes = [vp, vp]
-    L.Nlplant.argtypes = [vp, vp, i]
-    L.Nlplant.restype = None
-    L.atmos.argtypes = [d, d, vp]
-    L.atmos.restype = None
-    L.f16_dropin_config.argtypes = [d, u]
-    L.f16_dropin_config.restype = None
-    L.f16_xdot_batch.argtypes = [vp, vp, vp, vp, vp, l, l, d, i, u, vp]
-    L.f16_nlplant_batch.argtypes = [vp, vp, vp, vp, l, l, d, i, u, vp]
-    L.f16_rollout.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, d, d, i, u, vp]
-    L.f16_rollout_lqr.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, d, d, i, u, vp]
-    if hasattr(L, "f16_rollout_sched"):      # (absent from an older library loaded through F16HIP_SO for an A/B run: calling it then raises)
-        L.f16_rollout_sched.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
-        L.f16_rollout_lqr_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
-    if hasattr(L, "f16_rollout_cost"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        L.f16_rollout_cost.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, u, vp]
-    if hasattr(L, "f16_rollout_rk"):         # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        L.f16_rollout_rk.argtypes = [vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_rollout_lqr_rk.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_rollout_cost_rk.argtypes = [vp, vp, l, l, vp, vp, vp, ctypes.POINTER(CostWeights), vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-    if hasattr(L, "f16_rollout_lqr_gs"):     # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        gp = ctypes.POINTER(GainGrid)
-        L.f16_gain_lookup_host.argtypes = [gp, vp, d, d, vp]
-        L.f16_debug_gain_lookup.argtypes = [vp, gp, vp, vp, vp, l, vp]
-        L.f16_rollout_lqr_gs.argtypes = [vp, vp, vp, gp, vp, i, vp, vp, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-    if hasattr(L, "f16_mppi_blend"):         # (not part of the strict build, which holds the plant sources alone)
-        L.f16_mppi_blend.argtypes = [vp, vp, vp, d, vp, vp, vp, l, l, l, l, i, vp]
-    if hasattr(L, "f16_mppi_sample"):        # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        u64, u32, d3 = ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(d)
-        L.f16_mppi_sample.argtypes = [vp, vp, d3, u64, u32, vp, l, l, l, l, i, vp]
-        L.f16_debug_philox.argtypes = [vp, vp, vp, l, vp]
-        L.f16_rollout_mppi.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(CostWeights), d3, d, u64, u32, vp, vp, vp, vp, vp,
-                                       l, l, l, l, i, i, i, i, d, d, i, i, u, vp]
-    if hasattr(L, "f16_rollout_wind"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        wd, d3 = ctypes.POINTER(Wind), ctypes.POINTER(d)
-        L.f16_xdot_wind_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
-        L.f16_rollout_wind.argtypes = [vp, vp, vp, wd, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_rollout_lqr_wind.argtypes = [vp, vp, vp, vp, vp, wd, vp, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_gust_coeffs_host.argtypes = [d3, d3, d, d, d3, d3]
-        L.f16_gust_sample.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, vp, i, l, l, vp]
-    if hasattr(L, "f16_rollout_wind_ens"):   # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        wd, ep = ctypes.POINTER(Wind), ctypes.POINTER(Ens)
-        L.f16_ens_work_doubles.argtypes = [l, i]
-        L.f16_ens_work_doubles.restype = l
-        L.f16_rollout_wind_ens.argtypes = [vp, vp, vp, wd, vp, ep, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_rollout_lqr_wind_ens.argtypes = [vp, vp, vp, vp, vp, wd, vp, ep, vp, vp, l, l, i, i, i, d, d, i, i, u, vp]
-        L.f16_ens_from_traj.argtypes = [vp, vp, i, l, l, u, ep, vp]
-    L.f16_rollout_lqr_linear.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, u, vp]
-    L.f16_xdot_na_batch.argtypes = [vp, vp, vp, vp, vp, vp, l, l, d, i, u, vp]
-    L.f16_debug_table_lookup.argtypes = [vp, i, vp, vp, vp, i, vp, vp]
-    if hasattr(L, "f16_debug_sincos"):       # (absent from an older library loaded through F16HIP_SO for an A/B run)
-        L.f16_debug_sincos.argtypes = [vp, vp, l, vp]
-        L.f16_debug_pow.argtypes = [vp, vp, l, vp]
-    if hasattr(L, "f16_trim_batch"):
-        L.f16_trim_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, l, l, d, i, u, i, vp, vp]
-    if hasattr(L, "f16_linearise_batch"):
-        L.f16_linearise_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, l, l, d, d, i, u, vp]
-        L.f16_c2d_batch.argtypes = [vp, vp, vp, vp, vp, l, l, d, vp]
-        L.f16_linearise_full_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, l, l, d, d, i, u, vp]
-        L.f16_c2d_full_batch.argtypes = [vp, vp, vp, vp, vp, l, l, d, vp]
-        L.f16_lqr_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, l, l, vp]
-        L.f16_qp_default_settings.argtypes = [ctypes.POINTER(QPSettings)]
-        L.f16_qp_default_settings.restype = None
-        L.f16_mpc_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
-        L.f16_mpc_hzn_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, l, l, i, i, d, ctypes.POINTER(QPSettings), vp]
-        L.f16_mpc_qp_debug.argtypes = [vp, vp, vp, vp, vp, vp, l, l, i, d, vp, vp, vp, vp, vp]
-        L.f16_debug_spd_inverse.argtypes = [vp, vp, vp, i, l, vp]
-        L.f16_mpc_plan_create.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
-        L.f16_mpc_plan_solve.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-        wp = ctypes.POINTER(MPCWeights)
-        L.f16_mpc_default_weights.argtypes = [wp]
-        L.f16_mpc_default_weights.restype = None
-        L.f16_lqr_batch_w.argtypes = [vp, vp, vp, vp, wp, vp, vp, vp, l, l, vp]
-        L.f16_rollout_lqr_relin.argtypes = [vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, i, u, d, d, d, i, u, vp]
-        L.f16_mpc_batch_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
-        L.f16_mpc_plan_create_w.argtypes = [vp, ctypes.POINTER(vp), vp, vp, vp, wp, l, l, i, d, ctypes.POINTER(QPSettings), vp]
-        L.f16_mpc_plan_solve_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.f16_mpc_qp_debug_w.argtypes = [vp, vp, vp, vp, vp, vp, vp, wp, l, l, i, d, vp, vp, vp, vp, vp]
-        L.f16_rollout_mpc.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, d, i, u, vp]
-        L.f16_rollout_mpc_relin.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, d, d, i, u, vp]
-        if hasattr(L, "f16_rollout_mpc_hold"):      # (absent from an older library loaded through F16HIP_SO for an A/B run)
-            L.f16_rollout_mpc_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, d, d, i, u, vp]
-            L.f16_rollout_mpc_relin_hold.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, d, d, d, i, u, vp]
-        if hasattr(L, "f16_rollout_mpc_sched"):     # (absent from an older library loaded through F16HIP_SO for an A/B run)
-            L.f16_rollout_mpc_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, d, d, i, u, vp]
-            L.f16_rollout_mpc_relin_sched.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, d, d, d, i, u, vp]
-            L.f16_rollout_lqr_relin_sched.argtypes = [vp, vp, vp, vp, vp, wp, vp, vp, vp, vp, l, l, i, i, i, u, d, d, d, i, u, vp]
-        L.f16_mpc_plan_warm_start.argtypes = [vp, i]
-        if hasattr(L, "f16_mpc_plan_soft_rows"):    # (absent from an older library loaded through F16HIP_SO for an A/B run)
-            L.f16_mpc_plan_soft_rows.argtypes = [vp, vp]
-        L.f16_mpc_plan_destroy.argtypes = [vp]
-        L.f16_mpc_plan_destroy.restype = None
+    cabi.declare(L)      # every signature include/f16_hip.h declares; a symbol an older or plant-only library lacks is skipped
     _LIB = L
     return L
 

@@ -9,6 +9,7 @@ import ctypes
 
 import numpy as np
 
+from . import cabi
 from . import lib as _lib
 from .mppi import philox4x32_10
 
@@ -32,9 +33,7 @@ def gust_coefficients_host(sigma, length, v0, dt_row):
     d3 = ctypes.c_double * 3
     sg, L = d3(*np.broadcast_to(np.asarray(sigma, dtype=np.float64), (3,))), d3(*np.broadcast_to(np.asarray(length, dtype=np.float64), (3,)))
     a, b = d3(), d3()
-    lib = ctypes.CDLL(_lib.build())
-    lib.f16_gust_coeffs_host.argtypes = [ctypes.POINTER(ctypes.c_double)] * 2 + [ctypes.c_double] * 2 + [ctypes.POINTER(ctypes.c_double)] * 2
-    lib.f16_last_error.restype = ctypes.c_char_p
+    lib = cabi.declare(ctypes.CDLL(_lib.build()))
     rc = lib.f16_gust_coeffs_host(sg, L, float(v0), float(dt_row), a, b)
     if rc != 0:
         raise _lib.F16HipError(f"libf16hip error {rc}: {lib.f16_last_error().decode()}")

@@ -15,7 +15,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, env_of, names
+from header_cases import header_parameters, names
+from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, env_of
 from test_rollout_rk_calls_cpu import BAD_METHOD, METHODS, clib  # noqa: F401  (clib: the fixture)
 
 U = 2.0 ** -53
@@ -250,7 +251,6 @@ def refused(clib, symbol, method, ens, words, **over):
 @pytest.mark.parametrize("symbol", list(SIBLING))
 def test_parameter_lists_are_the_siblings_plus_the_ensemble(symbol):
     from f16_mpc_oop_py_amd import lib
-    from test_rollout_sched_cpu import header_parameters
     new, old = header_parameters(symbol), header_parameters(SIBLING[symbol])
     k = [p.replace("*", " ").split()[-1] for p in old].index("traj") + 1
     assert new == old[:k] + ["const f16_ens *h_ens"] + old[k:]

@@ -13,10 +13,10 @@ import pytest
 import torch
 
 from gs_cases import DH, DV, H0, NH, NV, V0, lookup_points, same_bits, small_schedule
+from header_cases import header, header_parameters, kind, names
 from test_mpc_loop_calls_cpu import B, DT, FI, FLAGS, XCG
-from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, address, env_of, names
+from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, address, env_of
 from test_rollout_rk_calls_cpu import BAD_METHOD, EULER, METHODS, RK4, call, calls_of, clib  # noqa: F401  (clib: the fixture)
-from test_rollout_sched_cpu import header_parameters
 
 GS = "f16_rollout_lqr_gs"
 
@@ -167,13 +167,11 @@ def test_header_library_and_binding_agree():
     # f16_rollout_lqr_rk's list with K replaced by the grid, the table and the period, and gs_out in front of status
     k, s = old.index("const double *K"), old.index("int32_t *status")
     assert new == old[:k] + ["const f16_gain_grid *h_grid", "const double *tab", "int gs_every"] + old[k + 1:s] + ["int32_t *gs_out"] + old[s:]
-    vp, gp = ctypes.c_void_p, ctypes.POINTER(lib.GainGrid)
-    kind = lambda p: gp if "f16_gain_grid" in p else vp if "*" in p else {"int": ctypes.c_int, "long": ctypes.c_long, "double": ctypes.c_double,
-                                                                          "unsigned": ctypes.c_uint}[p.split()[0]]
     for symbol in (GS, "f16_gain_lookup_host", "f16_debug_gain_lookup"):
         assert hasattr(exported, symbol), symbol
-        assert list(getattr(L, symbol).argtypes) == [kind(p) for p in header_parameters(symbol)], symbol
-    src = open(lib.__file__.replace("lib.py", "../include/f16_hip.h")).read()
+        assert list(getattr(L, symbol).argtypes) == [kind(p, lib) for p in header_parameters(symbol)], symbol
+    assert kind("const f16_gain_grid *h_grid", lib) == ctypes.POINTER(lib.GainGrid) and kind("const double *tab", lib) == ctypes.c_void_p
+    src = header(comments=True)
     assert "#define F16_GS_ENTRIES 12" in src and lib.F16_GS_ENTRIES == 12
     assert "typedef struct f16_gain_grid { double h0, dh, v0, dv; int nh, nv; } f16_gain_grid;" in src
     assert [f[0] for f in lib.GainGrid._fields_] == ["h0", "dh", "v0", "dv", "nh", "nv"]

@@ -2,23 +2,12 @@
 f16_rollout_mpc_relin_hold): the C-ABI boundary, and the argument checks of F16Batch.rollout_MPC(ctrl_every=...) and
 dist.closed_loop_mpc_rollout(ctrl_every=...) that come before any GPU call."""
 import ctypes
-import os
-import re
 
 import pytest
 
-from conftest import REPO
+from header_cases import header_parameters
 
 HOLD = {"f16_rollout_mpc_hold": "f16_rollout_mpc", "f16_rollout_mpc_relin_hold": "f16_rollout_mpc_relin"}
-
-
-def header_parameters(name):
-    """the parameter list of `name` as include/f16_hip.h declares it"""
-    src = open(os.path.join(REPO, "include", "f16_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;{]*)\)\s*;" % name, src)
-    assert m, f"{name} is not declared in include/f16_hip.h"
-    return [p.strip() for p in m.group(1).split(",")]
 
 
 def test_header_library_and_binding_agree_on_the_hold_entry_points():

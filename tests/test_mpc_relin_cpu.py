@@ -2,23 +2,12 @@
 F16Batch.rollout_MPC(relinearise=True) that come before any GPU call, and the checker loop the GPU tests compose from the C oracle
 (tests/test_gpu_mpc_relin.py), guarded here against the numpy pattern of tests/test_gpu_control.py::_oracle_closed_loop(relin=True)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+from header_cases import header_parameters
 from oracle import mpc_oracle as mo
-
-
-def header_parameters(name):
-    """the parameter list of `name` as include/f16_hip.h declares it"""
-    src = open(os.path.join(REPO, "include", "f16_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;{]*)\)\s*;" % name, src)
-    assert m, f"{name} is not declared in include/f16_hip.h"
-    return [p.strip() for p in m.group(1).split(",")]
 
 
 def test_header_library_and_binding_agree_on_the_relinearised_loop():

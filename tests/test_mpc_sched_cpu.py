@@ -3,29 +3,18 @@ f16_rollout_lqr_relin_sched): the C-ABI boundary, the argument checks of F16Batc
 F16Batch.rollout_LQR_relin(hold=...) and dist.closed_loop_mpc_rollout(dem_every=...) that come before any GPU call, and the fitness
 of the inputs of the CPU-twin test of tests/test_gpu_mpc_sched.py (a condition on the oracle alone)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
+from header_cases import header_parameters
 
 XCG = 0.35
 DT = 1e-3
 SCHED = {"f16_rollout_mpc_sched": "f16_rollout_mpc_hold", "f16_rollout_mpc_relin_sched": "f16_rollout_mpc_relin_hold",
          "f16_rollout_lqr_relin_sched": "f16_rollout_lqr_relin"}
 TWIN_ROWS = ((0.0, 0.0, 0.0), (0.02, -0.01, 0.005), (-0.02, 0.01, -0.005))      # the schedule of the CPU-twin test: 6 control steps, dem_hold 2
-
-
-def header_parameters(name):
-    """the parameter list of `name` as include/f16_hip.h declares it"""
-    src = open(os.path.join(REPO, "include", "f16_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;{]*)\)\s*;" % name, src)
-    assert m, f"{name} is not declared in include/f16_hip.h"
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
 
 
 def test_header_library_and_binding_agree_on_the_scheduled_closed_loops():

@@ -2,12 +2,11 @@
 sampling rule as mppi.sample_reference restates it (Philox4x32-10 + Box-Muller, include/f16_hip.h).  The device entries are tested in
 tests/test_gpu_mppi_loop.py."""
 import ctypes
-import os
 import re
 
 import numpy as np
 
-from conftest import REPO
+from header_cases import header
 
 # (counter, key, output) of Philox4x32-10: the known answers of include/f16_hip.h
 VECTORS = [([0, 0, 0, 0], [0, 0], [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]),
@@ -31,7 +30,7 @@ def test_philox_known_answers():
 
 
 def test_header_declares_the_three_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "f16_hip.h")).read(), flags=re.S)
+    src = header()
     for name in ("f16_mppi_sample", "f16_debug_philox", "f16_rollout_mppi"):
         assert re.search(r"\bint\s+" + name + r"\s*\(\s*f16_ctx\s*\*", src), name
 

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from header_cases import names
 from test_mpc_loop_calls_cpu import B, DT, FI, FLAGS, XCG, recording_env
-from test_rollout_sched_cpu import header_parameters
 
 F16_OK, F16_EINVAL = 0, -1                                                     # include/f16_hip.h
 FIVE = ("f16_rollout", "f16_rollout_sched", "f16_rollout_cost", "f16_rollout_lqr", "f16_rollout_lqr_sched")
@@ -24,11 +24,6 @@ NEEDED = {"f16_rollout_sched": (("u_seq",), "u_seq is NULL"),
           "f16_rollout_lqr": (("K", "dem"), "K / dem is NULL"),
           "f16_rollout_lqr_sched": (("K", "dem_seq"), "K / dem_seq is NULL")}
 HELD = ("f16_rollout_sched", "f16_rollout_lqr_sched", "f16_rollout_cost")      # the calls that take `hold`
-
-
-def names(symbol):
-    """the parameter names of `symbol` in the order of include/f16_hip.h"""
-    return [p.replace("*", " ").split()[-1] for p in header_parameters(symbol)]
 
 
 # ------------------------------------------------------------------------------------------------ the C rules

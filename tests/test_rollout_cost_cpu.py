@@ -2,18 +2,12 @@
 the blend rule as mppi.blend_reference states it.  The device entries are tested in tests/test_gpu_rollout_cost.py."""
 import ctypes
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import REPO
-
-
-def header():
-    src = open(os.path.join(REPO, "include", "f16_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+from header_cases import header
 
 
 def test_header_declares_the_two_entries_and_the_weights():

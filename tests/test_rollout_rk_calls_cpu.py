@@ -12,8 +12,8 @@ import pytest
 import torch
 
 from test_mpc_loop_calls_cpu import B, DT, FI, FLAGS, XCG
-from test_rollout_calls_cpu import (BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, POINTERS, address, env_of, names)
-from test_rollout_sched_cpu import header_parameters
+from header_cases import header, header_parameters, names
+from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, POINTERS, address, env_of
 
 EULER, RK4 = 1, 4                                                              # F16_INT_EULER, F16_INT_RK4 (include/f16_hip.h)
 THREE = {"f16_rollout_rk": "f16_rollout_sched", "f16_rollout_lqr_rk": "f16_rollout_lqr_sched", "f16_rollout_cost_rk": "f16_rollout_cost"}
@@ -62,8 +62,7 @@ def test_parameter_lists_are_the_scheduled_ones_plus_the_method(symbol):
     at, bt = getattr(L, symbol).argtypes, getattr(L, THREE[symbol]).argtypes
     assert list(at) == list(bt[:k]) + [ctypes.c_int] + list(bt[k:])
     assert hasattr(ctypes.CDLL(lib.build()), symbol)
-    src = open(lib.__file__.replace("lib.py", "../include/f16_hip.h")).read()
-    assert re.search(r"#define\s+F16_INT_EULER\s+1\b", src) and re.search(r"#define\s+F16_INT_RK4\s+4\b", src)
+    assert re.search(r"#define\s+F16_INT_EULER\s+1\b", header()) and re.search(r"#define\s+F16_INT_RK4\s+4\b", header())
     assert (lib.F16_INT_EULER, lib.F16_INT_RK4) == (EULER, RK4)
 
 

@@ -2,28 +2,18 @@
 (tools/make_golden.py: g17_input_schedules -- the reference's step loop and LQR loop under inputs that change during the run)
 against the C restatement chained per segment.  Tolerances: SURVEY.md 8(d), 1e-8 relative for xcg 0.25, 1e-6 for 0.35."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import REPO, golden
+from conftest import golden
+from header_cases import header_parameters
 
 SCHED = ("f16_rollout_sched", "f16_rollout_lqr_sched")
 
 
 def rel(a, b):
     return np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b)))
-
-
-def header_parameters(name):
-    """the parameter list of `name` as include/f16_hip.h declares it"""
-    src = open(os.path.join(REPO, "include", "f16_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^;{]*)\)\s*;" % name, src)
-    assert m, f"{name} is not declared in include/f16_hip.h"
-    return [p.strip() for p in m.group(1).split(",")]
 
 
 def test_header_library_and_binding_agree_on_the_scheduled_entry_points():

@@ -16,7 +16,8 @@ import pytest
 
 import envelope_cases as ec
 import wind_cases as wc
-from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, env_of, names
+from header_cases import header_parameters, names
+from test_rollout_calls_cpu import BAD_ARGUMENT, BAD_STEPS, F16_EINVAL, F16_OK, env_of
 from test_rollout_rk_calls_cpu import BAD_METHOD, METHODS, clib  # noqa: F401  (clib: the fixture)
 
 # the twin rebuilds xdot[6..8] through ~40 roundings (two conversions between the triple and body axes), each amplified by at most
@@ -98,10 +99,9 @@ def test_gust_coeffs_host_against_numpy():
         ah, bh = gust_coefficients_host(sigma, length, v0, dt)
         assert np.all(np.abs(ah - a) <= 2 * wc.EPS * a) and np.all(np.abs(bh - b) <= 8 * wc.EPS * np.maximum(b, 1e-300) / np.sqrt(1 - a * a))
         assert np.all((0 < a) & (a < 1))
-    from f16_mpc_oop_py_amd import lib
-    L = ctypes.CDLL(lib.build())
+    from f16_mpc_oop_py_amd import cabi, lib
+    L = cabi.declare(ctypes.CDLL(lib.build()))
     d3 = ctypes.c_double * 3
-    L.f16_gust_coeffs_host.argtypes = [ctypes.POINTER(ctypes.c_double)] * 2 + [ctypes.c_double] * 2 + [ctypes.POINTER(ctypes.c_double)] * 2
     ok = (d3(1, 1, 1), d3(100, 100, 100), 500.0, 0.01, d3(), d3())
     assert L.f16_gust_coeffs_host(*ok) == F16_OK
     for k, bad in ((0, None), (1, None), (4, None), (5, None), (0, d3(1, -1, 1)), (0, d3(1, float("nan"), 1)), (1, d3(100, 0, 100)),
@@ -170,7 +170,6 @@ def refused(clib, symbol, method, wind, words, **over):
 @pytest.mark.parametrize("symbol", list(SIBLING))
 def test_parameter_lists_are_the_siblings_plus_the_air(symbol):
     from f16_mpc_oop_py_amd import lib
-    from test_rollout_sched_cpu import header_parameters
     new, old = header_parameters(symbol), header_parameters(SIBLING[symbol])
     k = [p.replace("*", " ").split()[-1] for p in old].index("traj")
     assert new == old[:k] + ["const f16_wind *h_wind"] + old[k:]

@@ -18,9 +18,11 @@ the first that fails ends the run.  From the repository root:
     python tools/gpu_time_rollout_wind.py --build-parent HEAD~1          (no GPU needed; writes _exp/parent/libf16hip.so)
     python tools/gpu_time_rollout_wind.py > profiles/rollout_wind_time.jsonl      (on the GPU)"""
 import argparse
+import ast
 import ctypes
 import json
 import os
+import re
 import subprocess
 import sys
 import tempfile
@@ -40,8 +42,8 @@ def build_parent(rev):
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", REPO, "archive", rev, "f16_mpc_oop_py_amd/csrc", "include", "f16_mpc_oop_py_amd/lib.py"], capture_output=True, check=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-        names = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, sys.argv[1]); import lib; print(' '.join(lib.SOURCES))",
-                                os.path.join(tmp, "f16_mpc_oop_py_amd")], capture_output=True, text=True, check=True).stdout.split()
+        # (read, not imported: lib.py is a module of its package and does not import on its own)
+        names = ast.literal_eval(re.search(r"^SOURCES = (\[.*\])$", open(os.path.join(tmp, "f16_mpc_oop_py_amd", "lib.py")).read(), re.M).group(1))
         srcs = [os.path.join(tmp, "f16_mpc_oop_py_amd", "csrc", s) for s in names]
         subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + lib.HIPCC_FLAGS + ["-o", PARENT_SO] + srcs, check=True)
     print(f"{PARENT_SO}: built from {rev}")
