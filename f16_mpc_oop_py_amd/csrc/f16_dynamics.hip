@@ -731,8 +731,8 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 //                     moment equations
 //   wave 2  x[0..8]   sin/cos of phi, theta, beta, alpha on sub-lanes 0..3; kinematic +     | force equations, Euler
 //                     navigation equations, Euler on x[0..5]; the trajectory sample
-//   wave 3  x[12..17] atmosphere; the four actuators on sub-lanes 0..3; flap model, Euler;  | --
-//                     the LQR law and the input schedule
+//   wave 3  x[12..17] atmosphere; the four actuators on sub-lanes 0..3; flap model, Euler;  | the altitude part of the next step's
+//                     the LQR law and the input schedule                                    |   atmosphere (GROUPS = 1)
 // Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached), and with the cells the
 // TABLE VALUES read then (LongCorners / LatCorners, f16_plant_quad.hpp: the four / eight corner sets, the 1-D rows, the 45-degree
 // node): on such a step -- 93 % of the workload's -- a table wave forms no table address and reads nothing from LDS but the
@@ -760,7 +760,15 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // the constants cost the trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28
 // vector registers for the sin/cos table.  Same operations, same operands, same order.
 // Wave 2 publishes x[0..5] and tests x[2] where they become final, behind barrier B, under the wait for the totals; between the
-// last Euler update and barrier A it writes x[6..8] and its envelope flag only.
+// last Euler update and barrier A it writes x[6..8] and its envelope flag only.  (The box test on x[6..8] made by the waves that
+// read them, with no flag write in front of the barrier, was built and measured: not distinguishable, DESIGN.md.)
+// GROUPS = 1: the altitude-only part of the atmosphere -- tfac, the temperature with its 35,000 ft select, tfac^4 and the
+// extended-precision quotient of log tfac (atmos_alt, log_k_quot, f16_plant.hpp) -- is evaluated HALF A STEP AHEAD, in wave 3's second
+// half, which was empty: x[2] is final since wave 2's first half, which hands it over beside psi.  Behind barrier A wave 3 is left
+// with the log's polynomial and sums, the exp, the density and -- the only part that needs this step's airspeed -- qbar.  The cut
+// stands where the stamps put it: with the whole log ahead wave 3 paced the second half (883 cycles against wave 1's 728).
+// A wave reads its OWN states from its registers, not from LDS: wave 2's sin / cos polynomial starts without an LDS round trip, and
+// the sample's reads and stores stand under it.
 template <int GROUPS, bool LQR = false, bool SCHED = false>
 __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a) {
   constexpr int NA = 16 * GROUPS;
@@ -768,7 +776,9 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   __shared__ double xs[18][NA], xt[11][NA];                // published state; Cx Cz Cm | Cy Cn Cl static | qbar ps | Cy Cn Cl damping
   __shared__ int xenv[3][NA], xst[2][NA];
-  __shared__ double xpsi[3][NA];                           // psi after the step (wave 2 -> wave 0), its sin / cos (wave 0 -> wave 2)
+  // psi after the step (wave 2 -> wave 0), its sin / cos (wave 0 -> wave 2); GROUPS = 1: [3] the altitude after the step (wave 2 ->
+  // wave 3, written with psi in one ds_write2_b64)
+  __shared__ double xpsi[G1 ? 4 : 3][NA];
 #ifdef F16_EXP_STAMPQ
   const unsigned long long tstage0 = __builtin_amdgcn_s_memtime();
 #endif

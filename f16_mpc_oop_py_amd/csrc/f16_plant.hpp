@@ -119,8 +119,15 @@ constexpr PowK POW_K = {
     {1.53670161652585818e-01, 1.52503063567000663e-01, 1.81863527724766383e-01, 2.22221384831011309e-01, 2.85714293974435540e-01,
      3.99999999961319630e-01, 6.66666666666728247e-01}};
 
+// log_k in the two parts of its straight line (the quad rollout evaluates them in different halves of a step, f16_quad_steps.inc):
+// log_k_quot -- mantissa, exponent and the extended-precision quotient (y - 1) / (y + 1); log_k_sum -- polynomial, the sums, the
+// special arguments.
+struct LogQuot {
+  double h, l;                     // the quotient, high and low part
+  int e;                           // exponent of the argument
+};
 template <typename OP = KScalar>
-F16_DEV double log_k(const PowK &K, double x) {
+F16_DEV LogQuot log_k_quot(const PowK &K, double x) {
   const double m = __builtin_amdgcn_frexp_mant(x);
   const bool lo = m < K.two_thirds;
   const double sc = lo ? 2.0 : 1.0;
@@ -140,6 +147,12 @@ F16_DEV double log_k(const PowK &K, double x) {
   const double d32 = d28 + (((ym1 - d28) - s25) - s27);
   const double h = fma(r, d32, q);                         // quotient, high part
   const double l = fma(r, d32, -fma(-ym1, r, h));          // low part
+  return {h, l, e};
+}
+template <typename OP = KScalar>
+F16_DEV double log_k_sum(const PowK &K, double x, const LogQuot &qt) {
+  const double h = qt.h, l = qt.l;
+  const int e = qt.e;
   const double z = h * h;
   double c = OP::vvk(z, K.L[0], K.L[1]);
 #pragma unroll
@@ -170,6 +183,10 @@ F16_DEV double log_k(const PowK &K, double x) {
   res = x < 0.0 ? __builtin_nan("") : res;
   return x == 0.0 ? -__builtin_inf() : res;
 }
+template <typename OP = KScalar>
+F16_DEV double log_k(const PowK &K, double x) {
+  return log_k_sum<OP>(K, x, log_k_quot<OP>(K, x));
+}
 
 template <typename OP = KScalar>
 F16_DEV double exp_k(const PowK &K, double x) {
@@ -185,25 +202,43 @@ F16_DEV double exp_k(const PowK &K, double x) {
   return x < -1075.0 ? 0.0 : res;
 }
 
-// C/nlplant.c:467-490; pw(tfac) = exp(0.14 log tfac) of the default build (below)
-template <typename PW>
-F16_DEV void atmos_with(double alt, double vt, double &mach, double &qbar, double &ps, PW pw) {
-  const double rho0 = 2.377e-3;
-  const double tfac = 1 - .703e-5 * alt;
-  double temp = 519.0 * tfac;
-  if (alt >= 35000.0) temp = 390;
+// C/nlplant.c:467-490 in its two parts; pw(tfac) = exp(0.14 log tfac) of the default build (below).
+// (1) what the altitude alone decides: the quad rollout evaluates it half a step ahead of (2), f16_quad_steps.inc
+struct AtmosAlt {
+  double tfac, temp, t4;           // t4 = (tfac^2)^2, F16_FAST_POW only
+};
+F16_DEV AtmosAlt atmos_alt(double alt) {
+  AtmosAlt h;
+  h.tfac = 1 - .703e-5 * alt;
+  h.temp = 519.0 * h.tfac;
+  if (alt >= 35000.0) h.temp = 390;
 #ifdef F16_FAST_POW
   // tfac^4.14 = (tfac^2)^2 * exp(0.14 log tfac): |0.14 log tfac| < 0.2 on the flight envelope keeps the
   // exp-of-log error below 1 ulp; two exact-to-0.5ulp squarings on top => <= 2 ulp vs libm pow.
-  const double t2 = tfac * tfac;
-  const double rho = rho0 * ((t2 * t2) * pw(tfac));
+  const double t2 = h.tfac * h.tfac;
+  h.t4 = t2 * t2;
 #else
-  const double rho = rho0 * pow(tfac, 4.14);
+  h.t4 = 0;
 #endif
-  mach = vt / sqrt(1.4 * 1716.3 * temp);
+  return h;
+}
+// (2) density, and with the airspeed mach, qbar, ps
+template <typename PW>
+F16_DEV void atmos_air(const AtmosAlt &h, double vt, double &mach, double &qbar, double &ps, PW pw) {
+  const double rho0 = 2.377e-3;
+#ifdef F16_FAST_POW
+  const double rho = rho0 * (h.t4 * pw(h.tfac));
+#else
+  const double rho = rho0 * pow(h.tfac, 4.14);
+#endif
+  mach = vt / sqrt(1.4 * 1716.3 * h.temp);
   qbar = .5 * rho * (vt * vt);
-  ps = 1715.0 * rho * temp;
+  ps = 1715.0 * rho * h.temp;
   if (ps == 0) ps = 1715;
+}
+template <typename PW>
+F16_DEV void atmos_with(double alt, double vt, double &mach, double &qbar, double &ps, PW pw) {
+  atmos_air(atmos_alt(alt), vt, mach, qbar, ps, pw);
 }
 F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double &ps) {
   atmos_with(alt, vt, mach, qbar, ps, [](double tfac) { return exp(0.14 * log(tfac)); });

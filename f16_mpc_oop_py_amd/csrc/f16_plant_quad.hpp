@@ -32,8 +32,19 @@ F16_DEV int quad_bcast_i(int v) {
 // The values are computed where this call stands: the compiler may neither move the arithmetic that forms them behind it nor
 // fuse it with their later uses (an empty statement that claims to rewrite each of them in its vector registers).
 F16_DEV void quad_taken_here_1(double &v) { asm volatile("" : "+v"(v)); }
+F16_DEV void quad_taken_here_1(int &v) { asm volatile("" : "+v"(v)); }
 template <typename... T>
 F16_DEV void quad_taken_here(T &...v) { (quad_taken_here_1(v), ...); }
+
+// One trajectory sample from the five values sub-lane s read of the published state (states s, s + 4, s + 8, ...; the fifth only
+// on sub-lanes 0 and 1) to tr + k ld.
+F16_DEV void quad_store_sample(const double (&smp)[5], double *tr, int s, long ld) {
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int kk = s + 4 * j;
+    if (kk < 18) __builtin_nontemporal_store(smp[j], tr + kk * ld);
+  }
+}
 
 // The three axis brackets of a role, ONE PER SUB-LANE (0: alpha on ALPHA1, 1: beta, 2/3: elevator on DH1 or DH2), shared
 // across the quad by DPP broadcasts: first the cell indices (the table addresses need nothing else), later lambda.

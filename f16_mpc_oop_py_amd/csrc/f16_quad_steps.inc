@@ -7,10 +7,16 @@
 // aircraft, and stay in registers across the loop -- wave 2 and wave 0 the sin/cos table, wave 3 the exp / log table; no step
 // loads them again.  Wave 0 evaluates the first step's psi with that table (the form of the loop: on a NaN psi the literal form
 // differs in the sign of the NaN, and a continued rollout must give the bits of one launch).  Wave 2 publishes x[0..5] and tests
-// x[2] for the first trip; from then on it does both where these states become final, behind barrier B (below).
+// x[2] for the first trip; from then on it does both where these states become final, behind barrier B (below).  Wave 3 evaluates
+// the altitude part of the first step's atmosphere and the quotient of its log (atmos_alt, log_k_quot) from the x[2] it loaded;
+// from then on behind barrier B, from the altitude wave 2 hands over beside psi (xpsi[3]) -- half a step ahead of their use.
+// GROUPS = 1, behind barrier A: a wave takes the states it owns from its registers, not from the published copy (wave 2 the angles
+// of its sin / cos polynomial and the airspeed, wave 1 its P, Q, R).
     [[maybe_unused]] SinCosK ksc = {};
     [[maybe_unused]] PowK kpw = {};
     [[maybe_unused]] bool env_h = false;                   // wave 2: x[2] outside its box, tested where x[2] was last advanced
+    [[maybe_unused]] AtmosAlt ah = {};                    // wave 3: the altitude part of the coming step's atmosphere (atmos_alt) ...
+    [[maybe_unused]] LogQuot lq = {};                      //         ... and the quotient of log tfac (log_k_quot), taken half a step ahead
     if constexpr (G1) {
       if (wave == 0 || wave == 2) ksc = reloaded(QUAD_K.sc);
       if (wave == 3) kpw = reloaded(QUAD_K.pw);
@@ -31,6 +37,11 @@
 #pragma unroll
           for (int k = 0; k < 6; ++k) xs[k][ac] = x[k];
         }
+      }
+      if (wave == 3) {                                     // the first step's altitude part, in the form of the loop (second half, below)
+        ah = atmos_alt(x[2]);
+        lq = log_k_quot(kpw, ah.tfac);
+        quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e);
       }
       // The states a role neither owns nor reads are dead from here on: the epilogue writes back a role's own states only, but it
       // stands behind the join of the four loops, where the compiler no longer knows the role, and kept all 18 in registers across
@@ -78,40 +89,50 @@
       // trajectory sample of the step that just finished: all 18 states straight from the published copy, by the wave
       // with the most slack in the first half (wave 2 since the actuator wave became the longest; sub-lane s stores states
       // s, s+4, s+8, ...)
-      // GROUPS = 1: the step's own reads of the published copy are issued FIRST and the sample's five reads right behind them,
-      // all before the first store -- one LDS round trip for both (read, wait, store per state, this wave paid three in a row
-      // with nothing to switch to, and only then asked for its step inputs).  The extra trip reads the copy for nothing.
+      // GROUPS = 1: a wave takes the states it owns from its registers (xs[k] is a copy of x[k], for a frozen aircraft and on the
+      // first trip too) -- wave 2 x[3], x[4], x[6..8], so that its sin / cos polynomial starts without an LDS round trip, wave 1 its
+      // P, Q, R -- and reads the rest from the published copy.  The sample's five reads are issued with the step inputs,
+      // every trip (fenced there, or the compiler moves them into the branch that stores them and splits them round the first four
+      // stores: a second round trip), and its stores stand UNDER that polynomial; on the extra trip on the way out of the loop.
       double xa[17];
       int env_any = 0;
       if constexpr (G1) {
         env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
 #pragma unroll
         for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
+        if (wave == 2) { xa[3] = x[3]; xa[4] = x[4]; xa[6] = x[6]; xa[7] = x[7]; xa[8] = x[8]; }
+        if (wave == 1) { xa[9] = x[9]; xa[10] = x[10]; xa[11] = x[11]; }
+      }
+      [[maybe_unused]] double smp[5] = {0, 0, 0, 0, 0};    // GROUPS = 1, wave 2: read with the step inputs, whether or not a sample is due
+      [[maybe_unused]] bool sample_due = false;
+      if constexpr (G1) {
+        if (wave == 2) {
+#pragma unroll
+          for (int j = 0; j < 5; ++j) smp[j] = xs[s + 4 * j < 18 ? s + 4 * j : s][ac];
+          asm volatile("" ::: "memory");                   // (read HERE: no load moves behind this, into the branch that stores them)
+        }
       }
       if (wave == 2 && tr && t > 0 && --until_store == 0) {
         until_store = a.traj_every;
-        if (valid) {
-          if constexpr (G1) {
-            double smp[5];
-#pragma unroll
-            for (int j = 0; j < 5; ++j) smp[j] = xs[s + 4 * j < 18 ? s + 4 * j : s][ac];
-            __builtin_amdgcn_sched_barrier(0);             // every read above, every store below
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-              const int kk = s + 4 * j;
-              if (kk < 18) __builtin_nontemporal_store(smp[j], tr + kk * a.ld);
-            }
-          } else {
+        if constexpr (G1) {
+          sample_due = true;                               // (stored under the sin / cos polynomial below, on the extra trip on the way out)
+        } else {
+          if (valid) {
 #pragma unroll
             for (int j = 0; j < 5; ++j) {
               const int kk = s + 4 * j;
               if (kk < 18) __builtin_nontemporal_store(xs[kk][ac], tr + kk * a.ld);
             }
           }
+          tr += 18 * a.ld;
         }
-        tr += 18 * a.ld;
       }
-      if (t == a.nsteps) break;
+      if (t == a.nsteps) {
+        if constexpr (G1) {
+          if (sample_due && valid) quad_store_sample(smp, tr, s, a.ld);
+        }
+        break;
+      }
       if constexpr (!G1) {
         env_any = xenv[0][ac] | xenv[1][ac] | xenv[2][ac];
 #pragma unroll
@@ -148,10 +169,23 @@
       } else if (wave == 2) {
         // sin / cos of phi, theta, beta, alpha: one angle per sub-lane, then shared across the quad; psi's from wave 0
         // (GROUPS = 2: psi on sub-lane 2, beta in a round of its own on every lane)
-        const double ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? (G1 ? xa[8] : xa[5]) : xa[7]));
+        double ang;
+        if constexpr (G1) {                                // (from registers: one select behind the other, or the compiler branches round them)
+          ang = xa[7];
+          ang = s == 2 ? xa[8] : ang;
+          ang = s == 1 ? xa[4] : ang;
+          ang = s == 0 ? xa[3] : ang;
+        } else
+          ang = s == 0 ? xa[3] : (s == 1 ? xa[4] : (s == 2 ? xa[5] : xa[7]));
         double sn, cs, sb, s_psi, c_psi;
         if constexpr (G1) F16_SINCOS_KC(KVector, ksc, ang, &sn, &cs);   // (the table loaded in front of the loop, into vector registers)
         else F16_SINCOS(ang, &sn, &cs);
+        if constexpr (G1) {                                // (under the polynomial: its angles come from registers, the sample from LDS)
+          if (sample_due) {
+            if (valid) quad_store_sample(smp, tr, s, a.ld);
+            tr += 18 * a.ld;
+          }
+        }
         // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
         //  changes x[1] in the last place)
         if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
@@ -194,7 +228,9 @@
 #pragma unroll
             for (int k = 0; k < 6; ++k) x[k] += xd[k] * a.dt;   // env.py:126 (navigation / kinematic states)
           }
-          if (G1 && s == 0) xpsi[0][ac] = x[5];                  // wave 0 evaluates its sin / cos in the second half
+          // wave 0 evaluates psi's sin / cos in the second half, wave 3 the altitude part of the next step's atmosphere (a frozen
+          // aircraft hands over the values it was frozen with; not through xs[2], which is still being read in this half)
+          if constexpr (G1) if (s == 0) { xpsi[0][ac] = x[5]; xpsi[3][ac] = x[2]; }
         }
         // (in a loop of its own a role's two halves are one piece of code: left alone, the compiler moves what only the second
         //  half uses -- the three reciprocals, fu0 .. fw0 -- behind barrier B, into the half this wave sets the pace of, and
@@ -205,9 +241,14 @@
         if (vt <= 0.01) vt = 0.01;
         double mach, qbar, ps;
         double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
-        if constexpr (G1)                                  // (the table loaded in front of the loop)
-          atmos_with(xa[2], vt, mach, qbar, ps, [&](double tfac) { return pw = exp_k(kpw, 0.14 * log_k(kpw, tfac)); });
-        else
+        if constexpr (G1) {
+          // the altitude part (ah) and the quotient of the log (lq) were evaluated behind barrier B of the last step: what is left
+          // needs no LDS read up to the density and runs under the wait for x[6], x[7]; only qbar takes this step's airspeed.
+          // (pinned behind barrier A too: the compiler moved the rest of the chain in front of it, into the half wave 3 then paced)
+          quad_taken_here(ah.tfac, lq.h, lq.l, lq.e);
+          pw = exp_k(kpw, 0.14 * log_k_sum(kpw, ah.tfac, lq));   // (the table loaded in front of the loop)
+          atmos_air(ah, vt, mach, qbar, ps, [pw](double) { return pw; });
+        } else
           atmos_dev(xa[2], vt, mach, qbar, ps);
         if (s == 0) { xt[6][ac] = qbar; xt[7][ac] = ps; }
         if (live) {
@@ -224,9 +265,9 @@
           const double dsf = actuator_rate(uc, -lim, lim, 20.2, xact, rate);
           double lf1_dot, lf2_dot;
           if constexpr (G1)
-            upd_lef_with(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot,
-                         [pw](double h_, double V_, double &m_, double &q_, double &p_) {      // (h_ is the altitude pw was taken at)
-                           atmos_with(h_, V_, m_, q_, p_, [pw](double) { return pw; });
+            upd_lef_with(0.0, xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot,
+                         [pw, &ah](double, double V_, double &m_, double &q_, double &p_) {    // (the step's altitude part and factor)
+                           atmos_air(ah, V_, m_, q_, p_, [pw](double) { return pw; });
                          });
           else
             upd_lef_dev(xa[2], xa[6], xa[7], x[17], x[16], qbar, ps, lf1_dot, lf2_dot);
@@ -302,9 +343,17 @@
           x[10] += (mo1 + F16_DIVC(M_tot, Jy)) * a.dt;
           x[11] += (mo2 + (Jx * N_tot + Jxz * L_tot) * rden) * a.dt;
         }
-      } else if (G1 && wave == 0 && s == 0) {              // sin / cos of the next step's psi, off wave 2's first half
-        double sp, cp;
-        F16_SINCOS_K(ksc, xpsi[0][ac], &sp, &cp);
-        xpsi[1][ac] = sp; xpsi[2][ac] = cp;
+      } else if constexpr (G1) {
+        if (wave == 0 && s == 0) {                         // sin / cos of the next step's psi, off wave 2's first half
+          double sp, cp;
+          F16_SINCOS_K(ksc, xpsi[0][ac], &sp, &cp);
+          xpsi[1][ac] = sp; xpsi[2][ac] = cp;
+        } else if (wave == 3) {
+          // the altitude part of the next step's atmosphere, off wave 3's first half: x[2] is final since wave 2's first half
+          // (the extra trip evaluates a log nobody uses).  Pinned here: what crosses barrier A is three values, not the chain.
+          ah = atmos_alt(xpsi[3][ac]);
+          lq = log_k_quot(kpw, ah.tfac);
+          quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e);
+        }
       }
     }

@@ -13,6 +13,7 @@ Two listings: prints
       blocks in program order (operands: the tree that last wrote the register pair, followed through vector moves; a scalar
       register, a value loaded or produced by any other instruction, or a register written outside the loop is an anonymous leaf;
       inline constants and operand modifiers -- neg, abs, clamp, omod -- are part of the node) and the multisets of trees compared;
+      LDS reads per loop are listed with the counts;
   (4) wave 2: ds_write* between its last fp64 instruction of the second half and barrier A.
 Exit status 1 if the gate fails: a scalar load in a role loop of the head; more lane moves, v_accvgpr_*, 64-bit moves or scratch
 in a loop than before; scratch in a <1,*> instantiation; fp64 trees that differ; more than three ds_write* in (4); barriers
@@ -26,7 +27,7 @@ LLVM = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(os.environ.
 FP64 = re.compile(r"v_(fma|fmac|mul|add|max|min|rcp|rsq|sqrt|div_scale|div_fmas|div_fixup|ldexp|frexp\w*|fract|floor|ceil|rndne|trunc)_f64")
 ROLES = ["wave 0 longitudinal tables, psi", "wave 1 lateral tables, moments", "wave 2 trigonometry, forces, sample", "wave 3 atmosphere, actuators"]
 NAMES = {}          # tree -> the instruction at its root (for the listing of unmatched trees)
-KEYS = ["instructions", "s_load", "lane moves", "v_accvgpr", "64-bit moves", "scratch", "s_barrier", "fp64"]
+KEYS = ["instructions", "LDS reads", "s_load", "lane moves", "v_accvgpr", "64-bit moves", "scratch", "s_barrier", "fp64"]
 
 
 def listing(tree):
@@ -181,7 +182,7 @@ def role_of(blocks):
 
 def count(blocks):
     ops = [i.split()[0] for b in blocks for i in b["ins"]]
-    return {"instructions": len(ops), "s_load": sum(o.startswith(("s_load", "s_buffer_load")) for o in ops),
+    return {"instructions": len(ops), "LDS reads": sum(o.startswith("ds_read") for o in ops), "s_load": sum(o.startswith(("s_load", "s_buffer_load")) for o in ops),
             "lane moves": sum(o.startswith(("v_readlane", "v_writelane", "v_readfirstlane")) for o in ops),
             "v_accvgpr": sum(o.startswith("v_accvgpr") for o in ops), "64-bit moves": sum(o.startswith(("v_mov_b64", "v_pk_mov_b32")) for o in ops),
             "scratch": sum(o.startswith("scratch_") for o in ops), "s_barrier": ops.count("s_barrier"), "fp64": sum(bool(FP64.match(o)) for o in ops)}
