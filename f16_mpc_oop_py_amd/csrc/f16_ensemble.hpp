@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/f16_hip.h"
 #include "f16_plant.hpp"
 
 namespace f16 {
@@ -109,5 +110,10 @@ F16_DEV EnsGroup ens_fold_group(const double *rec, int nw, int k) {
   }
   return EnsGroup{(int)n, mean, m2, mn, mx};
 }
+
+// host, defined in f16_wind_ens.hip for the twins of other translation units (f16_observer.hip): the rules of an f16_ens, and the
+// finishing launch behind a rollout whose wavefronts wrote their records of S samples
+int ens_rules(const f16_ens *e, long B);
+int ens_finish_launch(const f16_ens *e, long B, int S, unsigned flags, void *stream, const char *what);
 
 }  // namespace f16

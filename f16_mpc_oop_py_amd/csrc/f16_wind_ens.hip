@@ -98,6 +98,11 @@ static int ens_finish(const EnsArgs &a, hipStream_t st, const char *what) {
   return hip_check(hipGetLastError(), what);
 }
 
+int ens_rules(const f16_ens *e, long B) { return check_ens(e, B); }
+int ens_finish_launch(const f16_ens *e, long B, int S, unsigned flags, void *stream, const char *what) {
+  return ens_finish(ens_args(e, B, S, flags), (hipStream_t)stream, what);
+}
+
 template <bool LQR>
 static int wind_rollout_ens(f16_ctx *ctx, const char *missing, double *x, const double *u, const double *K, const double *seq, const f16_wind *w,
                             double *traj, const f16_ens *e, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,

@@ -1,11 +1,13 @@
-// f16_wind_lanes.hpp -- what the wind rollout kernels of f16_wind.hip and their ensemble twins of f16_wind_ens.hip share, stated
-// once: the argument block, the lane loop (wind_lanes) and, on the host, the argument rules and the filling of the block.
+// f16_wind_lanes.hpp -- what the wind rollout kernels of f16_wind.hip, their ensemble twins of f16_wind_ens.hip and the
+// output-feedback twins of f16_observer.hip share, stated once: the argument block, the lane loop (wind_lanes) and, on the host, the
+// argument rules and the filling of the block.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/f16_hip.h"
 #include "f16_ctx.h"
 #include "f16_ensemble.hpp"
+#include "f16_observer.hpp"
 #include "f16_plant.hpp"
 #include "f16_rollout_common.hpp"
 #include "f16_wind.hpp"
@@ -33,9 +35,17 @@ struct WindArgs : SchedArgs {
 // (ens_wave_records) into ework[sample][wave][ENS_REC].  A WAVEFRONT runs the loop as a whole -- the loop condition looks at the
 // wave's first aircraft -- and a lane without an aircraft (b0 >= B: `live` false) flies a copy of aircraft B - 1, which keeps its
 // loads inside the arrays (the padding columns are never read), stores nothing and contributes nothing.
-template <int BLOCK, bool LQR, int STAGES, bool EXACT, bool ENS = false>
+// OBS (with LQR): output feedback (f16_observer.hpp).  The action of a step comes from the state at the start of the step through
+// measurement, correction, the LQR law on the estimate and prediction (observer_rule; under EXACT the out-of-line observer_update)
+// instead of from the state; o is the workgroup's ObsArgs in LDS.  The prediction lives in the xhat array between steps (a coalesced
+// 72 B read and write per aircraft and step, L2-resident: nine more doubles held across the Runge-Kutta step would not stay in
+// registers); at a sample point it is copied to xhat_traj.  With ENS a lane without an aircraft runs the rule too, as the copy of
+// aircraft B - 1 it is: it reads and writes column B - 1 of xhat in the same instructions as that aircraft's own lane of the same
+// wavefront, the same bits from the same inputs -- the one store such a lane makes.
+template <int BLOCK, bool LQR, int STAGES, bool EXACT, bool ENS = false, bool OBS = false>
 __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, double (*us)[BLOCK], double (*kq)[BLOCK], double (*ws)[BLOCK],
-                                           double *ework = nullptr) {
+                                           double *ework = nullptr, [[maybe_unused]] const ObsArgs *o = nullptr) {
+  static_assert(!OBS || LQR, "the observer feeds the LQR law");
   const bool gen = a.ga != nullptr;
   SchedArgs g = a;                   // the gust rows seen as a schedule of three values per row
   g.seq = a.gseq ? a.gseq : a.out; g.hold = a.ghold; g.nrows = a.grows;
@@ -75,6 +85,7 @@ __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, d
     int st = a.status ? a.status[b] : 0;
     double *tr = a.traj ? a.traj + b : nullptr;
     int until_store = a.traj_every;
+    [[maybe_unused]] long xsmp = 0;           // (OBS) the sample of xhat_traj to write next, in doubles: the same on every lane
     [[maybe_unused]] double *rec = ENS ? ework + (b0 >> 6) * ENS_REC : nullptr;       // the wave's record of the next sample
     constexpr int NR = LQR ? 3 : 4;
     RowAhead<NR> ra;
@@ -87,7 +98,13 @@ __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, d
         double u[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) u[k] = us[k][threadIdx.x];
-        if (LQR) {   // the controller reads the state, not the air data
+        if constexpr (OBS) {   // the controller reads the estimate
+          const uint32_t row = o->mrow0 + (uint32_t)t;
+          const Obs3 c = EXACT ? observer_update(o, b, row, x[3], x[4], x[7], x[8], x[9], x[10], x[11], x[17], x[16], x[13], x[14], x[15])
+                               : observer_rule(o, b, row, x[3], x[4], x[7], x[8], x[9], x[10], x[11], x[17], x[16], x[13], x[14], x[15]);
+#pragma unroll
+          for (int i = 0; i < 3; ++i) ul[i] = u[1 + i] = c.v[i];
+        } else if (LQR) {   // the controller reads the state, not the air data
           const double e0 = kq[9][threadIdx.x] - x[9], e1 = kq[10][threadIdx.x] - x[10], e2 = kq[11][threadIdx.x] - x[11];
 #pragma unroll
           for (int i = 0; i < 3; ++i)
@@ -107,12 +124,33 @@ __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, d
           until_store = a.traj_every;
           ens_wave_records(x, live, a.flags, rec);
           rec += ((a.B + 63) >> 6) * ENS_REC;
+          if constexpr (OBS) {
+            if (o->xhat_traj && live) {
+#pragma unroll
+              for (int k = 0; k < 9; ++k) __builtin_nontemporal_store(o->xhat[k * a.ld + b], o->xhat_traj + xsmp + k * a.ld + b);
+            }
+            xsmp += 9 * a.ld;
+          }
           if (tr) {
             if (live) {
 #pragma unroll
               for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
             }
             tr += 18 * a.ld;
+          }
+        }
+      } else if constexpr (OBS) {
+        if ((tr || o->xhat_traj) && --until_store == 0) {
+          until_store = a.traj_every;
+          if (tr) {
+#pragma unroll
+            for (int k = 0; k < 18; ++k) __builtin_nontemporal_store(x[k], tr + k * a.ld);
+            tr += 18 * a.ld;
+          }
+          if (o->xhat_traj) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) __builtin_nontemporal_store(o->xhat[k * a.ld + b], o->xhat_traj + xsmp + k * a.ld + b);
+            xsmp += 9 * a.ld;
           }
         }
       } else {
@@ -150,17 +188,21 @@ __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, d
     for (int k = 0; k < 18; ++k) finite = finite && isfinite(x[k]);
     if (!finite) st |= ST_NONFINITE;
     if (st & ST_ENVELOPE) st |= envelope_state_bits(x);
+    // (OBS: the write-back addresses are formed HERE, from an index the compiler cannot look through -- formed in the prologue they
+    // were carried across the Runge-Kutta step in scratch memory, the only values there)
+    long bw = b;
+    if constexpr (OBS) asm volatile("" : "+v"(bw));
 #pragma unroll
-    for (int k = 0; k < 18; ++k) a.out[k * a.ld + b] = x[k];
-    if (a.status) a.status[b] = st;
+    for (int k = 0; k < 18; ++k) a.out[k * a.ld + bw] = x[k];
+    if (a.status) a.status[bw] = st;
     if (LQR && a.u_out) {
-      a.u_out[b] = us[0][threadIdx.x];
+      a.u_out[bw] = us[0][threadIdx.x];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) a.u_out[(1 + i) * a.ld + b] = ul[i];
+      for (int i = 0; i < 3; ++i) a.u_out[(1 + i) * a.ld + bw] = ul[i];
     }
     if (gen) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) a.gstate[k * a.ld + b] = ws[3 + k][threadIdx.x];
+      for (int k = 0; k < 3; ++k) a.gstate[k * a.ld + bw] = ws[3 + k][threadIdx.x];
     }
   }
 }

@@ -273,15 +273,18 @@ class F16Batch:
         return e, (work, count, mean, m2, mn, mx), Ensemble(count, *(t.permute(0, 2, 1) for t in (mean, m2, mn, mx)), group=group)
 
     def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER, air=None, ensemble=None,
-                      keep_traj=False):
+                      keep_traj=False, observer=None):
         """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
         into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
         around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values.  method F16_INT_RK4:
         the _rk entry points, which are scheduled ones -- a constant input is one row held for every step.  ensemble (aircraft per
         group, or True): the _wind_ens entry points, which return the statistics of the samples (an ensemble.Ensemble; with
-        keep_traj the samples too); with ensemble=None the call is the one it was."""
+        keep_traj the samples too); with ensemble=None the call is the one it was.  observer = (observer.Observer, meas_seed,
+        return_estimate) with K: the _lqg_wind entry points (_observed_call)."""
         if ensemble is None and keep_traj:
             raise ValueError("keep_traj goes with ensemble=")
+        if observer is not None:
+            return self._observed_call(u, nsteps, traj_every, hold, K, dem, method, air, ensemble, keep_traj, *observer)
         every = int(traj_every or 1) if ensemble is not None else traj_every      # with ensemble= the sample period: every step by default
         traj = self._samples(nsteps, every) if ensemble is None or keep_traj else None
         # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
@@ -314,6 +317,42 @@ class F16Batch:
                                             self.B, int(nsteps), *held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag, *rule,
                                             self.flags, self._stream))
         return traj
+
+    def _observed_call(self, u0, nsteps, traj_every, hold, K, dem, method, air, ensemble, keep_traj, obs, meas_seed, want_estimate):
+        """The nonlinear rollout_LQR on noisy sensors through an observer: ONE call of f16_rollout_lqg_wind (with ensemble=:
+        f16_rollout_lqg_wind_ens) -- the _lqr_wind list with the observer behind the air.  No air = zero air through the wind kernels.
+        Returns what the call without observer returns; with want_estimate the samples of the estimate [S, 9, B] appended."""
+        if not 0 <= int(meas_seed) < 2 ** 64:
+            raise ValueError("meas_seed must fit 64 bits")
+        nsteps = int(nsteps)
+        if ensemble is not None:
+            every = int(traj_every or 1)
+            if every < 1 or nsteps % every:
+                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every}), the sample period of the ensemble")
+            traj = self._samples(nsteps, every) if keep_traj else None
+            est = self._samples(nsteps, every, rows=9) if want_estimate else None
+        else:
+            every = traj_every
+            traj = self._samples(nsteps, every)
+            est = self._samples(nsteps, every or 1, rows=9) if want_estimate else None
+        models, xhat = obs.flight(self)
+        head = (self.ctx.handle, _vp(self._x), _vp(u0), _vp(K), _vp(dem), None if air is None else ctypes.byref(air[0]), _vp(models), obs.group,
+                obs.sensed, obs.h_sigma, int(meas_seed), obs.row, _vp(xhat), _vp(traj), _vp(est))
+        tail = (_vp(self._u), _vp(self.status), self.B, self.B, nsteps, max(nsteps, 1) if hold is None else hold, int(every or 1), self.dt,
+                self.xcg, self.fi_flag, int(method), self.flags, self._stream)
+        result = None
+        if ensemble is not None:
+            e, keep, result = self._ensemble_buffers(ensemble, nsteps // every)
+            self._check(self.lib.f16_rollout_lqg_wind_ens(*head, ctypes.byref(e), *tail))
+            result._keep = keep      # (the workspace lives as long as the result: the launches may still be running)
+        else:
+            self._check(self.lib.f16_rollout_lqg_wind(*head, *tail))
+        obs.advance(nsteps)
+        if air is not None and air[2] is not None:
+            air[2].advance(nsteps)
+        out = (traj,) if ensemble is None else ((traj, result) if keep_traj else (result,))
+        out = out + (est,) if want_estimate else out
+        return out[0] if len(out) == 1 else out
 
     def rollout_schedule(self, actions, hold=1, nsteps=None, traj_every=None, method="euler", wind=None, gusts=None, gust_every=None,
                          ensemble=None, keep_traj=False):
@@ -773,7 +812,7 @@ class F16Batch:
 
     def rollout_LQR(self, nsteps, p_dem, q_dem, r_dem, K=None, u0=None, traj_every=None, linear=False, relinearise=False, Q=None,
                     R=None, hold=None, method="euler", schedule=None, gains_every=1, return_info=False, wind=None, gusts=None,
-                    gust_every=None, ensemble=None, keep_traj=False):
+                    gust_every=None, ensemble=None, keep_traj=False, observer=None, meas_seed=0, return_estimate=False):
         """The reference's LQR loops (test_env_mk2.py:25-88 `LQR(linear=...)`; flight_sim.py:139,181) as ONE launch.
         linear=False (test_env_mk2.py:70-85): per step `u = _calc_LQR_action(p_dem, q_dem, r_dem, K, x._get_mpc_x(),
         u.initial_condition[1:])`, `u.values[1:] = u`, `step(u.values)`, the state in registers for all nsteps.  K [B,3,9] defaults
@@ -803,7 +842,19 @@ class F16Batch:
         relinearise=True or schedule= (ValueError).
         ensemble=group / keep_traj= (see rollout_schedule): the statistics of the samples over the aircraft of each group instead of the
         samples (f16_rollout_lqr_wind_ens), on the same frozen-gain nonlinear loop, with or without wind= / gusts=; not combined
-        with linear=True, relinearise=True or schedule= (ValueError)."""
+        with linear=True, relinearise=True or schedule= (ValueError).
+        observer=obs (an observer.Observer), meas_seed=, return_estimate=: the same frozen-gain nonlinear loop on NOISY SENSORS -- per
+        step the sensed channels of the reduced state are measured with sampled noise (meas_seed: the key of the counter-based
+        sampler; it may equal a GustModel's seed), the observer corrects its estimate, the LQR law acts on the estimate and the
+        observer predicts (f16_rollout_lqg_wind / f16_rollout_lqg_wind_ens; include/f16_hip.h "OUTPUT FEEDBACK"), both methods, with
+        or without wind= / gusts= / ensemble=.  The estimate and the measurement-row counter live on the Observer: consecutive calls
+        continue one flight.  return_estimate=True appends the samples of the estimate [S, 9, B] (the content of the estimate at every
+        sample point: the prediction of the state stored there) to what the call returns.  Not combined with linear=True,
+        relinearise=True or schedule= (ValueError)."""
+        if observer is None and (return_estimate or meas_seed != 0):
+            raise ValueError("meas_seed and return_estimate go with observer=")
+        if observer is not None and (linear or relinearise or schedule is not None):
+            raise ValueError("observer= runs on the nonlinear loop with a fixed gain (not with linear=True, relinearise=True or schedule=)")
         if (ensemble is not None or keep_traj) and (linear or relinearise or schedule is not None):
             raise ValueError("ensemble= runs on the nonlinear loop with a fixed gain (not with linear=True, relinearise=True or schedule=)")
         if (wind is not None or gusts is not None) and (linear or relinearise or schedule is not None):
@@ -865,7 +916,8 @@ class F16Batch:
         else:
             u0s = self._soa(u0, 4)
         return self._rollout_call(u0s, nsteps, traj_every, hold=hold, K=Ks, dem=dem if dem_seq is None else dem_seq, method=method,
-                                  air=self._air(wind, gusts, gust_every, nsteps), ensemble=ensemble, keep_traj=keep_traj)
+                                  air=self._air(wind, gusts, gust_every, nsteps), ensemble=ensemble, keep_traj=keep_traj,
+                                  observer=None if observer is None else (observer, meas_seed, return_estimate))
 
     def rollout_LQR_relin(self, nsteps, x_ref=None, track=None, u0=None, Q=None, R=None, eps=1e-5, traj_every=None, gains_every=None,
                           hold=None):

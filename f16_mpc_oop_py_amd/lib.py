@@ -13,7 +13,7 @@ from . import cabi
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.environ.get("F16HIP_SO", os.path.join(HERE, "libf16hip.so"))   # override only for A/B experiments
-SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_mppi.hip", "f16_wind.hip", "f16_wind_ens.hip", "f16_debug.hip", "f16_tables.cpp"]
+SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.hip", "f16_mpc_wave.hip", "f16_mpc_big.hip", "f16_trim.hip", "f16_mppi.hip", "f16_wind.hip", "f16_wind_ens.hip", "f16_observer.hip", "f16_debug.hip", "f16_tables.cpp"]
 # the expression-exact (F16_STRICT) build of the plant alone: checker-side evidence that the device lookups and the plant
 # reproduce the reference bit for bit where no libm call is involved (tests/test_gpu_dynamics.py); never used by the product
 STRICT_SO_PATH = os.path.join(HERE, "libf16hip_strict.so")
@@ -41,6 +41,7 @@ F16_FLAG_NO_CELL_CACHE = _C["F16_FLAG_NO_CELL_CACHE"]  # diagnostic: quad rollou
 F16_INT_EULER, F16_INT_RK4 = _C["F16_INT_EULER"], _C["F16_INT_RK4"]    # the step rule of f16_rollout_rk / f16_rollout_lqr_rk / f16_rollout_cost_rk
 INTEGRATORS = {"euler": F16_INT_EULER, "rk4": F16_INT_RK4}
 F16_GS_ENTRIES = _C["F16_GS_ENTRIES"]          # doubles per node of a gain table: K[i][4 + j] at 3 i + j, the trim surface commands at 9 + i
+F16_OBS_DOUBLES = _C["F16_OBS_DOUBLES"]        # doubles per observer model record: Ad[81] Bd[27] Lf[81] x9_trim[9] s_trim[3], padded (observer.py)
 
 
 def integrator(method, rk4=True):

@@ -520,6 +520,77 @@ int f16_rollout_lqr_wind_ens(f16_ctx *ctx, double *x, const double *u0, const do
                              int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
 int f16_ens_from_traj(f16_ctx *ctx, const double *traj, int nsamples, long B, long ld, unsigned flags, const f16_ens *h_ens,
                       void *stream);
+/* OUTPUT FEEDBACK: the frozen-gain nonlinear LQR loop of f16_rollout_lqr_wind on NOISY SENSORS, through a steady-state Kalman filter
+ * on the reduced 9-state model, in one launch: sampled sensor noise, the filter between sensors and control law, the reference's LQR
+ * law on the estimate.  The rule is stated HERE ONCE; the device code (csrc/f16_observer.hpp) and the numpy restatement
+ * (f16_mpc_oop_py_amd/observer.py `observer_reference`, `meas_normals`, `kalman_reference`) follow it.
+ *   Notation.  MPC-state order (parameters.py:135: phi theta alpha beta p q r lf1 lf2): x9 = x[3, 4, 7, 8, 9, 10, 11, 17, 16];
+ *     s = x[13..15], the three surface positions -- the reduced model's inputs (env.py `_calc_xdot_na` writes u into those states).
+ *   Observer model: a record of F16_OBS_DOUBLES (208) contiguous doubles per model,
+ *         0 .. 80   Ad[81]      81 .. 107  Bd[27]      108 .. 188  Lf[81]      (all row-major)
+ *         189 .. 197  x9_trim[9]      198 .. 200  s_trim[3]      201 .. 207  zero padding
+ *     obs[M][208]: DEVICE.  Aircraft b uses model b / mgroup; mgroup is a multiple of 64, >= 64, or 0 = one model for the whole
+ *     batch (as the ensemble's group): a wavefront reads ONE model, at wave-uniform addresses, through the scalar cache.
+ *   Sensors.  sensed: a 9-bit mask, uniform over the batch, bit k = channel k of x9 is measured.  h_sigma[9]: HOST, the noise standard
+ *     deviation per channel, finite and >= 0 (0: a noise-free channel); it travels in the argument block.
+ *   Per step t of an aircraft that is not frozen, before the plant step, from the state at the start of the step, xm = the prediction
+ *     the xhat array holds:
+ *         1.  y_k = x9_k + (sigma_k * n_k)                                     sensed k; every operation rounded on its own
+ *         2.  e_k = y_k - xm_k;   xh_i = xm_i + sum_k Lf[i][k] e_k             over the sensed k in ascending order, one fma per term
+ *         3.  u[1+i] = lqr_action(K[i][4..6], dem - xh[4..6], u0[1+i])         f16_rollout_lqr's law on xh; the thrust command is held
+ *         4.  xm <- x9_trim + Ad (xh - x9_trim) + Bd (s - s_trim)              per entry: x9_trim_i, then the nine Ad terms, then the
+ *                                                                              three Bd terms, one fma per term
+ *         5.  the plant step of f16_rollout_lqr_wind
+ *     A frozen aircraft skips 1 - 5 and keeps xm.  The noise is counter-based: nothing "advances".
+ *   Noise.  Call j (0, 1, 2) of step t is Philox4x32-10 on the counter (mrow0 + t, j, 0xFFFFFFFE, aircraft), key = (meas_seed &
+ *     0xffffffff, meas_seed >> 32).  Gusts use 0xFFFFFFFF in word 2 and MPPI values below 256, so one seed may serve all three.
+ *     U_i = (r_i + 0.5) 2^-32 as in the gust sampler; all four Box-Muller outputs are used, (ra c1, ra s1, rb c3, rb s3) with
+ *     ra = sqrt(-2 log U0), rb = sqrt(-2 log U2), (c1, s1) = cos, sin(2 pi U1), (c3, s3) = cos, sin(2 pi U3), for channels
+ *     4 j .. 4 j + 3.  A call whose channels are all unsensed is not made.
+ *   f16_kalman_batch: the steady-state filter of M models.  Ad[81][ld]; w[9][ld] the diagonal process-noise variances per step;
+ *     v[9][ld] the measurement variances, > 0 on sensed channels and ignored elsewhere (all DEVICE).  The prediction covariance P
+ *     solves P = Ad P Ad' - Ad P C'(C P C' + V)^-1 C P Ad' + W by the doubling f16_lqr_batch runs (A <- Ad', G <- C'V^-1 C, H <- W),
+ *     one wavefront per model on the fp64 matrix cores; Lf = P (I + G P)^-1 C'V^-1 (= P C'(C P C' + V)^-1), in the 9 x 9 frame, the
+ *     columns of unsensed channels exactly zero.  Lf[81][ld] row-major; Pm[81][ld] (P) and iters[M] may be NULL.  status[M] is OR-ed
+ *     into: F16_ST_QP_MAXITER when 60 doublings do not converge or the solution is not finite (f16_lqr_batch's convention).
+ *     F16_EINVAL: a NULL pointer among the required ones, M < 0, ld < M, sensed outside 1 .. 0x1ff.  M == 0 is a no-op.
+ *   f16_observer_step: steps 1 - 4 for a batch, through the SAME out-of-line device function the rollout kernels call under
+ *     F16_FLAG_ONE_LANE (the default kernels inline the rule, as they inline the plant step; every product of steps 2 and 4 is one
+ *     fma and step 1 is rounded operation by operation whoever compiles it).  x[18][ld],
+ *     u0[4][ld], K[27][ld], dem[3][ld]; status[B] (may be NULL) is only read: an aircraft that carries F16_ST_ENVELOPE, or lies
+ *     outside the box of env.py:117-124 (unless F16_FLAG_NO_ENVELOPE), is skipped and nothing of it is written.  mrow: counter word 0.
+ *     xhat[9][ld] in / out: xm before and after.  y_out[9][ld] (may be NULL): the measurements, sensed channels only.  u_cmd[4][ld]:
+ *     the command of the step, u_cmd[0] = u0[0].
+ *   f16_rollout_lqg_wind / f16_rollout_lqg_wind_ens are f16_rollout_lqr_wind / f16_rollout_lqr_wind_ens under the rule: same
+ *     arguments, layouts, holds, envelope freeze, status bits, samples, u_out, no-op rules, both methods.  xhat in / out.  xhat_traj
+ *     [S][9][ld] (may be NULL): THE CONTENT OF xhat AT EVERY SAMPLE POINT, i.e. the prediction xm of the state stored in traj -- the
+ *     sample of the estimate is to xhat what the sample of the state is to x, for frozen aircraft and across split calls alike.
+ *     traj_every is read when traj or xhat_traj is given.  A NULL h_wind, or one whose pointers are all NULL, is zero air THROUGH THE
+ *     WIND KERNELS, as in the ensemble twin, not a forward.  Nothing is allocated: the calls can be captured into a graph.
+ *     F16_EINVAL: what the sibling refuses, in its order; then a NULL obs, h_sigma or xhat; mgroup < 0 or mgroup % 64 != 0; sensed
+ *     outside 1 .. 0x1ff; a sigma negative or not finite.  B == 0 or nsteps == 0 is a no-op.
+ *   Contracts.  Under F16_FLAG_ONE_LANE one call equals the chain of (f16_observer_step, one step of f16_rollout_wind with that
+ *     u_cmd) BIT FOR BIT; for every batch size, both methods and both flag settings n + m steps equal n steps then m steps with mrow0,
+ *     row0, xhat and gstate continued, where n is a multiple of hold and gust_hold.
+ *   Launch rules: those of the siblings (one lane per aircraft, 64 / 128 / 256 lanes, the exact kernel under F16_FLAG_ONE_LANE; never
+ *     the role-wave kernels).  xm lives in the xhat array between steps: a coalesced 72 B read and write per aircraft and step.
+ *   OUT OF SCOPE: observers in the MPC, MPPI, gain-scheduled and re-linearised loops; models not grouped by wavefront; a sensor
+ *     period other than one step; correlated or coloured sensor noise; time-varying filters; air-data sensors. */
+#define F16_OBS_DOUBLES 208
+int f16_kalman_batch(f16_ctx *ctx, const double *Ad, const double *w, const double *v, int sensed, double *Lf, double *Pm,
+                     int32_t *iters, int32_t *status, long M, long ld, void *stream);
+int f16_observer_step(f16_ctx *ctx, const double *x, const int32_t *status, const double *u0, const double *K, const double *dem,
+                      const double *obs, long mgroup, int sensed, const double *h_sigma, uint64_t meas_seed, uint32_t mrow,
+                      double *xhat, double *y_out, double *u_cmd, long B, long ld, unsigned flags, void *stream);
+int f16_rollout_lqg_wind(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, const f16_wind *h_wind,
+                         const double *obs, long mgroup, int sensed, const double *h_sigma, uint64_t meas_seed, uint32_t mrow0,
+                         double *xhat, double *traj, double *xhat_traj, double *u_out, int32_t *status, long B, long ld, int nsteps,
+                         int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream);
+int f16_rollout_lqg_wind_ens(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, const f16_wind *h_wind,
+                             const double *obs, long mgroup, int sensed, const double *h_sigma, uint64_t meas_seed, uint32_t mrow0,
+                             double *xhat, double *traj, double *xhat_traj, const f16_ens *h_ens, double *u_out, int32_t *status, long B,
+                             long ld, int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method,
+                             unsigned flags, void *stream);
 /* The reference's LINEAR-model closed loops as ONE launch (9-state reduced model, 3 inputs; one lane per aircraft, its matrices in
  * registers):   per step   u = -K (x_ref - x) + u0,   x = Ad x + Bd u
  *   test_env_mk2.py:46-62 `LQR(linear=True)` (what main.py:35 runs): the frozen model ssr.Ad / ssr.Bd under env.py:360-371
