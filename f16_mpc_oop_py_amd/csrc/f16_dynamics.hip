@@ -1068,10 +1068,9 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgsGS<SCHED, COST, GS> &a, voi
   const char *const what = COST ? "f16_rollout_cost launch" : "f16_rollout launch";
   if (a.flags & F16_FLAG_ONE_LANE) {
     // results independent of the batch size: ONE kernel for every B, its step an out-of-line function (k_rollout_exact)
-    const long blocks = (B + 63) / 64;
-    if constexpr (GS) hipLaunchKernelGGL((k_rollout_exact_gs<STAGES>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    if constexpr (GS) hipLaunchKernelGGL((k_rollout_exact_gs<STAGES>), one_lane_grid(B), dim3(64), 0, st, a);
     else
-    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST, STAGES>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((k_rollout_exact<LQR, SCHED, COST, STAGES>), one_lane_grid(B), dim3(64), 0, st, a);
     return hip_check(hipGetLastError(), what);
   }
   if constexpr (!COST && STAGES == 1 && !GS) {
@@ -1089,13 +1088,8 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgsGS<SCHED, COST, GS> &a, voi
       return hip_check(hipGetLastError(), what);
     }
   }
-  Geometry g = geometry(B, a.fi);
-  constexpr bool WIDE = STAGES == 1 || RK4_512;      // 512-lane workgroups
-  if (!WIDE && g.block == 512) {                     // the RK4 ceiling: 256 lanes, the grid that goes with them
-    g.block = 256;
-    const long blocks = (B + 255) / 256;
-    g.grid = (int)(blocks < 256 ? blocks : 256);
-  }
+  constexpr bool WIDE = STAGES == 1 || RK4_512;      // 512-lane workgroups; else the RK4 ceiling of 256 lanes
+  Geometry g = geometry(B, a.fi, WIDE ? 512 : 256);
 #ifdef F16_FAST_DIV
   // throughput regime, default numerics: lookups on the scaled-integer image
   static const int use_i32 = [] { const char *e = getenv("F16_ROLLOUT_I32"); return e ? atoi(e) : 1; }();

@@ -206,72 +206,49 @@ __global__ __launch_bounds__(64) void k_rollout_lqg_wind_exact(WindArgs a, ObsAr
   wind_lanes<64, true, STAGES, true, ENS, true>(a, a.tab, us, kq, ws, ework, &o);
 }
 
+// What an entry point states of the observer (WindRollout::obs; f16_observer_step: its own)
+struct ObsInputs {
+  const double *obs; long mgroup; int sensed; const double *h_sigma;      // (the entry points' order)
+  uint64_t meas_seed; uint32_t mrow0; double *xhat;
+};
+
 // the observer's rules, behind the sibling's: the pointers, the grouping, the sensors
-static int check_observer(const double *obs, const double *h_sigma, const double *xhat, long mgroup, int sensed) {
-  if (!obs || !h_sigma || !xhat) return set_error(F16_EINVAL, "obs / h_sigma / xhat is NULL");
-  if (mgroup < 0 || mgroup % 64 != 0) return set_error(F16_EINVAL, "mgroup must be 0 (one model) or a multiple of 64");
-  if (sensed < 1 || sensed > 0x1ff) return set_error(F16_EINVAL, "sensed must be a mask of the nine channels, 1 .. 0x1ff");
+static int check_observer(const ObsInputs &i) {
+  if (!i.obs || !i.h_sigma || !i.xhat) return set_error(F16_EINVAL, "obs / h_sigma / xhat is NULL");
+  if (i.mgroup < 0 || i.mgroup % 64 != 0) return set_error(F16_EINVAL, "mgroup must be 0 (one model) or a multiple of 64");
+  if (i.sensed < 1 || i.sensed > 0x1ff) return set_error(F16_EINVAL, "sensed must be a mask of the nine channels, 1 .. 0x1ff");
   for (int k = 0; k < 9; ++k)
-    if (!(h_sigma[k] >= 0.0) || !__builtin_isfinite(h_sigma[k])) return set_error(F16_EINVAL, "a sigma is negative or not finite");
+    if (!(i.h_sigma[k] >= 0.0) || !__builtin_isfinite(i.h_sigma[k])) return set_error(F16_EINVAL, "a sigma is negative or not finite");
   return F16_OK;
 }
 
-static ObsArgs observer_args(const double *obs, long mgroup, int sensed, const double *h_sigma, uint64_t seed, uint32_t mrow0, double *xhat,
-                             double *y_out, double *xhat_traj, long ld) {
+static ObsArgs observer_args(const ObsInputs &i, double *y_out, double *xhat_traj, long ld) {
   ObsArgs o{};
-  o.obs = obs; o.xhat = xhat; o.y_out = y_out; o.xhat_traj = xhat_traj;
-  o.mgroup = mgroup; o.ld = ld;
-  o.key0 = (uint32_t)(seed & 0xffffffffu); o.key1 = (uint32_t)(seed >> 32); o.mrow0 = mrow0;
-  o.sensed = sensed;
-  for (int k = 0; k < 9; ++k) o.sigma[k] = h_sigma[k];
+  o.obs = i.obs; o.xhat = i.xhat; o.y_out = y_out; o.xhat_traj = xhat_traj;
+  o.mgroup = i.mgroup; o.ld = ld;
+  o.key0 = (uint32_t)(i.meas_seed & 0xffffffffu); o.key1 = (uint32_t)(i.meas_seed >> 32); o.mrow0 = i.mrow0;
+  o.sensed = i.sensed;
+  for (int k = 0; k < 9; ++k) o.sigma[k] = i.h_sigma[k];
   return o;
 }
 
-// The launch rules are those of the siblings (f16_wind_lanes.hpp: wind_geometry; F16_FLAG_ONE_LANE -> the exact kernel).  e: the
-// f16_ens of the ensemble twin, or null.
-static int lqg_rollout(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, const f16_wind *w, const double *obs,
-                       long mgroup, int sensed, const double *h_sigma, uint64_t meas_seed, uint32_t mrow0, double *xhat, double *traj,
-                       double *xhat_traj, const f16_ens *e, bool ens, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
-                       int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream) {
-  if (!w) w = &STILL_AIR;      // zero air THROUGH the wind kernels
-  const double *sampled = traj ? traj : xhat_traj;
-  if (int rc = wind_check(ctx, true, "K / dem_seq is NULL", x, u0, K, dem_seq, w, sampled, B, ld, nsteps, hold, traj_every, method)) return rc;
-  if (ens) {
-    if (traj_every < 1 || nsteps % traj_every != 0)
-      return set_error(F16_EINVAL, "nsteps must be a multiple of traj_every >= 1: the sample period of the ensemble, with or without traj");
-    if (int rc = ens_rules(e, B)) return rc;
+// The kernel family of the output-feedback calls (f16_wind_lanes.hpp: wind_rollout): the kernels take the observer's block and the
+// ensemble's workspace (null without one) behind the argument block.
+template <bool E>
+struct LqgKernels {
+  static constexpr bool LQR = true, ENS = E, OBS = true;
+  static constexpr const char *what = "f16_rollout_lqg_wind launch", *what_finish = "f16_rollout_lqg_wind_ens finishing launch";
+  static int rules(const WindRollout &d) { return check_observer(*d.obs); }
+  static double *work(const WindRollout &d) { return E ? d.ens->work : nullptr; }
+  template <int BLOCK, int STAGES>
+  static void launch(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &d) {
+    hipLaunchKernelGGL((k_rollout_lqg_wind<BLOCK, STAGES, E>), grid, dim3(BLOCK), 0, st, a, observer_args(*d.obs, nullptr, d.xhat_traj, d.ld), work(d));
   }
-  if (int rc = check_observer(obs, h_sigma, xhat, mgroup, sensed)) return rc;
-  if (B == 0 || nsteps == 0) return F16_OK;
-  const WindArgs a = wind_args(ctx, true, x, u0, K, dem_seq, w, traj, u_out, status, B, ld, nsteps, hold,
-                               ens || sampled ? traj_every : nsteps + 1, dt, xcg, fi_flag, flags);
-  const ObsArgs o = observer_args(obs, mgroup, sensed, h_sigma, meas_seed, mrow0, xhat, nullptr, xhat_traj, ld);
-  double *work = ens ? e->work : nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  const bool rk4 = method == F16_INT_RK4;
-  auto launch = [&](auto ENS) {
-    constexpr bool E = decltype(ENS)::value;
-    if (flags & F16_FLAG_ONE_LANE) {
-      const long blocks = (B + 63) / 64;
-      const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
-      if (rk4) hipLaunchKernelGGL((k_rollout_lqg_wind_exact<4, E>), grid, dim3(64), 0, st, a, o, work);
-      else hipLaunchKernelGGL((k_rollout_lqg_wind_exact<1, E>), grid, dim3(64), 0, st, a, o, work);
-      return;
-    }
-    const Geometry g = wind_geometry(B, fi_flag);
-    by_block(g, [&](auto block) {
-      constexpr int BLOCK = decltype(block)::value;
-      if constexpr (BLOCK <= 256) {
-        if (rk4) hipLaunchKernelGGL((k_rollout_lqg_wind<BLOCK, 4, E>), dim3(g.grid), dim3(BLOCK), 0, st, a, o, work);
-        else hipLaunchKernelGGL((k_rollout_lqg_wind<BLOCK, 1, E>), dim3(g.grid), dim3(BLOCK), 0, st, a, o, work);
-      }
-    });
-  };
-  if (ens) launch(std::true_type{});
-  else launch(std::false_type{});
-  if (int rc = hip_check(hipGetLastError(), "f16_rollout_lqg_wind launch")) return rc;
-  return ens ? ens_finish_launch(e, B, nsteps / traj_every, flags, stream, "f16_rollout_lqg_wind_ens finishing launch") : F16_OK;
-}
+  template <int STAGES>
+  static void launch_exact(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &d) {
+    hipLaunchKernelGGL((k_rollout_lqg_wind_exact<STAGES, E>), grid, dim3(64), 0, st, a, observer_args(*d.obs, nullptr, d.xhat_traj, d.ld), work(d));
+  }
+};
 
 }  // namespace f16
 
@@ -293,12 +270,11 @@ extern "C" int f16_observer_step(f16_ctx *ctx, const double *x, const int32_t *s
                                  double *xhat, double *y_out, double *u_cmd, long B, long ld, unsigned flags, void *stream) {
   if (int rc = check_common(ctx, x, u0, B, ld)) return rc;
   if (!K || !dem || !u_cmd) return set_error(F16_EINVAL, "K / dem / u_cmd is NULL");
-  if (int rc = check_observer(obs, h_sigma, xhat, mgroup, sensed)) return rc;
+  const ObsInputs in{obs, mgroup, sensed, h_sigma, meas_seed, mrow, xhat};
+  if (int rc = check_observer(in)) return rc;
   if (B == 0) return F16_OK;
   ObsStepArgs a{x, u0, K, dem, status, u_cmd, B, ld, flags};
-  const ObsArgs o = observer_args(obs, mgroup, sensed, h_sigma, meas_seed, mrow, xhat, y_out, nullptr, ld);
-  const long blocks = (B + 63) / 64;
-  hipLaunchKernelGGL(k_observer_step, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, (hipStream_t)stream, a, o);
+  hipLaunchKernelGGL(k_observer_step, one_lane_grid(B), dim3(64), 0, (hipStream_t)stream, a, observer_args(in, y_out, nullptr, ld));
   return hip_check(hipGetLastError(), "f16_observer_step launch");
 }
 
@@ -307,8 +283,10 @@ extern "C" int f16_rollout_lqg_wind(f16_ctx *ctx, double *x, const double *u0, c
                                     double *xhat, double *traj, double *xhat_traj, double *u_out, int32_t *status, long B, long ld,
                                     int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags,
                                     void *stream) {
-  return lqg_rollout(ctx, x, u0, K, dem_seq, h_wind, obs, mgroup, sensed, h_sigma, meas_seed, mrow0, xhat, traj, xhat_traj, nullptr, false,
-                     u_out, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags, stream);
+  const ObsInputs in{obs, mgroup, sensed, h_sigma, meas_seed, mrow0, xhat};
+  WindRollout d{"K / dem_seq is NULL", x, u0, dem_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  d.K = K; d.u_out = u_out; d.obs = &in; d.xhat_traj = xhat_traj;
+  return wind_rollout<LqgKernels<false>>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqg_wind_ens(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq,
@@ -316,6 +294,8 @@ extern "C" int f16_rollout_lqg_wind_ens(f16_ctx *ctx, double *x, const double *u
                                         uint64_t meas_seed, uint32_t mrow0, double *xhat, double *traj, double *xhat_traj,
                                         const f16_ens *h_ens, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
                                         int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream) {
-  return lqg_rollout(ctx, x, u0, K, dem_seq, h_wind, obs, mgroup, sensed, h_sigma, meas_seed, mrow0, xhat, traj, xhat_traj, h_ens, true, u_out,
-                     status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags, stream);
+  const ObsInputs in{obs, mgroup, sensed, h_sigma, meas_seed, mrow0, xhat};
+  WindRollout d{"K / dem_seq is NULL", x, u0, dem_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  d.K = K; d.u_out = u_out; d.ens = h_ens; d.obs = &in; d.xhat_traj = xhat_traj;
+  return wind_rollout<LqgKernels<true>>(ctx, d, stream);
 }

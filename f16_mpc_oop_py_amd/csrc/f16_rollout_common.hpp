@@ -109,8 +109,9 @@ __device__ __forceinline__ void stage_tables(double *lds, const double *__restri
 // waves share a SIMD: fill all 256 CUs first (64 / 128 / 256 lanes), then two waves per SIMD (512 lanes) from 131,072
 // aircraft on -- the phased lookups (aero_totals_phased) keep a hifi step inside 256 registers there; measured with
 // every step stored: 15.8 (256 lanes) vs 17.1 (512) G steps/s at B = 262,144, 17.9 vs 21.5 at B = 1,048,576.
+// max_block: a ceiling on the workgroup size, with the grid that goes with it (256: the Runge-Kutta rollouts and the wind family)
 struct Geometry { int block, grid; };
-static Geometry geometry(long B, int fi) {
+static Geometry geometry(long B, int fi, int max_block = 512) {
   Geometry g;
   (void)fi;
   if (B <= 64L * 256) g.block = 64;          // <= 256 one-wave workgroups: one per CU
@@ -119,9 +120,16 @@ static Geometry geometry(long B, int fi) {
   else g.block = 512;                        // two waves per SIMD
   static const int force = [] { const char *e = getenv("F16_DYN_BLOCK"); return e ? atoi(e) : 0; }();   // tuning knob
   if (force == 64 || force == 128 || force == 256 || force == 512) g.block = force;
+  if (g.block > max_block) g.block = max_block;
   long blocks = (B + g.block - 1) / g.block;
   g.grid = (int)(blocks < 256 ? blocks : 256);
   return g;
+}
+
+// F16_FLAG_ONE_LANE, and the helper kernels of one lane per aircraft: 64-lane workgroups in a grid-stride loop, at most 4096 of them
+static dim3 one_lane_grid(long B) {
+  const long blocks = (B + 63) / 64;
+  return dim3((unsigned)(blocks < 4096 ? blocks : 4096));
 }
 
 // Geometry::block as a compile-time constant: f(std::integral_constant<int, BLOCK>) for the workgroup size of g

@@ -94,35 +94,20 @@ __global__ __launch_bounds__(64) void k_gust_sample(GustArgs a) {
 
 static bool still_air(const f16_wind *w) { return !w || (!w->wind_ned && !w->gust_seq && !w->ga && !w->gb && !w->gstate); }
 
-// The launch rules of the wind rollouts (f16_wind_lanes.hpp: wind_check, wind_args, wind_geometry): F16_FLAG_ONE_LANE ->
-// k_rollout_wind_exact; else k_rollout_wind at 64 / 128 / 256 lanes.
-template <bool LQR>
-static int wind_rollout(f16_ctx *ctx, const char *missing, double *x, const double *u, const double *K, const double *seq, const f16_wind *w,
-                        double *traj, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
-                        double xcg, int fi_flag, int method, unsigned flags, void *stream) {
-  if (int rc = wind_check(ctx, LQR, missing, x, u, K, seq, w, traj, B, ld, nsteps, hold, traj_every, method)) return rc;
-  if (B == 0 || nsteps == 0) return F16_OK;
-  const WindArgs a = wind_args(ctx, LQR, x, u, K, seq, w, traj, u_out, status, B, ld, nsteps, hold, traj ? traj_every : nsteps + 1, dt, xcg,
-                               fi_flag, flags);
-  const hipStream_t st = (hipStream_t)stream;
-  const bool rk4 = method == F16_INT_RK4;
-  if (flags & F16_FLAG_ONE_LANE) {
-    const long blocks = (B + 63) / 64;
-    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
-    if (rk4) hipLaunchKernelGGL((k_rollout_wind_exact<LQR, 4>), grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_rollout_wind_exact<LQR, 1>), grid, dim3(64), 0, st, a);
-    return hip_check(hipGetLastError(), "f16_rollout_wind launch");
+// The kernel family of the plain calls (f16_wind_lanes.hpp: wind_rollout): the kernels take the argument block alone.
+template <bool L>
+struct WindKernels {
+  static constexpr bool LQR = L, ENS = false, OBS = false;
+  static constexpr const char *what = "f16_rollout_wind launch";
+  template <int BLOCK, int STAGES>
+  static void launch(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &) {
+    hipLaunchKernelGGL((k_rollout_wind<BLOCK, L, STAGES>), grid, dim3(BLOCK), 0, st, a);
   }
-  const Geometry g = wind_geometry(B, fi_flag);
-  by_block(g, [&](auto block) {
-    constexpr int BLOCK = decltype(block)::value;
-    if constexpr (BLOCK <= 256) {
-      if (rk4) hipLaunchKernelGGL((k_rollout_wind<BLOCK, LQR, 4>), dim3(g.grid), dim3(BLOCK), 0, st, a);
-      else hipLaunchKernelGGL((k_rollout_wind<BLOCK, LQR, 1>), dim3(g.grid), dim3(BLOCK), 0, st, a);
-    }
-  });
-  return hip_check(hipGetLastError(), "f16_rollout_wind launch");
-}
+  template <int STAGES>
+  static void launch_exact(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &) {
+    hipLaunchKernelGGL((k_rollout_wind_exact<L, STAGES>), grid, dim3(64), 0, st, a);
+  }
+};
 
 }  // namespace f16
 
@@ -136,12 +121,7 @@ extern "C" int f16_xdot_wind_batch(f16_ctx *ctx, const double *x, const double *
   if (B == 0) return F16_OK;
   XdotWindArgs a = base_args<XdotWindArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
   a.x = x; a.u = u; a.out = xdot; a.wind = wind; a.gust = gust;
-  Geometry g = geometry(B, fi_flag);
-  if (g.block == 512) {
-    g.block = 256;
-    const long blocks = (B + 255) / 256;
-    g.grid = (int)(blocks < 256 ? blocks : 256);
-  }
+  const Geometry g = geometry(B, fi_flag, 256);
   by_block(g, [&](auto block) {
     constexpr int BLOCK = decltype(block)::value;
     if constexpr (BLOCK <= 256) hipLaunchKernelGGL((k_xdot_wind<BLOCK>), dim3(g.grid), dim3(BLOCK), 0, (hipStream_t)stream, a);
@@ -153,8 +133,8 @@ extern "C" int f16_rollout_wind(f16_ctx *ctx, double *x, const double *u_seq, co
                                 long ld, int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method,
                                 unsigned flags, void *stream) {
   if (still_air(h_wind)) return f16_rollout_rk(ctx, x, u_seq, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags, stream);
-  return wind_rollout<false>(ctx, "u_seq is NULL", x, u_seq, nullptr, u_seq, h_wind, traj, nullptr, status, B, ld, nsteps, hold, traj_every,
-                             dt, xcg, fi_flag, method, flags, stream);
+  WindRollout d{"u_seq is NULL", x, u_seq, u_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  return wind_rollout<WindKernels<false>>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr_wind(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq, const f16_wind *h_wind,
@@ -162,8 +142,9 @@ extern "C" int f16_rollout_lqr_wind(f16_ctx *ctx, double *x, const double *u0, c
                                     double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream) {
   if (still_air(h_wind))
     return f16_rollout_lqr_rk(ctx, x, u0, K, dem_seq, traj, u_out, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags, stream);
-  return wind_rollout<true>(ctx, "K / dem_seq is NULL", x, u0, K, dem_seq, h_wind, traj, u_out, status, B, ld, nsteps, hold, traj_every, dt,
-                            xcg, fi_flag, method, flags, stream);
+  WindRollout d{"K / dem_seq is NULL", x, u0, dem_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  d.K = K; d.u_out = u_out;
+  return wind_rollout<WindKernels<true>>(ctx, d, stream);
 }
 
 extern "C" int f16_gust_coeffs_host(const double *sigma, const double *length, double v0, double dt_row, double *a_out, double *b_out) {
@@ -190,7 +171,6 @@ extern "C" int f16_gust_sample(f16_ctx *ctx, const double *ga, const double *gb,
   a.ga = ga; a.gb = gb; a.gstate = gstate; a.gseq = g_seq;
   a.key0 = (uint32_t)(seed & 0xffffffffu); a.key1 = (uint32_t)(seed >> 32); a.row0 = row0;
   a.B = B; a.ld = ld; a.nrows = nrows;
-  const long blocks = (B + 63) / 64;
-  hipLaunchKernelGGL(k_gust_sample, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_gust_sample, one_lane_grid(B), dim3(64), 0, (hipStream_t)stream, a);
   return hip_check(hipGetLastError(), "f16_gust_sample launch");
 }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(64) void k_ens_finish(EnsArgs a) {
 }
 
 // the rules of an f16_ens behind the sibling's: every member, the group size, the leading dimension of the results
-static int check_ens(const f16_ens *e, long B) {
+int ens_rules(const f16_ens *e, long B) {
   if (!e || !e->work || !e->count || !e->mean || !e->m2 || !e->min || !e->max)
     return set_error(F16_EINVAL, "h_ens or one of its members is NULL");
   if (e->group < 64 || e->group % 64 != 0) return set_error(F16_EINVAL, "group must be a multiple of 64 and >= 64");
@@ -92,48 +92,27 @@ static EnsArgs ens_args(const f16_ens *e, long B, int S, unsigned flags) {
   return a;
 }
 
-static int ens_finish(const EnsArgs &a, hipStream_t st, const char *what) {
+int ens_finish_launch(const f16_ens *e, long B, int S, unsigned flags, void *stream, const char *what) {
+  const EnsArgs a = ens_args(e, B, S, flags);
   const long blocks = ((long)a.S * 18 * a.G + 63) / 64;
-  hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(64), 0, (hipStream_t)stream, a);
   return hip_check(hipGetLastError(), what);
 }
 
-int ens_rules(const f16_ens *e, long B) { return check_ens(e, B); }
-int ens_finish_launch(const f16_ens *e, long B, int S, unsigned flags, void *stream, const char *what) {
-  return ens_finish(ens_args(e, B, S, flags), (hipStream_t)stream, what);
-}
-
-template <bool LQR>
-static int wind_rollout_ens(f16_ctx *ctx, const char *missing, double *x, const double *u, const double *K, const double *seq, const f16_wind *w,
-                            double *traj, const f16_ens *e, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold,
-                            int traj_every, double dt, double xcg, int fi_flag, int method, unsigned flags, void *stream) {
-  if (!w) w = &STILL_AIR;      // zero air THROUGH the wind kernels
-  if (int rc = wind_check(ctx, LQR, missing, x, u, K, seq, w, traj, B, ld, nsteps, hold, traj_every, method)) return rc;
-  if (traj_every < 1 || nsteps % traj_every != 0)
-    return set_error(F16_EINVAL, "nsteps must be a multiple of traj_every >= 1: the sample period of the ensemble, with or without traj");
-  if (int rc = check_ens(e, B)) return rc;
-  if (B == 0 || nsteps == 0) return F16_OK;
-  const WindArgs a = wind_args(ctx, LQR, x, u, K, seq, w, traj, u_out, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, flags);
-  const hipStream_t st = (hipStream_t)stream;
-  const bool rk4 = method == F16_INT_RK4;
-  if (flags & F16_FLAG_ONE_LANE) {
-    const long blocks = (B + 63) / 64;
-    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
-    if (rk4) hipLaunchKernelGGL((k_rollout_wind_exact_ens<LQR, 4>), grid, dim3(64), 0, st, a, e->work);
-    else hipLaunchKernelGGL((k_rollout_wind_exact_ens<LQR, 1>), grid, dim3(64), 0, st, a, e->work);
-  } else {
-    const Geometry g = wind_geometry(B, fi_flag);
-    by_block(g, [&](auto block) {
-      constexpr int BLOCK = decltype(block)::value;
-      if constexpr (BLOCK <= 256) {
-        if (rk4) hipLaunchKernelGGL((k_rollout_wind_ens<BLOCK, LQR, 4>), dim3(g.grid), dim3(BLOCK), 0, st, a, e->work);
-        else hipLaunchKernelGGL((k_rollout_wind_ens<BLOCK, LQR, 1>), dim3(g.grid), dim3(BLOCK), 0, st, a, e->work);
-      }
-    });
+// The kernel family of the ensemble calls (f16_wind_lanes.hpp: wind_rollout): the kernels take the workspace behind the argument block.
+template <bool L>
+struct WindEnsKernels {
+  static constexpr bool LQR = L, ENS = true, OBS = false;
+  static constexpr const char *what = "f16_rollout_wind_ens launch", *what_finish = "f16_rollout_wind_ens finishing launch";
+  template <int BLOCK, int STAGES>
+  static void launch(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &d) {
+    hipLaunchKernelGGL((k_rollout_wind_ens<BLOCK, L, STAGES>), grid, dim3(BLOCK), 0, st, a, d.ens->work);
   }
-  if (int rc = hip_check(hipGetLastError(), "f16_rollout_wind_ens launch")) return rc;
-  return ens_finish(ens_args(e, B, nsteps / traj_every, flags), st, "f16_rollout_wind_ens finishing launch");
-}
+  template <int STAGES>
+  static void launch_exact(dim3 grid, hipStream_t st, const WindArgs &a, const WindRollout &d) {
+    hipLaunchKernelGGL((k_rollout_wind_exact_ens<L, STAGES>), grid, dim3(64), 0, st, a, d.ens->work);
+  }
+};
 
 }  // namespace f16
 
@@ -147,28 +126,30 @@ extern "C" long f16_ens_work_doubles(long B, int nsamples) {
 extern "C" int f16_rollout_wind_ens(f16_ctx *ctx, double *x, const double *u_seq, const f16_wind *h_wind, double *traj, const f16_ens *h_ens,
                                     int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt, double xcg,
                                     int fi_flag, int method, unsigned flags, void *stream) {
-  return wind_rollout_ens<false>(ctx, "u_seq is NULL", x, u_seq, nullptr, u_seq, h_wind, traj, h_ens, nullptr, status, B, ld, nsteps, hold,
-                                 traj_every, dt, xcg, fi_flag, method, flags, stream);
+  WindRollout d{"u_seq is NULL", x, u_seq, u_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  d.ens = h_ens;
+  return wind_rollout<WindEnsKernels<false>>(ctx, d, stream);
 }
 
 extern "C" int f16_rollout_lqr_wind_ens(f16_ctx *ctx, double *x, const double *u0, const double *K, const double *dem_seq,
                                         const f16_wind *h_wind, double *traj, const f16_ens *h_ens, double *u_out, int32_t *status, long B,
                                         long ld, int nsteps, int hold, int traj_every, double dt, double xcg, int fi_flag, int method,
                                         unsigned flags, void *stream) {
-  return wind_rollout_ens<true>(ctx, "K / dem_seq is NULL", x, u0, K, dem_seq, h_wind, traj, h_ens, u_out, status, B, ld, nsteps, hold,
-                                traj_every, dt, xcg, fi_flag, method, flags, stream);
+  WindRollout d{"K / dem_seq is NULL", x, u0, dem_seq, h_wind, traj, status, B, ld, nsteps, hold, traj_every, dt, xcg, fi_flag, method, flags};
+  d.K = K; d.u_out = u_out; d.ens = h_ens;
+  return wind_rollout<WindEnsKernels<true>>(ctx, d, stream);
 }
 
 extern "C" int f16_ens_from_traj(f16_ctx *ctx, const double *traj, int nsamples, long B, long ld, unsigned flags, const f16_ens *h_ens,
                                  void *stream) {
   if (!ctx || !traj || B < 0 || ld < B || nsamples < 0)
     return set_error(F16_EINVAL, "bad argument (NULL pointer, B < 0, ld < B or nsamples < 0)");
-  if (int rc = check_ens(h_ens, B)) return rc;
+  if (int rc = ens_rules(h_ens, B)) return rc;
   if (B == 0 || nsamples == 0) return F16_OK;
   EnsArgs a = ens_args(h_ens, B, nsamples, flags);
   a.traj = traj; a.ld = ld;
   const long items = (long)a.S * a.W;
   hipLaunchKernelGGL(k_ens_from_traj, dim3((unsigned)(items < 65536 ? items : 65536)), dim3(64), 0, (hipStream_t)stream, a);
   if (int rc = hip_check(hipGetLastError(), "f16_ens_from_traj launch")) return rc;
-  return ens_finish(a, (hipStream_t)stream, "f16_ens_from_traj finishing launch");
+  return ens_finish_launch(h_ens, B, nsamples, flags, stream, "f16_ens_from_traj finishing launch");
 }

@@ -1,6 +1,6 @@
 // f16_wind_lanes.hpp -- what the wind rollout kernels of f16_wind.hip, their ensemble twins of f16_wind_ens.hip and the
 // output-feedback twins of f16_observer.hip share, stated once: the argument block, the lane loop (wind_lanes) and, on the host, the
-// argument rules and the filling of the block.
+// one way from an entry point to the launch (WindRollout, wind_rollout).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -207,49 +207,85 @@ __device__ __forceinline__ void wind_lanes(const WindArgs &a, const double *T, d
   }
 }
 
-// ---- host: the argument rules and the argument block of the wind rollouts, for f16_wind.hip and f16_wind_ens.hip alike
+// ---- host: one rollout in moving air as its entry point states it, and the one way from there to the launch
 static const f16_wind STILL_AIR = {};
+struct ObsInputs;                      // f16_observer.hip
 
-// the sibling's checks in the sibling's order (f16_dynamics.hip: plant_rollout), then the wind fields
-static int wind_check(f16_ctx *ctx, bool lqr, const char *missing, const double *x, const double *u, const double *K, const double *seq,
-                      const f16_wind *w, const double *traj, long B, long ld, int nsteps, int hold, int traj_every, int method) {
-  if (!seq || (lqr && !K)) return set_error(F16_EINVAL, missing);
-  if (int rc = check_rollout(ctx, x, u, traj, B, ld, nsteps, traj_every)) return rc;
-  if (hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
-  if (method != F16_INT_EULER && method != F16_INT_RK4) return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
+// The six f16_rollout*_wind* calls differ in these values and in the kernel family F they hand to wind_rollout.
+struct WindRollout {
+  const char *missing;                 // the message for a NULL among the pointers the variant needs beyond x and u
+  double *x;                           // [18][ld], stepped in place
+  const double *u;                     // [4][ld]: row 0 of u_seq; u0 under the LQR law
+  const double *seq;                   // u_seq [nrows][4][ld]; under the LQR law dem_seq [nrows][3][ld]
+  const f16_wind *w;                   // null: zero air THROUGH the wind kernels (the plain calls forward still air before they come here)
+  double *traj;
+  int32_t *status;
+  long B, ld;
+  int nsteps, hold, traj_every;
+  double dt, xcg;
+  int fi, method;
+  unsigned flags;
+  // what an entry point leaves alone is the value of the simplest call, f16_rollout_wind:
+  const double *K = nullptr;           // LQR: the gain
+  double *u_out = nullptr;             // LQR: the last action, may be null
+  const f16_ens *ens = nullptr;        // F::ENS: the results and the workspace
+  const ObsInputs *obs = nullptr;      // F::OBS: the observer's inputs
+  double *xhat_traj = nullptr;         // F::OBS: the estimate at every sample point, with or without traj
+};
+
+// A kernel family F is what a translation unit hands over of its kernels: the lane loop's variant (LQR, ENS, OBS), the texts of a
+// failed launch (what; ENS: what_finish), with OBS the observer's rules (rules(d), checked last), and launch<BLOCK, STAGES>(grid, st, a, d) /
+// launch_exact<STAGES>(grid, st, a, d): its BLOCK-lane and its 64-lane F16_FLAG_ONE_LANE kernel with the family's extra arguments.
+// The rest is here.  The rules come in the sibling's order (f16_dynamics.hip: plant_rollout), then the wind fields, the ensemble's,
+// the family's.  The step rule looks at whichever sample array is given; the kernel counts a sample period the step counter never
+// reaches when nothing is sampled.  Geometry: one lane per aircraft under the 256-lane ceiling -- never a role-wave kernel.
+template <typename F>
+static int wind_rollout(f16_ctx *ctx, const WindRollout &d, void *stream) {
+  const f16_wind *w = d.w ? d.w : &STILL_AIR;
+  const double *sampled = d.traj ? d.traj : d.xhat_traj;
+  if (!d.seq || (F::LQR && !d.K)) return set_error(F16_EINVAL, d.missing);
+  if (int rc = check_rollout(ctx, d.x, d.u, sampled, d.B, d.ld, d.nsteps, d.traj_every)) return rc;
+  if (d.hold < 1) return set_error(F16_EINVAL, "hold must be >= 1");
+  if (d.method != F16_INT_EULER && d.method != F16_INT_RK4) return set_error(F16_EINVAL, "method must be F16_INT_EULER (1) or F16_INT_RK4 (4)");
   if (w->gust_seq && w->ga) return set_error(F16_EINVAL, "gust_seq and ga are both given: the gust rows are either read or generated");
   if ((w->ga != nullptr) != (w->gb != nullptr) || (w->ga != nullptr) != (w->gstate != nullptr))
     return set_error(F16_EINVAL, "ga, gb and gstate go together");
-  if ((w->gust_seq || w->ga) && w->gust_hold < 1) return set_error(F16_EINVAL, "gust_hold must be >= 1");
+  const bool gusts = w->gust_seq || w->ga;
+  if (gusts && w->gust_hold < 1) return set_error(F16_EINVAL, "gust_hold must be >= 1");
+  if constexpr (F::ENS) {
+    if (d.traj_every < 1 || d.nsteps % d.traj_every != 0)
+      return set_error(F16_EINVAL, "nsteps must be a multiple of traj_every >= 1: the sample period of the ensemble, with or without traj");
+    if (int rc = ens_rules(d.ens, d.B)) return rc;
+  }
+  if constexpr (F::OBS) if (int rc = F::rules(d)) return rc;
+  if (d.B == 0 || d.nsteps == 0) return F16_OK;
+  WindArgs a = base_args<WindArgs>(ctx, d.B, d.ld, d.xcg, d.fi, d.flags, d.status);
+  a.u = d.u; a.out = d.x; a.traj = d.traj;
+  a.nsteps = d.nsteps; a.traj_every = F::ENS || sampled ? d.traj_every : d.nsteps + 1; a.dt = d.dt;
+  a.K = d.K; a.dem = F::LQR ? d.seq : nullptr; a.u_out = d.u_out;
+  a.seq = d.seq; a.hold = d.hold; a.nrows = (d.nsteps - 1) / d.hold + 1;
+  a.wind = w->wind_ned; a.gseq = w->gust_seq; a.ga = w->ga; a.gb = w->gb; a.gstate = w->gstate;
+  a.ghold = gusts ? w->gust_hold : d.nsteps; a.grows = (d.nsteps - 1) / a.ghold + 1;
+  a.key0 = (uint32_t)(w->seed & 0xffffffffu); a.key1 = (uint32_t)(w->seed >> 32); a.row0 = w->row0;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool rk4 = d.method == F16_INT_RK4;
+  if (d.flags & F16_FLAG_ONE_LANE) {
+    if (rk4) F::template launch_exact<4>(one_lane_grid(d.B), st, a, d);
+    else F::template launch_exact<1>(one_lane_grid(d.B), st, a, d);
+  } else {
+    const Geometry g = geometry(d.B, d.fi, 256);
+    by_block(g, [&](auto block) {
+      constexpr int BLOCK = decltype(block)::value;
+      if constexpr (BLOCK <= 256) {
+        if (rk4) F::template launch<BLOCK, 4>(dim3(g.grid), st, a, d);
+        else F::template launch<BLOCK, 1>(dim3(g.grid), st, a, d);
+      }
+    });
+  }
+  if (int rc = hip_check(hipGetLastError(), F::what)) return rc;
+  if constexpr (F::ENS) return ens_finish_launch(d.ens, d.B, d.nsteps / d.traj_every, d.flags, stream, F::what_finish);
   return F16_OK;
 }
 
-// traj_every: the sample period as the kernel counts it (without samples: a period the step counter never reaches)
-static WindArgs wind_args(f16_ctx *ctx, bool lqr, double *x, const double *u, const double *K, const double *seq, const f16_wind *w,
-                          double *traj, double *u_out, int32_t *status, long B, long ld, int nsteps, int hold, int traj_every, double dt,
-                          double xcg, int fi_flag, unsigned flags) {
-  WindArgs a = base_args<WindArgs>(ctx, B, ld, xcg, fi_flag, flags, status);
-  a.u = u; a.out = x; a.traj = traj;
-  a.nsteps = nsteps; a.traj_every = traj_every; a.dt = dt;
-  a.K = K; a.dem = lqr ? seq : nullptr; a.u_out = u_out;
-  a.seq = seq; a.hold = hold; a.nrows = (nsteps - 1) / hold + 1;
-  const bool gusts = w->gust_seq || w->ga;
-  a.wind = w->wind_ned; a.gseq = w->gust_seq; a.ga = w->ga; a.gb = w->gb; a.gstate = w->gstate;
-  a.ghold = gusts ? w->gust_hold : nsteps; a.grows = (nsteps - 1) / a.ghold + 1;
-  a.key0 = (uint32_t)(w->seed & 0xffffffffu); a.key1 = (uint32_t)(w->seed >> 32); a.row0 = w->row0;
-  return a;
-}
-
-// The launch rules of the wind rollouts: the geometry of the one-lane-per-aircraft kernels with the 256-lane ceiling of the
-// Runge-Kutta rollouts -- never a role-wave kernel, never 512 lanes.  (F16_FLAG_ONE_LANE: 64-lane workgroups, at most 4096.)
-static Geometry wind_geometry(long B, int fi_flag) {
-  Geometry g = geometry(B, fi_flag);
-  if (g.block == 512) {
-    g.block = 256;
-    const long blocks = (B + 255) / 256;
-    g.grid = (int)(blocks < 256 ? blocks : 256);
-  }
-  return g;
-}
-
 }  // namespace f16
+

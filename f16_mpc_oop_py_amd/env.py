@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import cabi as _cabi
 from . import lib as _lib
 from . import parameters as P
 
@@ -274,80 +275,61 @@ class F16Batch:
 
     def _rollout_call(self, u, nsteps, traj_every, hold=None, K=None, dem=None, method=_lib.F16_INT_EULER, air=None, ensemble=None,
                       keep_traj=False, observer=None):
-        """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffer and the ONE call
+        """rollout, rollout_schedule and the nonlinear rollout_LQR behind their argument checks: the sample buffers and the ONE call
         into the library.  u [4,B], or with hold (steps per row) the schedule u_seq [S,4,B]; K [27,B] with dem [3,B]: the LQR law
         around the offset u, dem with hold the schedule dem_seq [S,3,B] -- its last action lands in u.values.  method F16_INT_RK4:
-        the _rk entry points, which are scheduled ones -- a constant input is one row held for every step.  ensemble (aircraft per
-        group, or True): the _wind_ens entry points, which return the statistics of the samples (an ensemble.Ensemble; with
-        keep_traj the samples too); with ensemble=None the call is the one it was.  observer = (observer.Observer, meas_seed,
-        return_estimate) with K: the _lqg_wind entry points (_observed_call)."""
+        the _rk entry points, which are scheduled ones -- a constant input is one row held for every step.  air (_air): the _wind
+        entry points.  ensemble (aircraft per group, or True): the _wind_ens ones, which return the statistics of the samples (an
+        ensemble.Ensemble; with keep_traj the samples too; no air = zero air).  observer = (observer.Observer, meas_seed,
+        return_estimate) with K: the _lqg_wind ones, the samples of the estimate [S, 9, B] appended when asked for.  The values are
+        gathered once under the header's parameter names and passed in its order (cabi.functions())."""
         if ensemble is None and keep_traj:
             raise ValueError("keep_traj goes with ensemble=")
-        if observer is not None:
-            return self._observed_call(u, nsteps, traj_every, hold, K, dem, method, air, ensemble, keep_traj, *observer)
-        every = int(traj_every or 1) if ensemble is not None else traj_every      # with ensemble= the sample period: every step by default
-        traj = self._samples(nsteps, every) if ensemble is None or keep_traj else None
-        # the four parameter lists of include/f16_hip.h are this one list; the LQR law adds three pointers, a schedule one integer
-        name, law, u_out = ("f16_rollout", (), ()) if K is None else ("f16_rollout_lqr", (_vp(K), _vp(dem)), (_vp(self._u),))
-        if ensemble is not None:  # the _wind_ens entry points: the _wind list with the f16_ens behind traj; no air = zero air through them
-            if every < 1 or int(nsteps) % every:
-                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every}), the sample period of the ensemble")
-            e, keep, result = self._ensemble_buffers(ensemble, int(nsteps) // every)
-            self._check(getattr(self.lib, name + "_wind_ens")(self.ctx.handle, _vp(self._x), _vp(u), *law, None if air is None else ctypes.byref(air[0]),
-                                                              _vp(traj), ctypes.byref(e), *u_out, _vp(self.status), self.B, self.B, int(nsteps),
-                                                              max(int(nsteps), 1) if hold is None else hold, every, self.dt, self.xcg,
-                                                              self.fi_flag, int(method), self.flags, self._stream))
-            result._keep = keep      # (the workspace lives as long as the result: the launches may still be running)
-            if air is not None and air[2] is not None:
-                air[2].advance(nsteps)
-            return (traj, result) if keep_traj else result
-        if air is not None:      # (_air) the _wind entry points: the scheduled parameter list with the air behind the schedule
-            self._check(getattr(self.lib, name + "_wind")(self.ctx.handle, _vp(self._x), _vp(u), *law, ctypes.byref(air[0]), _vp(traj), *u_out,
-                                                          _vp(self.status), self.B, self.B, int(nsteps), max(int(nsteps), 1) if hold is None else hold,
-                                                          int(traj_every or 1), self.dt, self.xcg, self.fi_flag, int(method), self.flags, self._stream))
-            if air[2] is not None:
-                air[2].advance(nsteps)
-            return traj
-        rule = ()
-        if method != _lib.F16_INT_EULER:
-            name, held, rule = name + "_rk", (max(int(nsteps), 1) if hold is None else hold,), (int(method),)
-        else:
-            name, held = (name, ()) if hold is None else (name + "_sched", (hold,))
-        self._check(getattr(self.lib, name)(self.ctx.handle, _vp(self._x), _vp(u), *law, _vp(traj), *u_out, _vp(self.status), self.B,
-                                            self.B, int(nsteps), *held, int(traj_every or 1), self.dt, self.xcg, self.fi_flag, *rule,
-                                            self.flags, self._stream))
-        return traj
-
-    def _observed_call(self, u0, nsteps, traj_every, hold, K, dem, method, air, ensemble, keep_traj, obs, meas_seed, want_estimate):
-        """The nonlinear rollout_LQR on noisy sensors through an observer: ONE call of f16_rollout_lqg_wind (with ensemble=:
-        f16_rollout_lqg_wind_ens) -- the _lqr_wind list with the observer behind the air.  No air = zero air through the wind kernels.
-        Returns what the call without observer returns; with want_estimate the samples of the estimate [S, 9, B] appended."""
-        if not 0 <= int(meas_seed) < 2 ** 64:
+        obs, meas_seed, want_estimate = observer or (None, 0, False)
+        if obs is not None and not 0 <= int(meas_seed) < 2 ** 64:
             raise ValueError("meas_seed must fit 64 bits")
         nsteps = int(nsteps)
-        if ensemble is not None:
-            every = int(traj_every or 1)
-            if every < 1 or nsteps % every:
-                raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every}), the sample period of the ensemble")
-            traj = self._samples(nsteps, every) if keep_traj else None
-            est = self._samples(nsteps, every, rows=9) if want_estimate else None
+        name = "f16_rollout" if K is None else "f16_rollout_lqr"
+        if obs is not None:
+            name = "f16_rollout_lqg_wind" + ("_ens" if ensemble is not None else "")
+        elif ensemble is not None or air is not None:
+            name += "_wind_ens" if ensemble is not None else "_wind"
+        elif method != _lib.F16_INT_EULER or hold is not None:
+            name += "_rk" if method != _lib.F16_INT_EULER else "_sched"
+        scheduled = name not in ("f16_rollout", "f16_rollout_lqr")
+        every = traj_every if ensemble is None else int(traj_every or 1)      # the sample period of the ensemble: every step by default
+        if ensemble is not None and (every < 1 or nsteps % every):
+            raise ValueError(f"nsteps ({nsteps}) must be a multiple of traj_every ({traj_every}), the sample period of the ensemble")
+        traj = self._samples(nsteps, every) if ensemble is None or keep_traj else None
+        est = self._samples(nsteps, every or 1, rows=9) if want_estimate else None
+        v = dict(ctx=self.ctx.handle, x=_vp(self._x), traj=_vp(traj), status=_vp(self.status), B=self.B, ld=self.B, nsteps=nsteps,
+                 traj_every=int(every or 1), dt=self.dt, xcg=self.xcg, fi_flag=self.fi_flag, flags=self.flags, stream=self._stream)
+        if K is None:
+            v["u_seq" if scheduled else "u"] = _vp(u)
         else:
-            every = traj_every
-            traj = self._samples(nsteps, every)
-            est = self._samples(nsteps, every or 1, rows=9) if want_estimate else None
-        models, xhat = obs.flight(self)
-        head = (self.ctx.handle, _vp(self._x), _vp(u0), _vp(K), _vp(dem), None if air is None else ctypes.byref(air[0]), _vp(models), obs.group,
-                obs.sensed, obs.h_sigma, int(meas_seed), obs.row, _vp(xhat), _vp(traj), _vp(est))
-        tail = (_vp(self._u), _vp(self.status), self.B, self.B, nsteps, max(nsteps, 1) if hold is None else hold, int(every or 1), self.dt,
-                self.xcg, self.fi_flag, int(method), self.flags, self._stream)
-        result = None
+            v.update(u0=_vp(u), K=_vp(K), u_out=_vp(self._u))
+            v["dem_seq" if scheduled else "dem"] = _vp(dem)
+        if scheduled:      # a constant input is one row held for every step
+            v["hold"] = max(nsteps, 1) if hold is None else hold
+        if scheduled and not name.endswith("_sched"):
+            v["method"] = int(method)
+        if "_wind" in name:
+            v["h_wind"] = None if air is None else ctypes.byref(air[0])
+        if obs is not None:
+            models, xhat = obs.flight(self)
+            v.update(obs=_vp(models), mgroup=obs.group, sensed=obs.sensed, h_sigma=obs.h_sigma, meas_seed=int(meas_seed), mrow0=obs.row,
+                     xhat=_vp(xhat), xhat_traj=_vp(est))
         if ensemble is not None:
             e, keep, result = self._ensemble_buffers(ensemble, nsteps // every)
-            self._check(self.lib.f16_rollout_lqg_wind_ens(*head, ctypes.byref(e), *tail))
+            v["h_ens"] = ctypes.byref(e)
+        params = [p for _, p in _cabi.functions()[name][1]]
+        if set(params) != set(v):
+            raise TypeError(f"{name}: no value for {sorted(set(params) - set(v))}, no parameter for {sorted(set(v) - set(params))}")
+        self._check(getattr(self.lib, name)(*(v[p] for p in params)))
+        if ensemble is not None:
             result._keep = keep      # (the workspace lives as long as the result: the launches may still be running)
-        else:
-            self._check(self.lib.f16_rollout_lqg_wind(*head, *tail))
-        obs.advance(nsteps)
+        if obs is not None:
+            obs.advance(nsteps)
         if air is not None and air[2] is not None:
             air[2].advance(nsteps)
         out = (traj,) if ensemble is None else ((traj, result) if keep_traj else (result,))

@@ -13,7 +13,10 @@ The sibling's own time (f16_rollout_wind, steady wind only, no samples, B = 4,09
 tools/gpu_time_rollout_wind.py) is measured the same way and held against profiles/rollout_wind_time.jsonl: `sibling_matches` says
 whether its median lies within 3 % of the recorded one (another day, another machine of the pool; the recorded spread is 1 %).
 From the repository root, on the GPU:
-    python tools/gpu_time_rollout_ens.py            (writes profiles/rollout_ens_time.jsonl; --out FILE for another place)"""
+    python tools/gpu_time_rollout_ens.py            (writes profiles/rollout_ens_time.jsonl; --out FILE for another place)
+--against-parent: instead, f16_rollout_wind_ens and f16_rollout_lqr_wind_ens (steady wind, one group, one sample, no traj) of this build
+against the same calls of the parent commit's library, by the protocol of tools/gpu_time_rollout_wind.py (alternate: a process per
+run at B = 4,096 and 65,536, this build's median inside the parent's min .. max); prints the lines."""
 import argparse
 import ctypes
 import json
@@ -23,6 +26,10 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tools"))
+import gpu_time_rollout_wind as W  # noqa: E402
+
+PAIRS = ("wind_ens_parent", "wind_ens", "lqr_ens_parent", "lqr_ens")
 SIZES = (4096, 262144)
 NSTEPS, DT, GHOLD = 1000, 0.001, 10
 PERIODS = (1, 10)
@@ -115,14 +122,56 @@ def run(B, repeats):
             torch.cuda.empty_cache()
 
 
+def run_pair(variant, B):
+    """one process of --against-parent: per method one warm-up call and one timed call -> a JSON line"""
+    import numpy as np
+    import torch
+    from f16_mpc_oop_py_amd import lib
+    from f16_mpc_oop_py_amd.workload import config2_states
+    assert torch.cuda.is_available(), "needs the MI355X"
+    L = lib.load()
+    ctx = lib.Context(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    x0, u0 = config2_states(B, seed=B)
+    dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
+    x0, u = dev(x0.T), dev(u0.T)
+    x, st = x0.clone(), torch.zeros(B, dtype=torch.int32, device="cuda:0")
+    wind = dev(np.random.default_rng(B).uniform(-20, 20, (3, B)))
+    air, e = lib.Wind(), lib.Ens()
+    air.wind_ned = wind.data_ptr()
+    keep = [torch.zeros(L.f16_ens_work_doubles(B, 1), dtype=torch.float64, device="cuda:0"), torch.zeros((1, 1), dtype=torch.int32, device="cuda:0")]
+    keep += [torch.zeros((1, 18, 1), dtype=torch.float64, device="cuda:0") for _ in range(4)]
+    e.group, e.ldg = (B + 63) // 64 * 64, 1
+    e.work, e.count, e.mean, e.m2, e.min, e.max = (t.data_ptr() for t in keep)
+    K = dev(np.repeat(np.load(os.path.join(REPO, "tests", "golden", "g567_trim_lin_lqr.npz"))["K_lqr_xcg25"].reshape(27, 1), B, 1))
+    dem = torch.zeros((3, B), dtype=torch.float64, device="cuda:0")
+
+    def reset():
+        x.copy_(x0); st.zero_()
+
+    def call(method):
+        if variant.startswith("lqr"):
+            rc = L.f16_rollout_lqr_wind_ens(ctx.handle, vp(x), vp(u), vp(K), vp(dem), ctypes.byref(air), None, ctypes.byref(e), None, vp(st), B, B, W.NSTEPS,
+                                            W.NSTEPS, W.NSTEPS, W.DT, 0.25, 1, method, 0, stream)
+        else:
+            rc = L.f16_rollout_wind_ens(ctx.handle, vp(x), vp(u), ctypes.byref(air), None, ctypes.byref(e), vp(st), B, B, W.NSTEPS, W.NSTEPS, W.NSTEPS, W.DT,
+                                        0.25, 1, method, 0, stream)
+        lib.check(rc, L)
+
+    print(json.dumps(W.timed_methods(variant, B, reset, call, st)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--run", type=int, metavar="B", help="one batch size in this process (what the parent starts)")
+    ap.add_argument("--run", nargs="+", metavar="B", help="one batch size in this process, or VARIANT B of --against-parent (what the parent starts)")
+    ap.add_argument("--against-parent", action="store_true")
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "rollout_ens_time.jsonl"))
     args = ap.parse_args()
     if args.run:
-        return run(args.run, args.repeats)
+        return run(int(args.run[0]), args.repeats) if len(args.run) == 1 else run_pair(args.run[0], int(args.run[1]))
+    if args.against_parent:
+        return W.alternate(__file__, PAIRS, W.SIZES, args.repeats, W.ONE_LANE_FAMILY)
     recorded = {}
     for line in open(os.path.join(REPO, "profiles", "rollout_wind_time.jsonl")):
         r = json.loads(line)

@@ -5,11 +5,13 @@ samples stored: 1,000 steps of 1 ms at B = 4,096 and 65,536, hifi, both methods.
     lqr          f16_rollout_lqr_wind of this build: the same instructions (tools/rollout_lqg_resources.py), so its median must lie
                  inside lqr_parent's min .. max (asserted after the lines are written)
     lqg_all      f16_rollout_lqg_wind, all nine channels sensed (three Philox calls per step), the gain of kalman_reference
+    lqg_ens      f16_rollout_lqg_wind_ens on the inputs of lqg_all: one group, one sample (the last step), no sample arrays
+    lqg_all_parent, lqg_ens_parent    the same two calls of the parent's library: held against them like lqr against lqr_parent
     lqg_rates    rates only, 0x70 (one call), a fixed small gain (the design is ill-conditioned and not the subject here)
     lqg_pass     pass-through on 0x7f (two calls), Lf = I on the sensed channels
 Protocol of tools/gpu_time_rollout_wind.py: a process per run (one warm-up call, one device-event timing per method around the library
 call alone), the variants alternating, `--repeats` rounds; medians with min .. max.  The parent process never touches the GPU; the
-children run one after another, each under a time limit, and the first that fails ends the run.  From the repository root:
+children run one after another, each under a time limit, and the first that fails ends the run (gpu_time_rollout_wind.py: alternate).  --variants A B ... times a subset.  From the repository root:
     python tools/gpu_time_rollout_wind.py --build-parent HEAD~1         (no GPU needed; writes _exp/parent/libf16hip.so)
     python tools/gpu_time_rollout_lqg.py > profiles/rollout_lqg_time.jsonl     (on the GPU)
 The committed profiles/rollout_lqg_time.jsonl was taken with --repeats 5 (each line says so); the default is 15."""
@@ -17,16 +19,14 @@ import argparse
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-PARENT_SO = os.path.join(REPO, "_exp", "parent", "libf16hip.so")
-ONE_LANE_FAMILY = {"F16_ROLLOUT_QUAD_MAXB": "0", "F16_ROLLOUT_4W_MAXB": "0"}
-VARIANTS = ("lqr_parent", "lqr", "lqg_all", "lqg_rates", "lqg_pass")
-SIZES = (4096, 65536)
-NSTEPS, DT = 1000, 0.001
+sys.path.insert(0, os.path.join(REPO, "tools"))
+from gpu_time_rollout_wind import DT, NSTEPS, ONE_LANE_FAMILY, SIZES, alternate, timed_methods  # noqa: E402
+
+VARIANTS = ("lqr_parent", "lqr", "lqg_all_parent", "lqg_all", "lqg_rates", "lqg_pass", "lqg_ens_parent", "lqg_ens")
 MPC_IDX = [3, 4, 7, 8, 9, 10, 11, 17, 16]
 
 
@@ -55,12 +55,13 @@ def run(variant, B):
     wind = dev(rng.uniform(-20, 20, (3, B)))
     air = lib.Wind()
     air.wind_ned = wind.data_ptr()
-    lqg = variant.startswith("lqg")
+    variant = variant[:-len("_parent")] if variant.endswith("_parent") else variant      # (the library is chosen by the environment)
+    lqg, ens = variant.startswith("lqg"), variant == "lqg_ens"
     if lqg:
         from f16_mpc_oop_py_amd.observer import kalman_reference, pack_models
-        sensed = {"lqg_all": 0x1ff, "lqg_rates": 0x70, "lqg_pass": 0x7f}[variant]
+        sensed = {"lqg_all": 0x1ff, "lqg_ens": 0x1ff, "lqg_rates": 0x70, "lqg_pass": 0x7f}[variant]
         sigma = np.deg2rad(np.array([0.1, 0.1, 0.1, 0.1, 0.5, 0.5, 0.5, 0.1, 0.1]))
-        if variant == "lqg_all":
+        if variant in ("lqg_all", "lqg_ens"):
             Lf = kalman_reference(Ad, np.full(9, 1e-8), sigma ** 2, sensed)[1]
         else:
             Lf = np.diag([(0.05 if variant == "lqg_rates" else 1.0) * ((sensed >> k) & 1) for k in range(9)])
@@ -70,6 +71,12 @@ def run(variant, B):
         xhat0 = x0[MPC_IDX].clone().contiguous()
         xhat = xhat0.clone()
         hs = (ctypes.c_double * 9)(*sigma)
+    if ens:
+        e, group = lib.Ens(), (B + 63) // 64 * 64
+        keep = [torch.zeros(L.f16_ens_work_doubles(B, 1), dtype=torch.float64, device="cuda:0"), torch.zeros((1, 1), dtype=torch.int32, device="cuda:0")]
+        keep += [torch.zeros((1, 18, 1), dtype=torch.float64, device="cuda:0") for _ in range(4)]
+        e.group, e.ldg = group, 1
+        e.work, e.count, e.mean, e.m2, e.min, e.max = (t.data_ptr() for t in keep)
 
     def reset():
         x.copy_(x0); st.zero_()
@@ -77,7 +84,11 @@ def run(variant, B):
             xhat.copy_(xhat0)
 
     def call(method):
-        if lqg:
+        if ens:
+            rc = L.f16_rollout_lqg_wind_ens(ctx.handle, vp(x), vp(u0), vp(Kd), vp(dem), ctypes.byref(air), vp(models), 0, sensed, ctypes.cast(hs, ctypes.c_void_p),
+                                            7, 0, vp(xhat), None, None, ctypes.byref(e), None, vp(st), B, B, NSTEPS, NSTEPS, NSTEPS, DT, 0.25, 1, method, 0,
+                                            stream)
+        elif lqg:
             rc = L.f16_rollout_lqg_wind(ctx.handle, vp(x), vp(u0), vp(Kd), vp(dem), ctypes.byref(air), vp(models), 0, sensed, ctypes.cast(hs, ctypes.c_void_p),
                                         7, 0, vp(xhat), None, None, None, vp(st), B, B, NSTEPS, NSTEPS, 1, DT, 0.25, 1, method, 0, stream)
         else:
@@ -85,55 +96,21 @@ def run(variant, B):
                                         0.25, 1, method, 0, stream)
         lib.check(rc, L)
 
-    out = dict(variant=variant, B=B)
-    for name, method in (("euler", lib.F16_INT_EULER), ("rk4", lib.F16_INT_RK4)):
-        reset()
-        call(method)
-        reset()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        call(method)
-        e1.record()
-        torch.cuda.synchronize()
-        out[name + "_ms"] = e0.elapsed_time(e1)
-        out[name + "_unflagged"] = int((st == 0).sum())
-    print(json.dumps(out), flush=True)
+    print(json.dumps(timed_methods(variant, B, reset, call, st)), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--run", nargs=2, metavar=("VARIANT", "B"), help="one run in this process (what the parent starts)")
     ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=VARIANTS)
     args = ap.parse_args()
     if args.run:
         return run(args.run[0], int(args.run[1]))
-    import numpy as np
-    assert os.path.exists(PARENT_SO), f"{PARENT_SO} is missing: run tools/gpu_time_rollout_wind.py --build-parent REV first"
-    base = {k: v for k, v in os.environ.items() if k not in ("F16_DYN_BLOCK", "F16_ROLLOUT_I32", "F16HIP_SO")}
-    base.update(ONE_LANE_FAMILY)
-    late = []
-    for B in SIZES:
-        times = {v: dict(euler=[], rk4=[]) for v in VARIANTS}
-        flying = {v: dict(euler=[], rk4=[]) for v in VARIANTS}
-        for _ in range(args.repeats):
-            for v in VARIANTS:
-                env = dict(base, F16HIP_SO=PARENT_SO) if v == "lqr_parent" else base
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--run", v, str(B)], env=env, capture_output=True, text=True, timeout=180)
-                if p.returncode != 0:
-                    sys.exit(f"run {v} at B = {B} ended with status {p.returncode}: nothing more is started\n{p.stderr[-2000:]}")
-                r = json.loads(p.stdout.strip().splitlines()[-1])
-                for m in ("euler", "rk4"):
-                    times[v][m].append(r[m + "_ms"])
-                    flying[v][m].append(r[m + "_unflagged"])
-        for m in ("euler", "rk4"):
-            stats = {v: dict(median=float(np.median(t[m])), min=float(np.min(t[m])), max=float(np.max(t[m]))) for v, t in times.items()}
-            ref = stats["lqr"]["median"]
-            print(json.dumps(dict(B=B, method=m, nsteps=NSTEPS, dt=DT, repeats=args.repeats, timer="device events, a process per run", knobs=ONE_LANE_FAMILY,
-                                  ms=stats, unflagged={v: int(min(f[m])) for v, f in flying.items()}, over_sibling={v: stats[v]["median"] / ref for v in VARIANTS[2:]})), flush=True)
-            if not stats["lqr_parent"]["min"] <= ref <= stats["lqr_parent"]["max"]:
-                late.append((B, m, ref, stats["lqr_parent"]))
-    assert not late, f"the sibling of this build lies outside the parent's min .. max: {late}"
+    def extra(B, m, stats, runs):
+        over = {v: stats[v]["median"] / stats["lqr"]["median"] for v in args.variants if "lqr" in stats and v.startswith("lqg") and not v.endswith("_parent")}
+        return dict(unflagged={v: int(min(r[m + "_unflagged"] for r in rs)) for v, rs in runs.items()}, over_sibling=over)
+    alternate(__file__, args.variants, SIZES, args.repeats, ONE_LANE_FAMILY, extra)
 
 
 if __name__ == "__main__":

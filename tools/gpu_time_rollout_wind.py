@@ -5,7 +5,8 @@
     rk_parent    f16_rollout_rk of the PARENT commit's library (built without a GPU by --build-parent, loaded through F16HIP_SO)
     rk           f16_rollout_rk of this build: the same code, so its median must lie inside rk_parent's min .. max (asserted after
                  the lines are written)
-    wind         f16_rollout_wind, steady wind only
+    wind_parent  f16_rollout_wind of the parent commit's library, steady wind only
+    wind         f16_rollout_wind, steady wind only: held against wind_parent like rk against rk_parent
     gust_seq10   + a gust_seq at gust_hold = 10
     gust_gen10   + in-kernel gusts at gust_hold = 10
     gust_gen1    + in-kernel gusts at gust_hold = 1
@@ -16,7 +17,8 @@ smallest, or the three largest, of the ten pooled values all come from the one s
 of four-point records; with fifteen it is 0.2 %, so a miss then means a difference.  The parent process never touches the GPU; the children run one after another, each under a time limit, and
 the first that fails ends the run.  From the repository root:
     python tools/gpu_time_rollout_wind.py --build-parent HEAD~1          (no GPU needed; writes _exp/parent/libf16hip.so)
-    python tools/gpu_time_rollout_wind.py > profiles/rollout_wind_time.jsonl      (on the GPU)"""
+    python tools/gpu_time_rollout_wind.py > profiles/rollout_wind_time.jsonl      (on the GPU)
+--variants A B ... times a subset (a line of a subset is appended to the file, not written over it)."""
 import argparse
 import ast
 import ctypes
@@ -31,7 +33,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 PARENT_SO = os.path.join(REPO, "_exp", "parent", "libf16hip.so")
 ONE_LANE_FAMILY = {"F16_ROLLOUT_QUAD_MAXB": "0", "F16_ROLLOUT_4W_MAXB": "0"}
-VARIANTS = ("rk_parent", "rk", "wind", "gust_seq10", "gust_gen10", "gust_gen1")
+VARIANTS = ("rk_parent", "rk", "wind_parent", "wind", "gust_seq10", "gust_gen10", "gust_gen1")
 SIZES = (4096, 65536)
 NSTEPS, DT = 1000, 0.001
 
@@ -70,7 +72,8 @@ def run(variant, B):
     x, st = x0.clone(), torch.zeros(B, dtype=torch.int32, device="cuda:0")
     rng = np.random.default_rng(B)
     air, keep = lib.Wind(), []
-    if variant not in ("rk", "rk_parent"):
+    variant = variant[:-len("_parent")] if variant.endswith("_parent") else variant      # (the library is chosen by the environment)
+    if variant != "rk":
         keep.append(dev(rng.uniform(-20, 20, (3, B))))
         air.wind_ned = keep[-1].data_ptr()
     hold = 1 if variant == "gust_gen1" else 10
@@ -86,12 +89,19 @@ def run(variant, B):
         x.copy_(x0); st.zero_()
 
     def call(method):
-        if variant in ("rk", "rk_parent"):
+        if variant == "rk":
             rc = L.f16_rollout_rk(ctx.handle, vp(x), vp(u), None, vp(st), B, B, NSTEPS, NSTEPS, 1, DT, 0.25, 1, method, 0, stream)
         else:
             rc = L.f16_rollout_wind(ctx.handle, vp(x), vp(u), ctypes.byref(air), None, vp(st), B, B, NSTEPS, NSTEPS, 1, DT, 0.25, 1, method, 0, stream)
         lib.check(rc, L)
 
+    print(json.dumps(timed_methods(variant, B, reset, call, st)), flush=True)
+
+
+def timed_methods(variant, B, reset, call, st):
+    """per method one warm-up call and one call between device events, the state put back before each -> the JSON line of a run"""
+    import torch
+    from f16_mpc_oop_py_amd import lib
     out = dict(variant=variant, B=B)
     for name, method in (("euler", lib.F16_INT_EULER), ("rk4", lib.F16_INT_RK4)):
         reset()
@@ -105,7 +115,35 @@ def run(variant, B):
         torch.cuda.synchronize()
         out[name + "_ms"] = e0.elapsed_time(e1)
         out[name + "_unflagged"] = int((st == 0).sum())
-    print(json.dumps(out), flush=True)
+    return out
+
+
+def alternate(script, variants, sizes, repeats, knobs, extra=lambda B, m, stats, runs: {}):
+    """The protocol for the parent process of a timing tool: per batch size `repeats` rounds of one child process per variant
+    (`script --run VARIANT B`; a *_parent variant under F16HIP_SO = the parent's library), one JSON line per (B, method) with the
+    medians and min .. max, then the assertion that every variant with a *_parent twin has its median inside the twin's min .. max."""
+    import numpy as np
+    assert os.path.exists(PARENT_SO), f"{PARENT_SO} is missing: run tools/gpu_time_rollout_wind.py --build-parent REV first"
+    base = {k: v for k, v in os.environ.items() if k not in ("F16_DYN_BLOCK", "F16_ROLLOUT_I32", "F16HIP_SO")}
+    base.update(knobs)
+    late = []
+    for B in sizes:
+        runs = {v: [] for v in variants}
+        for _ in range(repeats):
+            for v in variants:
+                env = dict(base, F16HIP_SO=PARENT_SO) if v.endswith("_parent") else base
+                p = subprocess.run([sys.executable, os.path.abspath(script), "--run", v, str(B)], env=env, capture_output=True, text=True, timeout=180)
+                if p.returncode != 0:
+                    sys.exit(f"run {v} at B = {B} ended with status {p.returncode}: nothing more is started\n{p.stderr[-2000:]}")
+                runs[v].append(json.loads(p.stdout.strip().splitlines()[-1]))
+        for m in ("euler", "rk4"):
+            t = {v: [r[m + "_ms"] for r in rs] for v, rs in runs.items()}
+            stats = {v: dict(median=float(np.median(x)), min=float(np.min(x)), max=float(np.max(x))) for v, x in t.items()}
+            print(json.dumps(dict(B=B, method=m, nsteps=NSTEPS, dt=DT, repeats=repeats, timer="device events, a process per run", knobs=knobs,
+                                  ms=stats, **extra(B, m, stats, runs))), flush=True)
+            late += [(B, m, v, stats[v]["median"], stats[v + "_parent"]) for v in variants
+                     if v + "_parent" in stats and not stats[v + "_parent"]["min"] <= stats[v]["median"] <= stats[v + "_parent"]["max"]]
+    assert not late, f"calls of this build whose median lies outside the min .. max of the parent's: {late}"
 
 
 def main():
@@ -113,35 +151,14 @@ def main():
     ap.add_argument("--build-parent", metavar="REV")
     ap.add_argument("--run", nargs=2, metavar=("VARIANT", "B"), help="one run in this process (what the parent starts)")
     ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=VARIANTS)
     args = ap.parse_args()
     if args.build_parent:
         return build_parent(args.build_parent)
     if args.run:
         return run(args.run[0], int(args.run[1]))
-    import numpy as np
-    assert os.path.exists(PARENT_SO), f"{PARENT_SO} is missing: run --build-parent REV first"
-    base = {k: v for k, v in os.environ.items() if k not in ("F16_DYN_BLOCK", "F16_ROLLOUT_I32", "F16HIP_SO")}
-    base.update(ONE_LANE_FAMILY)
-    late = []
-    for B in SIZES:
-        times = {v: dict(euler=[], rk4=[]) for v in VARIANTS}
-        for _ in range(args.repeats):
-            for v in VARIANTS:
-                env = dict(base, F16HIP_SO=PARENT_SO) if v == "rk_parent" else base
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--run", v, str(B)], env=env, capture_output=True, text=True, timeout=180)
-                if p.returncode != 0:
-                    sys.exit(f"run {v} at B = {B} ended with status {p.returncode}: nothing more is started\n{p.stderr[-2000:]}")
-                r = json.loads(p.stdout.strip().splitlines()[-1])
-                for m in ("euler", "rk4"):
-                    times[v][m].append(r[m + "_ms"])
-        for m in ("euler", "rk4"):
-            stats = {v: dict(median=float(np.median(t[m])), min=float(np.min(t[m])), max=float(np.max(t[m]))) for v, t in times.items()}
-            ref = stats["rk"]["median"]
-            print(json.dumps(dict(B=B, method=m, nsteps=NSTEPS, dt=DT, repeats=args.repeats, timer="device events, a process per run", knobs=ONE_LANE_FAMILY,
-                                  ms=stats, over_still_air={v: stats[v]["median"] / ref for v in VARIANTS[2:]})), flush=True)
-            if not stats["rk_parent"]["min"] <= ref <= stats["rk_parent"]["max"]:
-                late.append((B, m, ref, stats["rk_parent"]))
-    assert not late, f"the still-air call of this build lies outside the parent's min .. max: {late}"
+    still = lambda stats: {v: stats[v]["median"] / stats["rk"]["median"] for v in args.variants if "rk" in stats and not v.startswith("rk") and not v.endswith("_parent")}
+    alternate(__file__, args.variants, SIZES, args.repeats, ONE_LANE_FAMILY, lambda B, m, stats, runs: dict(over_still_air=still(stats)))
 
 
 if __name__ == "__main__":

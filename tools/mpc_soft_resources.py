@@ -15,31 +15,17 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from f16_mpc_oop_py_amd import lib  # noqa: E402
+sys.path.insert(0, os.path.join(REPO, "tools"))
+from device_code import compiled, demangled, parent_tree, parse_remarks  # noqa: E402
 
-FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill")
+COLUMNS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill")
 HEAD = ("SGPR", "VGPR", "AGPR", "scratch B/lane", "LDS B", "waves/SIMD", "SGPR spill", "VGPR spill")
 
 
-def remarks(csrc):
-    """{demangled name: {field: value}} of one compile of <csrc>/f16_mpc_wave.hip (kernels and out-of-line device functions)"""
-    flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                                                                         "-o", os.path.join(tmp, "wave.s"), os.path.join(csrc, "f16_mpc_wave.hip")]
-        err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-        asm = open(os.path.join(tmp, "wave.s")).read()
-    funcs, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = {"mangled": m.group(1)}
-            funcs.append(cur)
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*): (\d+)", line)
-        if m and cur is not None and m.group(1) in FIELDS:
-            cur[m.group(1)] = int(m.group(2))
+def remarks(root):
+    """{demangled name: {field: value}} of one compile of csrc/f16_mpc_wave.hip under `root` (kernels and out-of-line device functions)"""
+    err, asm = compiled(root, "f16_mpc_wave.hip")
+    funcs = parse_remarks(err)
     # the out-of-line device functions have no remark: their figures stand behind their code in the listing ("; Function info:")
     # -- and there is no spill count for them, so the scratch accesses inside their loops are counted instead (the hot loop: Depth >= 2)
     for m in re.finditer(r"\.Lfunc_end\d+:\n\t\.size\t(\S+), [^\n]*\n(?:[^\n]*\n){1,16}?; Function info:\n(.*?); MemoryBound", asm, flags=re.S):
@@ -56,8 +42,7 @@ def remarks(csrc):
                 hot += 1
         funcs.append({"mangled": m.group(1), "TotalSGPRs": int(info["TotalNumSgprs"]), "VGPRs": int(info["NumVgprs"]), "AGPRs": int(info["NumAgprs"]),
                       "ScratchSize [bytes/lane]": int(info["ScratchSize"]), "hot": hot})
-    names = subprocess.run(["c++filt"], input="\n".join(k["mangled"] for k in funcs), capture_output=True, text=True, check=True).stdout.split("\n")
-    return dict(zip(names, funcs))
+    return demangled(funcs)
 
 
 def twin_key(name):
@@ -79,15 +64,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-rev", default="HEAD~1", help="the revision whose hard kernels the figures are compared with")
     a = ap.parse_args()
-    here = table(remarks(lib.CSRC))
+    here = table(remarks(REPO))
     with tempfile.TemporaryDirectory() as tmp:
-        tar = subprocess.run(["git", "-C", REPO, "archive", a.parent_rev, "f16_mpc_oop_py_amd/csrc", "include"], capture_output=True, check=True).stdout
-        subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-        parent = table(remarks(os.path.join(tmp, "f16_mpc_oop_py_amd", "csrc")))
+        parent = table(remarks(parent_tree(a.parent_rev, tmp)))
     rev = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", a.parent_rev], capture_output=True, text=True, check=True).stdout.strip()
     out = os.path.join(REPO, "profiles", "mpc_soft_resources.txt")
     bad = []
-    fmt = lambda k: "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(FIELDS, (6, 6, 6, 15, 8, 11, 11, 11)))
+    fmt = lambda k: "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(COLUMNS, (6, 6, 6, 15, 8, 11, 11, 11)))
     with open(out, "w") as f:
         f.write("# hipcc -Rpass-analysis=kernel-resource-usage, gfx950, flags of the default build, csrc/f16_mpc_wave.hip: every soft-row\n"
                 "# instantiation (f16_mpc_plan_soft_rows) beside its hard twin, and the hard twin as the parent revision compiles it.  A kernel's\n"
@@ -104,7 +87,7 @@ def main():
                     f"{'':<18}{'':<7}{'soft':<8}{fmt(soft)}{note(soft)}\n")
             if soft.get("hot", 0):
                 bad.append((fam, targs, "soft twin: scratch accesses inside a loop"))
-            if any(hard.get(fl, 0) != par.get(fl, 0) for fl in FIELDS):
+            if any(hard.get(fl, 0) != par.get(fl, 0) for fl in COLUMNS):
                 bad.append((fam, targs, "hard differs from the parent"))
             if fam.startswith("k_") and any(soft.get(fl, 0) != hard.get(fl, 0) for fl in ("LDS Size [bytes/block]", "Occupancy [waves/SIMD]")):
                 bad.append((fam, targs, "soft twin: LDS size or occupancy"))

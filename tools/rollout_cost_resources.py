@@ -6,37 +6,16 @@ default build (no GPU needed).  Writes profiles/rollout_cost_resources.txt.
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from f16_mpc_oop_py_amd import lib  # noqa: E402
-
-FIELDS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
+sys.path.insert(0, os.path.join(REPO, "tools"))
+from device_code import FIELDS, WIDTHS, remarks  # noqa: E402
 
 
 def main():
-    src = os.path.join(lib.CSRC, "f16_dynamics.hip")
-    flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                                                                         "-o", os.path.join(tmp, "dyn.s"), src]
-        err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = {"mangled": m.group(1)}
-            kernels.append(cur)
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*): (\d+)", line)
-        if m and cur is not None and m.group(1) in FIELDS:
-            cur[m.group(1)] = int(m.group(2))
-    names = subprocess.run(["c++filt"], input="\n".join(k["mangled"] for k in kernels), capture_output=True, text=True, check=True).stdout.split("\n")
     rows = []
-    for k, n in zip(kernels, names):
+    for n, k in remarks(REPO, "f16_dynamics.hip").items():
         m = re.match(r"void f16::(k_rollout(?:_i|_exact)?)<(.*?)>\(", n)
         if not m:
             continue
@@ -55,7 +34,7 @@ def main():
         f.write(f"{'kernel':<16}{'<..>':<10}{'variant':<11}{'VGPR':>5}{'AGPR':>5}{'SGPR':>5}{'scratch B/lane':>15}{'waves/SIMD':>11}"
                 f"{'SGPR spill':>11}{'VGPR spill':>11}{'LDS B':>8}\n")
         for kern, targs, variant, k in rows:
-            f.write(f"{kern:<16}{targs:<10}{variant:<11}" + "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(FIELDS, (5, 5, 5, 15, 11, 11, 11, 8))) + "\n")
+            f.write(f"{kern:<16}{targs:<10}{variant:<11}" + "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(FIELDS, WIDTHS)) + "\n")
             assert k.get("LDS Size [bytes/block]", 0) <= 163840, (kern, targs, variant)
     print(open(out).read())
 

@@ -12,62 +12,19 @@ import argparse
 import hashlib
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
-from f16_mpc_oop_py_amd import lib  # noqa: E402
-from rollout_rk4_resources import FIELDS, remarks  # noqa: E402
-
-WIDTHS = (5, 5, 5, 15, 11, 11, 11, 8)
-SRC = os.path.join("f16_mpc_oop_py_amd", "csrc", "f16_dynamics.hip")
-
-
-def assembly(root, src=SRC):
-    """{function symbol: [instruction lines]} of `src` (default: f16_dynamics.hip) under `root`"""
-    flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "dyn.s")
-        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(root, src)],
-                       capture_output=True, text=True, check=True)
-        text = open(out).read()
-    symbols = set(re.findall(r"^\s*\.type\s+([\w.$]+),@function", text, re.M))
-    funcs, name = {}, None
-    for line in text.splitlines():
-        m = re.match(r"([A-Za-z_][\w.$]*):", line)
-        if m and m.group(1) in symbols:
-            name = m.group(1)
-            funcs[name] = []
-            continue
-        if line.startswith(".Lfunc_end"):
-            name = None
-            continue
-        if name is None:
-            continue
-        code = line.split(";")[0].strip()
-        if not code or code.startswith(".") and not code.startswith(".LBB"):
-            continue
-        funcs[name].append(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", code))
-    return funcs
-
-
-def parent_tree(rev, tmp):
-    tar = subprocess.run(["git", "-C", REPO, "archive", rev, "f16_mpc_oop_py_amd/csrc", "include"], capture_output=True, check=True).stdout
-    subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
-    return tmp
+from device_code import FIELDS, WIDTHS, assembly, default_parent, parent_tree, remarks  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default=None)
-    rev = ap.parse_args().parent
-    if rev is None:
-        dirty = subprocess.run(["git", "-C", REPO, "status", "--porcelain", "f16_mpc_oop_py_amd/csrc", "include"], capture_output=True, text=True).stdout
-        rev = "HEAD" if dirty.strip() else "HEAD~1"
-    found = remarks([])
+    rev = default_parent(ap.parse_args().parent)
+    found = remarks(REPO, "f16_dynamics.hip")
     new, twins = [], {}
     for n, k in found.items():
         m = re.match(r"void f16::k_rollout_gs<(-?\d+), (-?\d+), (\d+)>\(", n)

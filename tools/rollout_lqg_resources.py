@@ -13,16 +13,12 @@ import argparse
 import hashlib
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
-from rollout_gs_resources import assembly, parent_tree  # noqa: E402
-from rollout_rk4_resources import FIELDS  # noqa: E402
-from rollout_wind_resources import CSRC, WIDTHS, remarks  # noqa: E402
+from device_code import FIELDS, WIDTHS, assembly, default_parent, parent_tree, remarks  # noqa: E402
 
 EXISTING = ("f16_wind.hip", "f16_wind_ens.hip", "f16_control.hip")
 
@@ -30,18 +26,15 @@ EXISTING = ("f16_wind.hip", "f16_wind_ens.hip", "f16_control.hip")
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default=None)
-    rev = ap.parse_args().parent
-    if rev is None:
-        dirty = subprocess.run(["git", "-C", REPO, "status", "--porcelain", "f16_mpc_oop_py_amd/csrc", "include"], capture_output=True, text=True).stdout
-        rev = "HEAD" if dirty.strip() else "HEAD~1"
+    rev = default_parent(ap.parse_args().parent)
     before, after, asm_before, asm_after = {}, {}, {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         parent = parent_tree(rev, tmp)
         for name in EXISTING:
-            before[name], asm_before[name] = remarks(parent, name), assembly(parent, os.path.join(CSRC, name))
+            before[name], asm_before[name] = remarks(parent, name), assembly(parent, name)
     for name in EXISTING:
-        after[name], asm_after[name] = remarks(REPO, name), assembly(REPO, os.path.join(CSRC, name))
-    obs, asm_obs = remarks(REPO, "f16_observer.hip"), assembly(REPO, os.path.join(CSRC, "f16_observer.hip"))
+        after[name], asm_after[name] = remarks(REPO, name), assembly(REPO, name)
+    obs, asm_obs = remarks(REPO, "f16_observer.hip"), assembly(REPO, "f16_observer.hip")
     for k in obs.values():
         k["instr"] = len(asm_obs.get(k["mangled"], ()))
     for name in EXISTING:

@@ -10,15 +10,12 @@ import re
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
-from rollout_rk4_resources import FIELDS, remarks  # noqa: E402
-
-WIDTHS = (5, 5, 5, 15, 11, 11, 11, 8)
+from device_code import FIELDS, WIDTHS, remarks  # noqa: E402
 
 
 def main():
-    found = remarks([])
+    found = remarks(REPO, "f16_dynamics.hip")
     fused, twins = [], {}
     for n, k in found.items():
         m = re.match(r"void f16::k_rollout_mppi<(-?\d+), (-?\d+), (\d+)>\(", n)

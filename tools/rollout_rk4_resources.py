@@ -8,38 +8,13 @@ if a reachable RK4 instantiation has scratch or spills.
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from f16_mpc_oop_py_amd import lib  # noqa: E402
+sys.path.insert(0, os.path.join(REPO, "tools"))
+from device_code import FIELDS, WIDTHS, remarks  # noqa: E402
 
-FIELDS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 VARIANT = {("false", "true", "false"): "open loop", ("true", "true", "false"): "LQR law", ("false", "true", "true"): "scored"}
-
-
-def remarks(extra):
-    """{demangled kernel name: {field: value}} of one compile of f16_dynamics.hip"""
-    src = os.path.join(lib.CSRC, "f16_dynamics.hip")
-    flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + extra
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                                                                         "-o", os.path.join(tmp, "dyn.s"), src]
-        err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = {"mangled": m.group(1)}
-            kernels.append(cur)
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*): (\d+)", line)
-        if m and cur is not None and m.group(1) in FIELDS:
-            cur[m.group(1)] = int(m.group(2))
-    names = subprocess.run(["c++filt"], input="\n".join(k["mangled"] for k in kernels), capture_output=True, text=True, check=True).stdout.split("\n")
-    return dict(zip(names, kernels))
 
 
 def rows_of(found, reachable):
@@ -58,9 +33,9 @@ def rows_of(found, reachable):
 
 
 def main():
-    rows = rows_of(remarks([]), True)
+    rows = rows_of(remarks(REPO, "f16_dynamics.hip"), True)
     built = {r[:4] for r in rows}
-    rows += [r[:4] + (False, r[5]) for r in rows_of(remarks(["-DF16_RK4_512"]), True) if r[:4] not in built]
+    rows += [r[:4] + (False, r[5]) for r in rows_of(remarks(REPO, "f16_dynamics.hip", ["-DF16_RK4_512"]), True) if r[:4] not in built]
     rows.sort(key=lambda r: (r[0], [int(v) for v in r[1].split(",") if v.strip()], r[2], r[3]))
     out = os.path.join(REPO, "profiles", "rollout_rk4_resources.txt")
     bad = []
@@ -75,7 +50,7 @@ def main():
                 f"{'SGPR spill':>11}{'VGPR spill':>11}{'LDS B':>8}\n")
         for kern, targs, variant, stages, reachable, k in rows:
             f.write(f"{kern:<16}{targs:<10}{variant:<11}{stages:>7}{'yes' if reachable else 'no':>6}"
-                    + "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(FIELDS, (5, 5, 5, 15, 11, 11, 11, 8))) + "\n")
+                    + "".join(f"{k.get(fl, 0):>{w}}" for fl, w in zip(FIELDS, WIDTHS)) + "\n")
             assert k.get("LDS Size [bytes/block]", 0) <= 163840, (kern, targs, variant)
             # k_rollout_exact calls its step: the compiler reserves a stack for the call (the step's own frame), which is no spill
             if stages == 4 and reachable and kern != "k_rollout_exact" and (k.get("ScratchSize [bytes/lane]", 0) or k.get("VGPRs Spill", 0)):

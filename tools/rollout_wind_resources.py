@@ -15,49 +15,18 @@ import argparse
 import hashlib
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
-from f16_mpc_oop_py_amd import lib  # noqa: E402
-from rollout_gs_resources import assembly, parent_tree  # noqa: E402
-from rollout_rk4_resources import FIELDS  # noqa: E402
-
-WIDTHS = (5, 5, 5, 15, 11, 11, 11, 8)
-CSRC = os.path.join("f16_mpc_oop_py_amd", "csrc")
-
-
-def remarks(root, name):
-    """{demangled kernel name: {field: value}} of one compile of csrc/<name> under `root`"""
-    flags = [f for f in lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    with tempfile.TemporaryDirectory() as tmp:
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags + ["--offload-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                                                                         "-o", os.path.join(tmp, "k.s"), os.path.join(root, CSRC, name)]
-        err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    kernels, cur = [], None
-    for line in err.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = {"mangled": m.group(1)}
-            kernels.append(cur)
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][A-Za-z /\[\]]*): (\d+)", line)
-        if m and cur is not None and m.group(1) in FIELDS:
-            cur[m.group(1)] = int(m.group(2))
-    names = subprocess.run(["c++filt"], input="\n".join(k["mangled"] for k in kernels), capture_output=True, text=True, check=True).stdout.split("\n")
-    return {n: dict({f: k.get(f, 0) for f in FIELDS}, mangled=k["mangled"]) for n, k in zip(names, kernels)}
+from device_code import FIELDS, WIDTHS, assembly, default_parent, parent_tree, remarks  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default=None)
-    rev = ap.parse_args().parent
-    if rev is None:
-        dirty = subprocess.run(["git", "-C", REPO, "status", "--porcelain", "f16_mpc_oop_py_amd/csrc", "include"], capture_output=True, text=True).stdout
-        rev = "HEAD" if dirty.strip() else "HEAD~1"
+    rev = default_parent(ap.parse_args().parent)
     with tempfile.TemporaryDirectory() as tmp:
         parent = parent_tree(rev, tmp)
         dyn_before, asm_before = remarks(parent, "f16_dynamics.hip"), assembly(parent)
@@ -65,8 +34,8 @@ def main():
     wind = remarks(REPO, "f16_wind.hip")
     rollouts = sorted(n for n in dyn_before if "k_rollout" in n)
     moved = [n for n in rollouts if dyn_before[n] != dyn.get(n)]
-    asm_wind = assembly(REPO, os.path.join(CSRC, "f16_wind.hip"))
-    ens, asm_ens = remarks(REPO, "f16_wind_ens.hip"), assembly(REPO, os.path.join(CSRC, "f16_wind_ens.hip"))
+    asm_wind = assembly(REPO, "f16_wind.hip")
+    ens, asm_ens = remarks(REPO, "f16_wind_ens.hip"), assembly(REPO, "f16_wind_ens.hip")
     for found, asm in ((wind, asm_wind), (dyn, asm_after), (ens, asm_ens)):          # instructions of each kernel's own body, as emitted
         for k in found.values():
             k["instr"] = len(asm.get(k["mangled"], ()))
