@@ -730,10 +730,22 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 //   wave 1  x[9..11]  Cy, Cn, Cl static totals on sub-lanes 0,1,2; rate products of the     | moment equations, Euler
 //                     moment equations
 //   wave 2  x[0..8]   sin/cos of phi, theta, beta, alpha on sub-lanes 0..3; kinematic +     | force equations, Euler
-//                     navigation equations, Euler on x[0..5]; the trajectory sample
+//                     navigation equations, Euler on x[0..5]; GROUPS = 2: the trajectory
+//                     sample
 //   wave 3  x[12..17] atmosphere; the four actuators on sub-lanes 0..3; flap model, Euler;  | the altitude part of the next step's
-//                     the LQR law and the input schedule                                    |   atmosphere (GROUPS = 1)
-// Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached), and with the cells the
+//                     the LQR law and the input schedule                                    |   atmosphere, its log's quotient and
+//                                                                                           |   polynomial (GROUPS = 1)
+//   wave 4  --        GROUPS = 1 only (320 threads): the trajectory sample -- five reads of | --
+//                     the published state per lane, five stores when a sample is due
+// GROUPS = 1: THE SAMPLES ARE STORED BY A FIFTH WAVE.  None of the sample's work feeds the step, and on wave 2 it stood in a half that
+// wave paces: the reads, the counter and its branch, five address computations and stores, and the scalars of all that, which pushed
+// wave 2's lane masks out into lane moves.  The store wave runs the same loop text with role index 4, so it executes the same barriers;
+// it owns the sample pointer and counter, keeps no state across its loop (what the common prologue loads in front of the role
+// switch is dead for it), reads no envelope flag, reports no status and writes nothing in the epilogue.  Five waves on four
+// SIMDs: two share one, so the kernel is compiled for 256 vector registers (it used 250 / 254 before) and the dispatcher picks the
+// pair (what the stamps say about it).
+// Both table waves re-use the last step's cells while every lane stays inside its own (quad_br_cached), with the cell the refined
+// reciprocal of its width (lambda on such a step is one subtraction and one product, no v_rcp_f64 chain and no guard), and the
 // TABLE VALUES read then (LongCorners / LatCorners, f16_plant_quad.hpp: the four / eight corner sets, the 1-D rows, the 45-degree
 // node): on such a step -- 93 % of the workload's -- a table wave forms no table address and reads nothing from LDS but the
 // published state; the values are re-read on a step on which a lane has left its cell, at launch start and for every group of
@@ -754,9 +766,10 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // LAUNCH: each role loads its own table from QUAD_K (constant memory, f16_plant.hpp) once, in front of its own step loop
 // (f16_quad_steps.inc), and no step loads it again.  Waves 0 (psi) and 3 (atmosphere) keep theirs in scalar registers, the
 // constant the scalar operand of a three-address FMA; wave 2 (trigonometry) keeps its 21 doubles in lane-uniform vector registers
-// -- its loop's lane masks and sample scalars leave no room for 42 scalar registers -- and issues the same FMA with three vector
-// operands.  (Loaded at the top of a role's part of every step, as before, the loads were issued BEHIND the role's wait for its
-// LDS reads and the first multiply waited for them: 228 / 625 / 135 cycles per step on waves 2 / 3 / 0, DESIGN.md.)  As literals
+// and issues the same FMA with three vector operands (chosen when its loop's lane masks and sample scalars left no room for 42
+// scalar registers; the scalar form with the sample on a wave of its own: DESIGN.md, the store wave's section).  (Loaded at the
+// top of a role's part of every step, as before, the loads were issued BEHIND the role's wait for its LDS reads and the first
+// multiply waited for them: 228 / 625 / 135 cycles per step on waves 2 / 3 / 0, DESIGN.md.)  As literals
 // the constants cost the trigonometry, psi and atmosphere roles a register move in front of nearly every polynomial step, and 28
 // vector registers for the sin/cos table.  Same operations, same operands, same order.
 // Wave 2 publishes x[0..5] and tests x[2] where they become final, behind barrier B, under the wait for the totals; between the
@@ -767,12 +780,13 @@ __global__ __launch_bounds__(256) void k_rollout_4w(RolloutArgs<SCHED> a) {
 // half, which was empty: x[2] is final since wave 2's first half, which hands it over beside psi.  Behind barrier A wave 3 is left
 // with the log's polynomial and sums, the exp, the density and -- the only part that needs this step's airspeed -- qbar.  The cut
 // stands where the stamps put it: with the whole log ahead wave 3 paced the second half (883 cycles against wave 1's 728).
-// A wave reads its OWN states from its registers, not from LDS: wave 2's sin / cos polynomial starts without an LDS round trip, and
-// the sample's reads and stores stand under it.
+// A wave reads its OWN states from its registers, not from LDS: wave 2's sin / cos polynomial starts without an LDS round trip.
+constexpr int quad_block_threads(int groups) { return groups == 1 ? 320 : 256 * groups; }
 template <int GROUPS, bool LQR = false, bool SCHED = false>
-__global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a) {
+__global__ __launch_bounds__(quad_block_threads(GROUPS)) void k_rollout_q(RolloutArgs<SCHED> a) {
   constexpr int NA = 16 * GROUPS;
   constexpr bool G1 = GROUPS == 1;     // cell re-use and psi on wave 0: one group only (at GROUPS = 2 the registers spill)
+  constexpr int NT = quad_block_threads(GROUPS);           // threads of the block: four role waves per group; GROUPS = 1: and the store wave
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
   __shared__ double xs[18][NA], xt[11][NA];                // published state; Cx Cz Cm | Cy Cn Cl static | qbar ps | Cy Cn Cl damping
   __shared__ int xenv[3][NA], xst[2][NA];
@@ -785,15 +799,15 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
   {
     const double2 *src = reinterpret_cast<const double2 *>(a.tab);
     double2 *dst = reinterpret_cast<double2 *>(tab);
-    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += 256 * GROUPS) dst[i] = src[i];
+    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += NT) dst[i] = src[i];
     __syncthreads();
   }
 #ifdef F16_EXP_STAMPQ
   const unsigned long long tstage = __builtin_amdgcn_s_memtime() - tstage0;     // kernel entry to the first barrier: the table staging
 #endif
-  // GROUPS = 1: the role index from a scalar register (wave-uniform), so that the role dispatch is a scalar branch
-  const int role = G1 ? __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3) : (threadIdx.x >> 6) & 3;
-  const int grp = threadIdx.x >> 8, lane = threadIdx.x & 63, ac = 16 * grp + (lane >> 2), s = lane & 3;
+  // GROUPS = 1: the role index from a scalar register (wave-uniform), so that the role dispatch is a scalar branch; 4 = the store wave
+  const int role = G1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (threadIdx.x >> 6) & 3;
+  const int grp = G1 ? 0 : threadIdx.x >> 8, lane = threadIdx.x & 63, ac = 16 * grp + (lane >> 2), s = lane & 3;
   const bool envchk = !(a.flags & FLAG_NO_ENVELOPE);
   for (long b0 = (long)blockIdx.x * NA; b0 < a.B; b0 += (long)gridDim.x * NA) {
     const bool valid = b0 + ac < a.B;
@@ -811,7 +825,7 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
     }
     double xact = s == 0 ? x[12] : (s == 1 ? x[13] : (s == 2 ? x[14] : x[15]));   // wave 3: its actuator state
     int st = a.status ? a.status[b] : 0;
-    double *tr = a.traj ? a.traj + b : nullptr;            // next sample (written by wave 2 from the published state)
+    double *tr = a.traj ? a.traj + b : nullptr;            // next sample (from the published state; GROUPS = 1: by the store wave)
     int until_store = a.traj_every;
     QuadCell qc = quad_cell_none();                        // waves 0 / 1: cells of the last full lookup (none at launch start)
     LongCorners klong = {};                                // GROUPS = 1, wave 0: the table values of that lookup (a role's loop keeps its own alone)
@@ -858,6 +872,10 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
           constexpr int wave = 2;
 #include "f16_quad_steps.inc"
         } break;
+        case 4: {
+          constexpr int wave = 4;
+#include "f16_quad_steps.inc"
+        } break;
         default: {
           constexpr int wave = 3;
 #include "f16_quad_steps.inc"
@@ -869,7 +887,9 @@ __global__ __launch_bounds__(256 * GROUPS) void k_rollout_q(RolloutArgs<SCHED> a
     }
 #ifdef F16_EXP_STAMPQ
     if (lane == 0 && blockIdx.x == 0 && a.traj) {   // diagnostic build: cycles per segment, per wave, into trajectory row 2
-      double *d = a.traj + 18 * a.ld * 2 + role * 4;
+      // (the store wave's row in state row 2: columns 16.. of row 0 belong to the next workgroup's aircraft, whose sample may be
+      //  written back from another L2 after this)
+      double *d = a.traj + 18 * a.ld * 2 + (role < 4 ? role * 4 : 2 * a.ld);
       d[0] = (double)tD; d[1] = (double)tA; d[2] = (double)tB; d[3] = (double)tC;
       a.traj[18 * a.ld * 2 + a.ld + role] = (double)tstage;   // (state row 1 of the same sample; once per launch, not per step)
     }
@@ -1077,7 +1097,7 @@ static int rollout_dispatch(f16_ctx *ctx, RolloutArgsGS<SCHED, COST, GS> &a, voi
     if (hifi && B <= 2 * maxq) {
       // four lanes per aircraft.  At most 16 aircraft per CU: one 16-aircraft workgroup per CU; at most 32: two 16-aircraft
       // groups per workgroup
-      if (B <= maxq) hipLaunchKernelGGL((k_rollout_q<1, LQR, SCHED>), dim3((unsigned)((B + 15) / 16)), dim3(256), 0, st, a);
+      if (B <= maxq) hipLaunchKernelGGL((k_rollout_q<1, LQR, SCHED>), dim3((unsigned)((B + 15) / 16)), dim3(quad_block_threads(1)), 0, st, a);
       else hipLaunchKernelGGL((k_rollout_q<2, LQR, SCHED>), dim3((unsigned)((B + 31) / 32)), dim3(512), 0, st, a);
       return hip_check(hipGetLastError(), what);
     }

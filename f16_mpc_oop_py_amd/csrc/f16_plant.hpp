@@ -149,14 +149,30 @@ F16_DEV LogQuot log_k_quot(const PowK &K, double x) {
   const double l = fma(r, d32, -fma(-ym1, r, h));          // low part
   return {h, l, e};
 }
+// log_k_sum in its two parts: log_k_poly -- the square of the quotient and the Horner polynomial in it, which need the quotient alone
+// (the quad rollout evaluates them with the quotient, half a step ahead); log_k_tail -- the sums and the special arguments.
+struct LogPoly {
+  double z, c;                     // h^2, the polynomial in it
+};
 template <typename OP = KScalar>
-F16_DEV double log_k_sum(const PowK &K, double x, const LogQuot &qt) {
-  const double h = qt.h, l = qt.l;
-  const int e = qt.e;
-  const double z = h * h;
+F16_DEV LogPoly log_k_poly(const PowK &K, const LogQuot &qt) {
+  const double z = qt.h * qt.h;
   double c = OP::vvk(z, K.L[0], K.L[1]);
 #pragma unroll
   for (int k = 2; k < 7; ++k) c = OP::vvk(z, c, K.L[k]);
+  return {z, c};
+}
+template <typename OP = KScalar>
+F16_DEV double log_k_tail(const PowK &K, double x, const LogQuot &qt, const LogPoly &pl);
+template <typename OP = KScalar>
+F16_DEV double log_k_sum(const PowK &K, double x, const LogQuot &qt) {
+  return log_k_tail<OP>(K, x, qt, log_k_poly<OP>(K, qt));
+}
+template <typename OP>
+F16_DEV double log_k_tail(const PowK &K, double x, const LogQuot &qt, const LogPoly &pl) {
+  const double h = qt.h, l = qt.l;
+  const int e = qt.e;
+  const double z = pl.z, c = pl.c;
   const double a44 = __builtin_ldexp(h, 1), a45 = __builtin_ldexp(l, 1);
   const double t46 = h * z;
   const double u48 = fma(t46, c, a44);

@@ -48,7 +48,8 @@ F16_DEV void quad_store_sample(const double (&smp)[5], double *tr, int s, long l
 
 // The three axis brackets of a role, ONE PER SUB-LANE (0: alpha on ALPHA1, 1: beta, 2/3: elevator on DH1 or DH2), shared
 // across the quad by DPP broadcasts: first the cell indices (the table addresses need nothing else), later lambda.
-struct QuadBr { BrCell c; int ja, jb, jd; bool offa, offb, offd; };
+// l: the lane's own lambda where the cell cache forms it with the cell (quad_br_cached, F16_FAST_DIV), else unused
+struct QuadBr { BrCell c; int ja, jb, jd; bool offa, offb, offd; double l; };
 template <bool USE_D2, typename TP>
 F16_DEV BrRaw quad_br_load(TP T, double alpha, double beta, double el, int s, int &nX, double &vX) {
   const int ax = s < 2 ? s : 2;
@@ -61,6 +62,7 @@ F16_DEV BrRaw quad_br_load(TP T, double alpha, double beta, double el, int s, in
 }
 F16_DEV QuadBr quad_br_cells(const BrRaw &r, int nX, double vX) {
   QuadBr q;
+  q.l = 0;
   bool off;
   q.c = br_cell(r, nX, vX, off);
   q.ja = quad_bcast_i<0>(q.c.j); q.jb = quad_bcast_i<1>(q.c.j); q.jd = quad_bcast_i<2>(q.c.j);
@@ -76,29 +78,59 @@ F16_DEV QuadBr quad_br_cells(const BrRaw &r, int nX, double vX) {
 // cell is unique for an on-grid v < x1, so the full path could not have picked another one.  x0 = NaN: no cell yet.
 // `hit` tells the caller which path was taken (the same for the whole wave): on a hit the cell indices are last step's, so
 // every table address is last step's too, and the role keeps the values it read then (LongCorners / LatCorners below).
-struct QuadCell { int ja, jb, jd; double x0, x1; };
-F16_DEV QuadCell quad_cell_none() { QuadCell c; c.ja = c.jb = c.jd = 0; c.x0 = c.x1 = __builtin_nan(""); return c; }
+// What the cell fixes stays with the cell: rw, the refined reciprocal of its width (F16_FAST_DIV: the f16_rcp of br_axis, taken
+// on the miss path where x0 and x1 are read).  On a hit lambda = (v - x0) * rw: the same product as br_axis's, without its
+// `v == x1` guard, which a hit (v < x1) cannot meet; the miss path keeps the guard.  The strict build divides, in br_axis.
+struct QuadCell { int ja, jb, jd; double x0, x1, rw; };
+F16_DEV QuadCell quad_cell_none() { QuadCell c; c.ja = c.jb = c.jd = 0; c.x0 = c.x1 = __builtin_nan(""); c.rw = 0; return c; }
 template <bool USE_D2, bool CACHE, typename TP>
 F16_DEV QuadBr quad_br_cached(TP T, double alpha, double beta, double el, int s, unsigned flags, QuadCell &cc, bool &hit) {
   const double v = s == 0 ? alpha : (s == 1 ? beta : el);
-  const bool in = cc.x0 <= v && v < cc.x1;
   QuadBr q;
-  hit = CACHE && !(flags & FLAG_NO_CELL_CACHE) && __builtin_amdgcn_ballot_w64(!in) == 0;   // wave-uniform
+  q.l = 0;
+  if constexpr (CACHE) {
+    // every lane inside its cell: the two compares' lane masks themselves (all 64 lanes are live here: a ragged tail shadows)
+    // F16_FLAG_NO_CELL_CACHE clears the mask (uniform over the launch): one scalar compare decides, wave-uniform
+    const unsigned long long keep = (flags & FLAG_NO_CELL_CACHE) ? 0ull : ~0ull;
+    const auto inside = __builtin_amdgcn_ballot_w64(cc.x0 <= v) & __builtin_amdgcn_ballot_w64(v < cc.x1) & keep;
+    hit = inside == __builtin_amdgcn_ballot_w64(true);
+  } else
+    hit = false;
   if (hit) {
     q.c.j = 0; q.c.v = v; q.c.x0 = cc.x0; q.c.x1 = cc.x1;                          // (br_axis's j is not used by the quads)
     q.ja = cc.ja; q.jb = cc.jb; q.jd = cc.jd;
     q.offa = q.offb = q.offd = false;
+#ifdef F16_FAST_DIV
+    q.l = (v - cc.x0) * cc.rw;
+#endif
   } else {
     int nX; double vX;
     const BrRaw rx = quad_br_load<USE_D2>(T, alpha, beta, el, s, nX, vX);
     F16_PHASE();
     q = quad_br_cells(rx, nX, vX);
-    if (CACHE) { cc.ja = q.ja; cc.jb = q.jb; cc.jd = q.jd; cc.x0 = q.c.x0; cc.x1 = q.c.x1; }
+    if (CACHE) {
+      cc.ja = q.ja; cc.jb = q.jb; cc.jd = q.jd; cc.x0 = q.c.x0; cc.x1 = q.c.x1;
+#ifdef F16_FAST_DIV
+      cc.rw = f16_rcp(q.c.x1 - q.c.x0);
+      q.l = q.c.v == q.c.x1 ? 1.0 : (q.c.v - q.c.x0) * cc.rw;                   // (br_axis, with the reciprocal kept)
+#endif
+    }
   }
   return q;
 }
+template <bool CACHE>
 F16_DEV void quad_br_axes(const QuadBr &q, Axis &a, Axis &b, Axis &d) {
-  const Axis own = br_axis(q.c);                                  // one division per lane
+  Axis own;
+#ifdef F16_FAST_DIV
+  if constexpr (CACHE) {
+    own.j = q.c.j; own.l = q.l;
+    quad_taken_here(own.l);       // (rounded as br_axis rounds it behind its select: without the guard `1 - l` would fuse with the hit's product)
+    own.m = 1 - own.l;
+  } else
+    own = br_axis(q.c);
+#else
+  own = br_axis(q.c);                                             // one division per lane
+#endif
   a.j = q.ja; a.l = quad_bcast<0>(own.l); a.m = quad_bcast<0>(own.m);
   b.j = q.jb; b.l = quad_bcast<1>(own.l); b.m = quad_bcast<1>(own.m);
   d.j = q.jd; d.l = quad_bcast<2>(own.l); d.m = quad_bcast<2>(own.m);
@@ -193,16 +225,17 @@ F16_DEV double quad_long(TP T, const double *xu, int s, double xcg, unsigned fla
     const int ir = k == 0 ? 1 : (k == 1 ? 7 : 4), ib = k == 1 ? 9 : 10;     // CYr CYp | CNr CNp | CLr CLp; dCNbeta, dCLbeta
     c.r0 = g[ir]; c.r1 = g[S_G1A + ir]; c.p0 = g[ir + 1]; c.p1 = g[S_G1A + ir + 1]; c.b0 = g[ib]; c.b1 = g[S_G1A + ib];
     c.hr0 = h[ir]; c.hr1 = h[S_G1B + ir]; c.hp0 = h[ir + 1]; c.hp1 = h[S_G1B + ir + 1];
+    // (the off-grid bits with the lookup that finds them: a hit has every lane inside its cell, on the grid)
+    if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
+    if (qb.offb) status |= ST_BETA;
+    if (qb.offd) status |= ST_EL;
   }
-  if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
-  if (qb.offb) status |= ST_BETA;
-  if (qb.offd) status |= ST_EL;
   if (hi_a && in.alpha > c.a45) status |= ST_ALPHA2;
   Q2STAMP(2)
   F16_PHASE();
   // (3) arithmetic
   Axis a1, b, d1;
-  quad_br_axes(qb, a1, b, d1);
+  quad_br_axes<CACHE>(qb, a1, b, d1);
   Axis a2 = a1;
   if (hi_a) { a2.j = N_A2 - 2; a2.l = 1.0; a2.m = 0.0; }
   const W4 W1 = bil_weights(a1, b), W2 = bil_weights(a2, b);
@@ -251,15 +284,16 @@ F16_DEV double quad_lat(TP T, const double *xu, int s, unsigned flags, QuadCell 
     constexpr int SAB = S_G2B, SBB = S_G2B * N_A2;
     TP pb = T + OFF_G2B + n2 * SAB;
     c.ql = ld4(pb + 3 + k, SAB, SBB); c.qal = ld4(pb + 6 + k, SAB, SBB);
+    // (the off-grid bits with the lookup that finds them: a hit has every lane inside its cell, on the grid)
+    if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
+    if (qb.offb) status |= ST_BETA;
+    if (qb.offd) status |= ST_EL;
   }
-  if (qb.offa) status |= ST_ALPHA1 | ST_ALPHA2;
-  if (qb.offb) status |= ST_BETA;
-  if (qb.offd) status |= ST_EL;
   if (hi_a && in.alpha > c.a45) status |= ST_ALPHA2;
   F16_PHASE();
   // (3) arithmetic
   Axis a1, b, d2;
-  quad_br_axes(qb, a1, b, d2);
+  quad_br_axes<CACHE>(qb, a1, b, d2);
   Axis a2 = a1;
   if (hi_a) { a2.j = N_A2 - 2; a2.l = 1.0; a2.m = 0.0; }
   const W4 W1 = bil_weights(a1, b), W2 = bil_weights(a2, b);

@@ -1,15 +1,16 @@
 // f16_quad_steps.inc -- the step loop of k_rollout_q (f16_dynamics.hip), included there once per role and once for all roles.
-// `wave` is defined by the including scope: a compile-time constant 0..3 in a role's own loop (GROUPS = 1: every `if (wave == ...)`
+// `wave` is defined by the including scope: a compile-time constant 0..4 in a role's own loop (GROUPS = 1: every `if (wave == ...)`
 // below is resolved then, and that copy keeps the statements, the published states and the loop-carried registers of its role
-// alone), the wave's role index itself in the shared loop (GROUPS = 2).  Every copy executes the same barriers: A and B per step,
-// A alone on the extra trip.  Text, not a function: the shared loop then compiles exactly as it did inside the kernel.
+// alone; 4 is the store wave, which reads the sample behind barrier A, stores it when one is due and does nothing else), the
+// wave's role index 0..3 itself in the shared loop (GROUPS = 2, where wave 2 stores the samples).  Every copy executes the same
+// barriers: A and B per step, A alone on the extra trip.  Text, not a function: the shared loop then compiles exactly as it did inside the kernel.
 // GROUPS = 1, in front of a role's loop: the role's constants (QUAD_K, f16_plant.hpp) are loaded HERE, once per launch and group of
 // aircraft, and stay in registers across the loop -- wave 2 and wave 0 the sin/cos table, wave 3 the exp / log table; no step
 // loads them again.  Wave 0 evaluates the first step's psi with that table (the form of the loop: on a NaN psi the literal form
 // differs in the sign of the NaN, and a continued rollout must give the bits of one launch).  Wave 2 publishes x[0..5] and tests
 // x[2] for the first trip; from then on it does both where these states become final, behind barrier B (below).  Wave 3 evaluates
-// the altitude part of the first step's atmosphere and the quotient of its log (atmos_alt, log_k_quot) from the x[2] it loaded;
-// from then on behind barrier B, from the altitude wave 2 hands over beside psi (xpsi[3]) -- half a step ahead of their use.
+// the altitude part of the first step's atmosphere, the quotient of its log and the log's polynomial (atmos_alt, log_k_quot,
+// log_k_poly) from the x[2] it loaded; from then on behind barrier B, from the altitude wave 2 hands over beside psi (xpsi[3]) -- half a step ahead of their use.
 // GROUPS = 1, behind barrier A: a wave takes the states it owns from its registers, not from the published copy (wave 2 the angles
 // of its sin / cos polynomial and the airspeed, wave 1 its P, Q, R).
     [[maybe_unused]] SinCosK ksc = {};
@@ -17,12 +18,13 @@
     [[maybe_unused]] bool env_h = false;                   // wave 2: x[2] outside its box, tested where x[2] was last advanced
     [[maybe_unused]] AtmosAlt ah = {};                    // wave 3: the altitude part of the coming step's atmosphere (atmos_alt) ...
     [[maybe_unused]] LogQuot lq = {};                      //         ... and the quotient of log tfac (log_k_quot), taken half a step ahead
+    [[maybe_unused]] LogPoly lp = {};                      //         ... and the log's polynomial in that quotient (log_k_poly), with it
     if constexpr (G1) {
       if (wave == 0 || wave == 2) ksc = reloaded(QUAD_K.sc);
       if (wave == 3) kpw = reloaded(QUAD_K.pw);
       // operand class (f16_plant.hpp): waves 0 and 3 keep the table in scalar registers (KScalar) and only the two Horner start
-      // coefficients, vector operands of their FMA, in vector registers; wave 2's loop has no scalar registers for 42 more (its lane
-      // masks and the sample's scalars went out into lane moves), so its whole table stays in lane-uniform vector registers (KVector)
+      // coefficients, vector operands of their FMA, in vector registers; wave 2's whole table stays in lane-uniform vector registers
+      // (KVector: chosen when its loop had no scalar registers for 42 more; the scalar form since the sample left this wave: DESIGN.md)
       if (wave == 2) table_in_vgprs(ksc);
       if (wave == 0) { in_vgpr(ksc.S[7]); in_vgpr(ksc.C[8]); }
       if (wave == 3) { in_vgpr(kpw.E[0]); in_vgpr(kpw.L[0]); }
@@ -41,7 +43,8 @@
       if (wave == 3) {                                     // the first step's altitude part, in the form of the loop (second half, below)
         ah = atmos_alt(x[2]);
         lq = log_k_quot(kpw, ah.tfac);
-        quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e);
+        lp = log_k_poly(kpw, lq);
+        quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e, lp.z, lp.c);
       }
       // The states a role neither owns nor reads are dead from here on: the epilogue writes back a role's own states only, but it
       // stands behind the join of the four loops, where the compiler no longer knows the role, and kept all 18 in registers across
@@ -86,14 +89,14 @@
       QSTAMP(tD)
       __syncthreads();
       QSTAMP(tA)
-      // trajectory sample of the step that just finished: all 18 states straight from the published copy, by the wave
-      // with the most slack in the first half (wave 2 since the actuator wave became the longest; sub-lane s stores states
-      // s, s+4, s+8, ...)
+      // trajectory sample of the step that just finished: all 18 states straight from the published copy (sub-lane s stores states
+      // s, s+4, s+8, ...) -- GROUPS = 2 by wave 2, GROUPS = 1 by the store wave (4), which owns tr, until_store and sample_due
       // GROUPS = 1: a wave takes the states it owns from its registers (xs[k] is a copy of x[k], for a frozen aircraft and on the
       // first trip too) -- wave 2 x[3], x[4], x[6..8], so that its sin / cos polynomial starts without an LDS round trip, wave 1 its
-      // P, Q, R -- and reads the rest from the published copy.  The sample's five reads are issued with the step inputs,
+      // P, Q, R -- and reads the rest from the published copy.  The store wave issues the sample's five reads behind barrier A,
       // every trip (fenced there, or the compiler moves them into the branch that stores them and splits them round the first four
-      // stores: a second round trip), and its stores stand UNDER that polynomial; on the extra trip on the way out of the loop.
+      // stores: a second round trip); they have landed before barrier B, behind which wave 2 rewrites x[0..5].  On the extra trip the
+      // sample is stored on the way out of the loop.
       double xa[17];
       int env_any = 0;
       if constexpr (G1) {
@@ -103,19 +106,19 @@
         if (wave == 2) { xa[3] = x[3]; xa[4] = x[4]; xa[6] = x[6]; xa[7] = x[7]; xa[8] = x[8]; }
         if (wave == 1) { xa[9] = x[9]; xa[10] = x[10]; xa[11] = x[11]; }
       }
-      [[maybe_unused]] double smp[5] = {0, 0, 0, 0, 0};    // GROUPS = 1, wave 2: read with the step inputs, whether or not a sample is due
+      [[maybe_unused]] double smp[5] = {0, 0, 0, 0, 0};    // GROUPS = 1, store wave: read behind barrier A, whether or not a sample is due
       [[maybe_unused]] bool sample_due = false;
       if constexpr (G1) {
-        if (wave == 2) {
+        if (wave == 4) {
 #pragma unroll
           for (int j = 0; j < 5; ++j) smp[j] = xs[s + 4 * j < 18 ? s + 4 * j : s][ac];
           asm volatile("" ::: "memory");                   // (read HERE: no load moves behind this, into the branch that stores them)
         }
       }
-      if (wave == 2 && tr && t > 0 && --until_store == 0) {
+      if (wave == (G1 ? 4 : 2) && tr && t > 0 && --until_store == 0) {
         until_store = a.traj_every;
         if constexpr (G1) {
-          sample_due = true;                               // (stored under the sin / cos polynomial below, on the extra trip on the way out)
+          sample_due = true;                               // (stored in the store wave's first half below, on the extra trip on the way out)
         } else {
           if (valid) {
 #pragma unroll
@@ -138,7 +141,8 @@
 #pragma unroll
         for (int k = 0; k < 17; ++k) xa[k] = xs[k][ac];
       }
-      if ((!G1 || wave != 0) && env_any) st |= ST_ENVELOPE;   // (a wave 0 with a loop of its own reads no flag: it reports no status)
+      // (a wave 0 with a loop of its own reads no flag: it reports no status; nor does the store wave)
+      if ((!G1 || (wave != 0 && wave != 4)) && env_any) st |= ST_ENVELOPE;
       const bool live = !(st & ST_ENVELOPE);
       // first-half results wave 2 keeps in registers for the second half
       double xd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -180,12 +184,6 @@
         double sn, cs, sb, s_psi, c_psi;
         if constexpr (G1) F16_SINCOS_KC(KVector, ksc, ang, &sn, &cs);   // (the table loaded in front of the loop, into vector registers)
         else F16_SINCOS(ang, &sn, &cs);
-        if constexpr (G1) {                                // (under the polynomial: its angles come from registers, the sample from LDS)
-          if (sample_due) {
-            if (valid) quad_store_sample(smp, tr, s, a.ld);
-            tr += 18 * a.ld;
-          }
-        }
         // (keep this statement order: the FMA contraction of the navigation sums below follows it, and another order
         //  changes x[1] in the last place)
         if constexpr (G1) { sb = quad_bcast<2>(sn); cb = quad_bcast<2>(cs); } else F16_SINCOS(xa[8], &sb, &cb);
@@ -236,6 +234,12 @@
         //  half uses -- the three reciprocals, fu0 .. fw0 -- behind barrier B, into the half this wave sets the pace of, and
         //  contracts it with the force equations there: other last bits)
         if constexpr (G1) quad_taken_here(U, V, W, vtc, r1, r2, r3, fu0, fv0, fw0);
+      } else if (G1 && wave == 4) {
+        // the store wave: the sample it read behind barrier A, and nothing else up to barrier B
+        if (sample_due) {
+          if (valid) quad_store_sample(smp, tr, s, a.ld);
+          tr += 18 * a.ld;
+        }
       } else {
         double vt = xa[6];
         if (vt <= 0.01) vt = 0.01;
@@ -245,8 +249,8 @@
           // the altitude part (ah) and the quotient of the log (lq) were evaluated behind barrier B of the last step: what is left
           // needs no LDS read up to the density and runs under the wait for x[6], x[7]; only qbar takes this step's airspeed.
           // (pinned behind barrier A too: the compiler moved the rest of the chain in front of it, into the half wave 3 then paced)
-          quad_taken_here(ah.tfac, lq.h, lq.l, lq.e);
-          pw = exp_k(kpw, 0.14 * log_k_sum(kpw, ah.tfac, lq));   // (the table loaded in front of the loop)
+          quad_taken_here(ah.tfac, lq.h, lq.l, lq.e, lp.z, lp.c);
+          pw = exp_k(kpw, 0.14 * log_k_tail(kpw, ah.tfac, lq, lp));   // (the table loaded in front of the loop)
           atmos_air(ah, vt, mach, qbar, ps, [pw](double) { return pw; });
         } else
           atmos_dev(xa[2], vt, mach, qbar, ps);
@@ -353,7 +357,8 @@
           // (the extra trip evaluates a log nobody uses).  Pinned here: what crosses barrier A is three values, not the chain.
           ah = atmos_alt(xpsi[3][ac]);
           lq = log_k_quot(kpw, ah.tfac);
-          quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e);
+          lp = log_k_poly(kpw, lq);                        // (the log's polynomial needs the quotient alone: with it, in the half with slack)
+          quad_taken_here(ah.tfac, ah.temp, ah.t4, lq.h, lq.l, lq.e, lp.z, lp.c);
         }
       }
     }

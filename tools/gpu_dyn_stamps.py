@@ -13,8 +13,10 @@ env = F16Batch(x0, u0)
 T = 1000
 traj = env.rollout(T, traj_every=1)
 torch.cuda.synchronize()
-d = traj[2].reshape(-1)[:16].cpu().numpy().reshape(4, 4) / T
+flat = traj[2].reshape(-1)
+# (the store wave's row stands in state row 2 of the sample: with a library that has no store wave it reads that row's states)
+d = torch.cat((flat[:16], flat[2 * B:2 * B + 4])).cpu().numpy().reshape(5, 4) / T
 np.set_printoptions(linewidth=200, precision=0, suppress=True)
-print("cycles per step; rows = waves (long, lat, trig/forces, atmos/act); cols = second half+publish, barrier A, first half, barrier B")
+print("cycles per step; rows = waves (long, lat, trig/forces, atmos/act, sample stores); cols = second half+publish, barrier A, first half, barrier B")
 print(d, d.sum(1))
-print("cycles from kernel entry to the first barrier (table staging), per wave:", traj[2].reshape(-1)[B:B + 4].cpu().numpy())
+print("cycles from kernel entry to the first barrier (table staging), per wave:", traj[2].reshape(-1)[B:B + 5].cpu().numpy())

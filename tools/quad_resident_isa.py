@@ -1,9 +1,12 @@
-"""The four role loops of every k_rollout_q<1,*> in the compiler's ISA: what a step still loads, moves and publishes (no GPU needed).
+"""The role loops of every k_rollout_q<1,*> in the compiler's ISA -- the four roles of a step and the wave that stores the samples:
+what a step still loads, moves and publishes (no GPU needed).
 usage: python tools/quad_resident_isa.py PARENT_TREE [HEAD_TREE]     (checkouts of the two commits; HEAD_TREE defaults to this one)
    or: python tools/quad_resident_isa.py --asm parent.s parent.remarks head.s head.remarks     (listings + stderr of
        hipcc ... -S --cuda-device-only -Rpass-analysis=kernel-resource-usage, the flags of tools/quad_role_loops.py)
    or: python tools/quad_resident_isa.py --so f16_mpc_oop_py_amd/libf16hip.so       (the BUILT library: its gfx950 code object is
-       unbundled and disassembled; prints, per role loop, scalar loads and s_barrier only -- what tests/test_quad_resident_isa.py reads)
+       unbundled and disassembled; prints, per role loop, scalar loads and s_barrier only -- what tests/test_quad_resident_isa.py
+       reads: sixteen `wave N` lines for the four roles of a step; the store wave's loop is reported on a line of another form and
+       gated the same way: one loop, no scalar load, two barriers, no fp64 arithmetic)
 Two listings: prints
   (1) every function of the file compared between the two (comments and directives dropped): which ones differ;
   (2) VGPRs, AGPRs, scratch of every k_rollout_q instantiation;
@@ -15,9 +18,24 @@ Two listings: prints
       inline constants and operand modifiers -- neg, abs, clamp, omod -- are part of the node) and the multisets of trees compared;
       LDS reads per loop are listed with the counts;
   (4) wave 2: ds_write* between its last fp64 instruction of the second half and barrier A.
+  (5) the store wave's loop of the head (the parent may have none): one per instantiation, no scalar load, two s_barrier, no fp64
+      arithmetic, its global stores.
 Exit status 1 if the gate fails: a scalar load in a role loop of the head; more lane moves, v_accvgpr_*, 64-bit moves or scratch
-in a loop than before; scratch in a <1,*> instantiation; fp64 trees that differ; more than three ds_write* in (4); barriers
-other than two per loop; any function outside k_rollout_q<1,*> that differs."""
+in a loop than before; scratch in a <1,*> instantiation; fp64 trees that differ in any of the four loops of a step; more than
+three ds_write* in (4); barriers other than two per loop; a store loop that fails (5); any function outside k_rollout_q<1,*> that
+differs.
+A canonicalisation, `v_max_f64 d, x, x`, is the identity on every value but a signalling NaN: the evaluator follows it like a move
+(of a leaf it makes a leaf) and it is no tree of its own; they are counted apart.  Where the compiler hoists one out of a loop or
+leaves it inside, the trees stay the same.
+Differences a change has BY DESIGN are named on the command line, never in this file (default: none, and then every gate above is
+the strict one):
+  --named ROLE:SIDE:TREE   one tree that only SIDE (before | after) has in the loop of ROLE (0..3), in the form the tool prints for
+                           unmatched trees, e.g. `v_mul_f64(L;v_add_f64(L;neg L))` (a trailing `...`: any tree that starts so);
+                           taken out of the comparison once per
+                           instantiation, and it is an error if it is not there.  What is left must be identical.
+  --more INST:ROLE:KEY:N   the loop of ROLE in instantiation INST (`1,0,0` ...; `*`: all) may have N more `lane moves` or
+                           `64-bit moves` than before.
+The record of a change (profiles/*_isa.txt) starts with the command line that made it."""
 import collections, hashlib, os, re, subprocess, sys, tempfile
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-DF16_FAST_TAN", "-DF16_FAST_POW",
@@ -25,9 +43,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 HERE = os.path.dirname(os.path.abspath(__file__))
 LLVM = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")))), "llvm", "bin")
 FP64 = re.compile(r"v_(fma|fmac|mul|add|max|min|rcp|rsq|sqrt|div_scale|div_fmas|div_fixup|ldexp|frexp\w*|fract|floor|ceil|rndne|trunc)_f64")
-ROLES = ["wave 0 longitudinal tables, psi", "wave 1 lateral tables, moments", "wave 2 trigonometry, forces, sample", "wave 3 atmosphere, actuators"]
+ROLES = ["wave 0 longitudinal tables, psi", "wave 1 lateral tables, moments", "wave 2 trigonometry, forces", "wave 3 atmosphere, actuators",
+         "wave 4 sample stores"]
 NAMES = {}          # tree -> the instruction at its root (for the listing of unmatched trees)
-KEYS = ["instructions", "LDS reads", "s_load", "lane moves", "v_accvgpr", "64-bit moves", "scratch", "s_barrier", "fp64"]
+KEYS = ["instructions", "LDS reads", "s_load", "lane moves", "v_accvgpr", "64-bit moves", "scratch", "s_barrier", "fp64", "canonicalisations"]
+EXPR = {}           # tree -> its readable form
 
 
 def listing(tree):
@@ -176,16 +196,25 @@ def step_loops(bl):
 def role_of(blocks):
     ops = [i.split()[0] for b in blocks for i in b["ins"]]
     if any(o.startswith(("v_log_f32", "v_exp_f32", "v_ldexp_f64")) for o in ops): return 3
-    if any(o.startswith("global_store") for o in ops): return 2
+    # the store wave: the sample's stores and no fp64 arithmetic at all (before it existed the stores stood in wave 2's loop)
+    if any(o.startswith("global_store") for o in ops) and not any(FP64.match(o) for o in ops): return 4
+    # the table waves clamp a breakpoint guess and form table addresses (their miss path); wave 2 does neither
+    if not any(o.startswith(("v_max_i32", "v_mad_u64_u32")) for o in ops): return 2
     return 0 if any(o.startswith("v_rndne_f64") for o in ops) else 1
+
+
+def canonicalisation(ins):
+    m = re.match(r"v_max_f64\S*\s+\S+,\s*(\S+),\s*(\S+)$", ins)
+    return bool(m) and m.group(1) == m.group(2)
 
 
 def count(blocks):
     ops = [i.split()[0] for b in blocks for i in b["ins"]]
-    return {"instructions": len(ops), "LDS reads": sum(o.startswith("ds_read") for o in ops), "s_load": sum(o.startswith(("s_load", "s_buffer_load")) for o in ops),
+    canon = sum(canonicalisation(i) for b in blocks for i in b["ins"])
+    return {"canonicalisations": canon, "global stores": sum(o.startswith("global_store") for o in ops),"instructions": len(ops), "LDS reads": sum(o.startswith("ds_read") for o in ops), "s_load": sum(o.startswith(("s_load", "s_buffer_load")) for o in ops),
             "lane moves": sum(o.startswith(("v_readlane", "v_writelane", "v_readfirstlane")) for o in ops),
             "v_accvgpr": sum(o.startswith("v_accvgpr") for o in ops), "64-bit moves": sum(o.startswith(("v_mov_b64", "v_pk_mov_b32")) for o in ops),
-            "scratch": sum(o.startswith("scratch_") for o in ops), "s_barrier": ops.count("s_barrier"), "fp64": sum(bool(FP64.match(o)) for o in ops)}
+            "scratch": sum(o.startswith("scratch_") for o in ops), "s_barrier": ops.count("s_barrier"), "fp64": sum(bool(FP64.match(o)) for o in ops) - canon}
 
 
 def regs(tok):
@@ -220,6 +249,16 @@ def trees(blocks):
             flags = toks[-1].split()[1:] if " " in toks[-1] else []
             toks[-1] = toks[-1].split()[0]
             dst = regs(toks[0])
+            if canonicalisation(ins) and dst:
+                # the identity: the tree of the source (a leaf stays a leaf; a negated tree is a node of its own, not counted)
+                t = operand(toks[1])
+                if t.split(" ")[-1] == "L":
+                    for x in dst: val.pop(x, None)
+                else:
+                    e = t if re.fullmatch(r"[0-9a-f]{16}", t) else h("canon(" + t + ")")
+                    if e not in EXPR: EXPR[e] = "canon(" + " ".join(EXPR.get(w, w) for w in t.split(" ")) + ")"
+                    for k, x in enumerate(dst): val[x] = (e, k)
+                continue
             if FP64.match(op):
                 src = toks[1:]
                 if op.startswith("v_div_scale"): src = toks[2:]                 # (a second, scalar destination)
@@ -231,6 +270,7 @@ def trees(blocks):
                 e = h(name + "(" + ";".join(args) + ")" + " ".join(sorted(flags)))
                 out[e] += 1
                 NAMES[e] = name
+                EXPR[e] = name + "(" + ";".join(" ".join(EXPR.get(w, w) for w in x.split(" ")) for x in args) + ")" + "".join(" " + f for f in sorted(flags))
                 if dst:
                     for k, x in enumerate(dst): val[x] = (e, k)
             elif dst is not None:
@@ -300,6 +340,18 @@ def role_loops(bl):
 
 
 a = sys.argv[1:]
+NAMED_TREES, MORE = [], {}
+while "--named" in a or "--more" in a:
+    i = min(a.index(x) for x in ("--named", "--more") if x in a)
+    if a[i] == "--named":
+        role, side, expr = a[i + 1].split(":", 2)
+        assert side in ("before", "after"), side
+        NAMED_TREES.append((int(role), side, expr))
+    else:
+        inst, role, key, n = a[i + 1].split(":")
+        MORE[(inst, int(role), key)] = int(n)
+    del a[i:i + 2]
+more = lambda inst, r, k: MORE.get((inst, r, k), MORE.get(("*", r, k), 0))
 if a[:1] == ["--so"]:
     ok = True
     fns = code_object_functions(a[1])
@@ -309,7 +361,7 @@ if a[:1] == ["--so"]:
     for n in names:
         q = re.match(r"_ZN3f1611k_rollout_qILi1ELb(\d)ELb(\d)E", n)
         rl = role_loops(fns[n])
-        if sorted(rl) != [0, 1, 2, 3] or any(len(v) != 1 for v in rl.values()):
+        if sorted(rl) != [0, 1, 2, 3, 4] or any(len(v) != 1 for v in rl.values()):
             print(f"k_rollout_q<1,{q.group(1)},{q.group(2)}>: step loops per role {dict((k, len(v)) for k, v in rl.items())}: NOT ONE PER ROLE"); ok = False
             continue
         for r in range(4):
@@ -317,6 +369,11 @@ if a[:1] == ["--so"]:
             good = c["s_load"] == 0 and c["s_barrier"] == 2
             ok &= good
             print(f"k_rollout_q<1,{q.group(1)},{q.group(2)}> {ROLES[r]}: s_load {c['s_load']} s_barrier {c['s_barrier']}{'' if good else '  FAIL'}")
+        c = count(rl[4][0])
+        good = c["s_load"] == 0 and c["s_barrier"] == 2 and c["fp64"] == 0 and c["global stores"] > 0
+        ok &= good
+        print(f"    store loop of <1,{q.group(1)},{q.group(2)}>: scalar loads {c['s_load']}, barriers {c['s_barrier']}, fp64 {c['fp64']}, "
+              f"global stores {c['global stores']}{'' if good else '  FAIL'}")
     print("PASS" if ok else "FAIL")
     sys.exit(0 if ok else 1)
 if a[:1] == ["--asm"]:
@@ -326,6 +383,7 @@ else:
     ht, hr = listing(a[1] if len(a) > 1 else os.path.join(HERE, ".."))
 
 ok = True
+print("python tools/quad_resident_isa.py " + " ".join(x if re.fullmatch(r"[\w./,:=-]+", x) else "'" + x + "'" for x in sys.argv[1:]))
 pf, hf = functions(pt), functions(ht)
 diff = [n for n in pf if n in hf and pf[n] != hf[n]]
 only = sorted(set(pf) ^ set(hf))
@@ -349,6 +407,7 @@ for n in hf:
     q = re.match(r"_ZN3f1611k_rollout_qILi1ELb(\d)ELb(\d)E", n)
     if not q or n not in pf: continue
     lp, lh = role_loops(blocks_of_listing(pt, n)), role_loops(blocks_of_listing(ht, n))
+    inst = f"1,{q.group(1)},{q.group(2)}"
     for r in range(4):
         tag = f"<1,{q.group(1)},{q.group(2)}> {ROLES[r]}"
         if len(lp.get(r, [])) != 1 or len(lh.get(r, [])) != 1:
@@ -356,20 +415,40 @@ for n in hf:
             continue
         cp, ch = count(lp[r][0]), count(lh[r][0])
         tp, th = trees(lp[r][0]), trees(lh[r][0])
-        same = tp == th
-        fails = []
+        only_p, only_h = tp - th, th - tp
+        fails, named = [], []
+        for role, side, expr in NAMED_TREES:
+            if role != r: continue
+            c = only_p if side == "before" else only_h
+            e = next((e for e in c if (EXPR[e].startswith(expr[:-3]) if expr.endswith("...") else EXPR[e] == expr)), None)
+            if e is None: fails.append(f"named tree not among the {side}-only trees: {expr}")
+            else:
+                c[e] -= 1
+                if not c[e]: del c[e]
+                named.append(f"{side} only: {expr}")
+        same = not only_p and not only_h
         if ch["s_load"]: fails.append("scalar loads in the loop")
         for k in ("lane moves", "v_accvgpr", "64-bit moves", "scratch"):
-            if ch[k] > cp[k]: fails.append(f"more {k}")
+            if ch[k] > cp[k] + more(inst, r, k): fails.append(f"more {k}")
         if ch["s_barrier"] != 2: fails.append("barriers")
-        if not same or cp["fp64"] != ch["fp64"]: fails.append("fp64 trees differ")
+        if not same: fails.append("fp64 trees differ")
         ok &= not fails
         print(f"    {tag}: " + ", ".join(f"{k} {cp[k]} -> {ch[k]}" for k in KEYS)
-              + f"; fp64 trees {'identical' if same else f'DIFFER ({sum(((tp - th) + (th - tp)).values())} unmatched)'}" + (f"  FAIL: {'; '.join(fails)}" if fails else ""))
-        if not same:
-            roots = lambda c: dict(collections.Counter(NAMES[e] for e in c.elements()))
-            print(f"      roots of the unmatched trees, before only: {roots(tp - th)}; after only: {roots(th - tp)}")
-    fp, fh = sum(count(lp[r][0])["fp64"] for r in lp), sum(count(lh[r][0])["fp64"] for r in lh)
+              + f"; fp64 trees {'identical' if same else f'DIFFER ({sum((only_p + only_h).values())} unmatched)'}"
+              + (f" apart from {len(named)} named" if named else "") + (f"  FAIL: {'; '.join(fails)}" if fails else ""))
+        for nm in named: print(f"      named, {nm}")
+        for side, c in (("before", only_p), ("after", only_h)):
+            for e in sorted(c.elements(), key=lambda e: EXPR[e]): print(f"      unmatched, {side} only: {EXPR[e][:400]}")
+    st = lh.get(4, [])
+    if len(st) != 1:
+        print(f"(5) <1,{q.group(1)},{q.group(2)}> store loops found: {len(st)}  FAIL"); ok = False
+    else:
+        c = count(st[0])
+        good = c["s_load"] == 0 and c["s_barrier"] == 2 and c["fp64"] == 0 and c["global stores"] > 0
+        ok &= good
+        print(f"(5) <1,{q.group(1)},{q.group(2)}> store loop: " + ", ".join(f"{k} {c[k]}" for k in ("instructions", "LDS reads", "s_load", "lane moves", "scratch", "s_barrier", "fp64", "global stores"))
+              + ("" if good else "  FAIL"))
+    fp, fh = sum(count(lp[r][0])["fp64"] for r in lp if r < 4), sum(count(lh[r][0])["fp64"] for r in lh if r < 4)
     wp, wh = publish_writes(lp[2][0]) if 2 in lp else None, publish_writes(lh[2][0]) if 2 in lh else None
     good = wh is not None and wh <= 3
     ok &= good

@@ -1,4 +1,5 @@
-"""Structure of the quad rollout's step loops in the compiler's ISA (product flags; no GPU needed): one loop per role wave.
+"""Structure of the quad rollout's step loops in the compiler's ISA (product flags; no GPU needed): one loop per role wave -- the
+four roles of a step and the wave that stores the samples.
 usage: python tools/quad_role_loops.py [--asm listing.s] [extra hipcc flags ...]
 For every k_rollout_q instantiation, from the control-flow graph of its listing:
   (a) the role dispatch -- every conditional branch, outside the step loops, whose two sides lead to different step loops -- must be
@@ -7,7 +8,7 @@ For every k_rollout_q instantiation, from the control-flow graph of its listing:
       the barrier counts of the four waves would come apart and the workgroup would hang.  Where the compiler joins two roles'
       paths and parts them again, it carries the outcome of the s_cmp in a scalar register pair and branches on `vcc = exec & pair`
       (or on EXEC itself, one way only): accepted while nothing in front of the branch writes EXEC, listed with the rest;
-  (b) the number of s_barrier in each role's step loop, which must be the same in all four (two: A and B);
+  (b) the number of s_barrier in each role's step loop, which must be the same in all five (two: A and B);
   (c) per step loop: instructions, branch instructions (every one a candidate for a taken jump), lane-mask (EXEC) operations, lane
       moves (v_readlane / v_writelane / v_readfirstlane: spilled scalar registers), scalar moves (literals rebuilt), with the totals
       of the single shared loop of the commit before beside them (PARENT, counted by this script on that commit's listing).
@@ -117,7 +118,7 @@ for m in re.finditer(r"\n(_ZN3f1611k_rollout_qILi(\d)ELb(\d)ELb(\d)E\w*):[^\n]*\
             for s in b.succ:
                 if s in by and s not in outer: r |= reach[s]
             if r != reach[b.name]: reach[b.name], changed = r, True
-    if len(heads) == 4:
+    if len(heads) == 5:
         nscalar = 0
         for bi, b in enumerate(bl):
             if b.loop in loops: continue
@@ -154,8 +155,11 @@ for m in re.finditer(r"\n(_ZN3f1611k_rollout_qILi(\d)ELb(\d)ELb(\d)E\w*):[^\n]*\
         print(f"  (b) s_barrier per step loop: {[c['barrier'] for c in counts]}  {'equal' if same else 'NOT EQUAL'}")
         for h, c in zip(heads, counts):
             ops = [i.split()[0] for b in loops[h] for i in b.ins]
+            # marks as in tools/quad_resident_isa.py (role_of): the store wave has the sample's stores and no fp64 arithmetic, the
+            # table waves clamp a breakpoint guess and form table addresses
             role = ("atmosphere/actuators (wave 3)" if any(o.startswith(("v_log_f32", "v_exp_f32", "v_ldexp_f64")) for o in ops) else
-                    "trigonometry/forces (wave 2)" if any(o.startswith("global_store") for o in ops) else
+                    "sample stores (wave 4)" if any(o.startswith("global_store") for o in ops) and not any(re.match(r"v_\w+_f64", o) and not o.startswith("v_cmp") for o in ops) else
+                    "trigonometry/forces (wave 2)" if not any(o.startswith(("v_max_i32", "v_mad_u64_u32")) for o in ops) else
                     "longitudinal tables + psi (wave 0)" if any(o.startswith("v_rndne_f64") for o in ops) else "lateral tables/moments (wave 1)")
             pre = count([b for b in bl if b.loop not in loops and reach[b.name] == {h}])
             print(f"  (c) {h:9s} {row(c)}  [{role}; its first trip apart, outside the loop: {pre['all']} instructions, {pre['barrier']} s_barrier]")
@@ -170,7 +174,7 @@ for m in re.finditer(r"\n(_ZN3f1611k_rollout_qILi(\d)ELb(\d)ELb(\d)E\w*):[^\n]*\
         print(f"  (c) {heads[0]:9s} {row(c)}  [all four roles]")
     else:
         ok = False
-        print("  NEITHER ONE STEP LOOP NOR FOUR")
+        print("  NEITHER ONE STEP LOOP NOR FIVE")
 name, res = None, {}
 for l in remarks.split("\n"):
     f = re.search(r"Function Name: (\S+)", l)
