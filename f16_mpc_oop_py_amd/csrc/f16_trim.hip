@@ -11,8 +11,8 @@
 // evaluation of latency whatever branch scipy's rules then take; the decisions, the accepted coordinates and the
 // evaluation COUNT are those of the sequential algorithm (nfev counts what scipy would have evaluated).  The simplex is
 // replicated in the registers of the row's lanes (identical bookkeeping on every lane: no LDS, no synchronisation).
-// A condition that cannot be trimmed runs to the reference's maxiter = 50,000 iterations as scipy does: 50,000 evaluation
-// latencies (~0.15 s) instead of the ~350,000 of the one-evaluation-per-trip form this replaces.
+// A condition that cannot be trimmed runs to the reference's maxiter = 50,000 as scipy does (49,999 iterations: scipy's counter
+// starts at 1): as many evaluation latencies (~0.15 s) instead of the ~350,000 of the one-evaluation-per-trip form this replaces.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -78,7 +78,10 @@ __device__ __forceinline__ double row_get(double v, int src) {
   return __hiloint2double(hi, lo);
 }
 
-// stable sort of the six vertices by cost (numpy argsort on six elements: insertion sort, i.e. stable)
+// STABLE sort of the six vertices by cost: tied vertices keep their order.  scipy sorts with numpy's default argsort, on six
+// elements an insertion sort (stable) -- except on x86 hosts where numpy dispatches it to a vectorised sorting network, which is
+// not stable, so scipy's own order of exact ties depends on the host; the stable rule is the one held here (ties are exact only
+// where clipped commands give two vertices the same plant input; tests/trim_cases.py: THE TIE RULE)
 __device__ __forceinline__ void sort_simplex(double (&sim)[6][5], double (&fs)[6]) {
   int rank[6];
 #pragma unroll
@@ -133,7 +136,10 @@ __global__ __launch_bounds__(256) void k_trim(TrimArgs a) {
         if (p == k + 1) y = (y != 0.0) ? (1 + 0.05) * y : 0.00025;
         sim[p][k] = y;
       }
-    int iters = 0, nfev = 6, st = 0;
+    // scipy's counter: `iterations = 1` before the loop, `while iterations < maxiter`, += 1 after an iteration -- so iters is
+    // the iterations performed + 1 (scipy's nit), a launch performs at most maxiter - 1, and iters >= maxiter after the loop
+    // is scipy's status 2 (include/f16_hip.h states the rule)
+    int iters = 1, nfev = 6, st = 0;
     {
       double q[5];
 #pragma unroll
@@ -266,7 +272,7 @@ __global__ __launch_bounds__(256) void k_trim(TrimArgs a) {
         for (int k = 0; k < 5; ++k) same = same && (__double_as_longlong(sim[p][k]) == __double_as_longlong(sim_in[p][k]));
       }
       if (same && a.fast_forward) {
-        const int left = a.maxiter - iters;                   // (the termination test did not fire for this simplex and never will)
+        const int left = a.maxiter - iters;                   // scipy's loop would run while iters < maxiter (the termination test did not fire for this simplex and never will)
         nfev += left * (nfev - nfev_in);
         iters = a.maxiter;
       }

@@ -57,7 +57,10 @@ class F16Batch:
     @staticmethod
     def trim(h_t, v_t, *, stab_flag=None, xcg=None, fi_flag=P.fi_flag, device="cuda:0", flags=0, maxiter=50000, context=None):
         """Batched F16.trim: straight-and-level trim at altitudes h_t [B] (ft) and airspeeds v_t [B] (ft/s) by the
-        reference's Nelder-Mead, all conditions in one launch.  Returns (x_trim [B,18], info dict)."""
+        reference's Nelder-Mead, all conditions in one launch.  Returns (x_trim [B,18], info dict).
+        `maxiter` and info["iters"] are scipy's option `maxiter` and result `nit`: the counter starts at 1, so at most
+        maxiter - 1 iterations are performed, iters = performed + 1, and the F16_ST_QP_MAXITER bit of info["status"] is scipy's
+        status 2 (iters >= maxiter); info["nfev"] is scipy's nfev (include/f16_hip.h: f16_trim_batch)."""
         if not torch.cuda.is_available():
             raise _lib.F16HipError("trim needs an AMD GPU (no CPU fallback)")
         dev = torch.device(device)

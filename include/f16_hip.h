@@ -612,7 +612,15 @@ int f16_xdot_na_batch(f16_ctx *ctx, const double *x_full, const double *x9, cons
 /* ---- (2) batched trim ---------------------------------------------------- */
 /* env.py:198-292 F16.trim(h_t, v_t) for B flight conditions h[B], v[B] (device): the reference's Nelder-Mead
  * (scipy defaults, tol 1e-10, maxiter 5e4; initial guess env.py:265-271 unless h_x0[5] on the HOST is given)
- * -> x_trim[18][ld]; cost[B], iters[B], nfev[B], status[B] may be NULL. */
+ * -> x_trim[18][ld]; cost[B], iters[B], nfev[B], status[B] may be NULL.
+ *   The iteration count.  maxiter and iters mean what scipy's option `maxiter` and result `nit` mean: scipy's counter starts at
+ *     1, the loop runs `while iterations < maxiter` and adds 1 after every iteration.  So a call performs at most maxiter - 1
+ *     iterations, iters[b] = iterations performed + 1, and F16_ST_QP_MAXITER is set where scipy reports status 2: iters[b] >=
+ *     maxiter after the loop (also when the termination test would have held for that last simplex: the cap is tested first).
+ *     maxiter <= 0 stands for the reference's 50,000.  nfev[b] counts what the sequential algorithm evaluates: 6 for the initial
+ *     simplex, then 1 (reflection accepted), 2 (expansion or contraction tried) or 7 (shrink) per iteration.
+ *   status[b] is OR-ed into, never cleared: the caller zeroes it, and a bit that is already set survives the call.
+ *   Columns B .. ld - 1 of x_trim are not written. */
 int f16_trim_batch(f16_ctx *ctx, const double *h, const double *v, double *x_trim, double *cost, int32_t *iters,
                    int32_t *nfev, int32_t *status, long B, long ld, double xcg, int fi_flag, unsigned flags,
                    int maxiter, const double *h_x0, void *stream);
