@@ -55,12 +55,19 @@ class F16Batch:
 
     # ------------------------------------------------------------------ env.py:198-292
     @staticmethod
-    def trim(h_t, v_t, *, stab_flag=None, xcg=None, fi_flag=P.fi_flag, device="cuda:0", flags=0, maxiter=50000, context=None):
+    def trim(h_t, v_t, gamma=None, turn_rate=None, pullup_rate=None, runs=2, q0=None, *, stab_flag=None, xcg=None, fi_flag=P.fi_flag,
+             device="cuda:0", flags=0, maxiter=50000, context=None):
         """Batched F16.trim: straight-and-level trim at altitudes h_t [B] (ft) and airspeeds v_t [B] (ft/s) by the
         reference's Nelder-Mead, all conditions in one launch.  Returns (x_trim [B,18], info dict).
         `maxiter` and info["iters"] are scipy's option `maxiter` and result `nit`: the counter starts at 1, so at most
         maxiter - 1 iterations are performed, iters = performed + 1, and the F16_ST_QP_MAXITER bit of info["status"] is scipy's
-        status 2 (iters >= maxiter); info["nfev"] is scipy's nfev (include/f16_hip.h: f16_trim_batch)."""
+        status 2 (iters >= maxiter); info["nfev"] is scipy's nfev (include/f16_hip.h: f16_trim_batch).
+
+        With any of gamma (flight-path angle, rad), turn_rate (psi_dot, rad/s) or pullup_rate (theta_dot, rad/s) -- a scalar or
+        [B] each -- the trim is the steady climb, coordinated turn or pull-up of include/f16_hip.h: f16_trim_man_batch: six
+        unknowns (the sideslip is free), `runs` Nelder-Mead runs each from the best point of the last (one run stalls, two
+        converge), q0 [B, 6] or [6] an optional start (P3, dh, da, dr, alpha, beta); iters and nfev are totals over the runs.
+        With all three None the call is f16_trim_batch as before (runs and q0 are not read)."""
         if not torch.cuda.is_available():
             raise _lib.F16HipError("trim needs an AMD GPU (no CPU fallback)")
         dev = torch.device(device)
@@ -77,16 +84,26 @@ class F16Batch:
         nfev = torch.zeros(B, dtype=torch.int32, device=dev)
         st = torch.zeros(B, dtype=torch.int32, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(ctx.lib.f16_trim_batch(ctx.handle, _vp(h), _vp(v), _vp(xt), _vp(cost), _vp(iters), _vp(nfev), _vp(st), B, B,
-                                          xcg, int(fi_flag), int(flags), int(maxiter), None, stream), ctx.lib)
+        if gamma is None and turn_rate is None and pullup_rate is None:
+            _lib.check(ctx.lib.f16_trim_batch(ctx.handle, _vp(h), _vp(v), _vp(xt), _vp(cost), _vp(iters), _vp(nfev), _vp(st), B, B,
+                                              xcg, int(fi_flag), int(flags), int(maxiter), None, stream), ctx.lib)
+        else:
+            given = lambda a: None if a is None else torch.as_tensor(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (B,))), device=dev)
+            g, pd, td = given(gamma), given(turn_rate), given(pullup_rate)
+            q = None if q0 is None else torch.as_tensor(np.array(np.broadcast_to(np.asarray(q0, dtype=np.float64), (B, 6)).T, order="C"),
+                                                        device=dev)       # [6][B]
+            _lib.check(ctx.lib.f16_trim_man_batch(ctx.handle, _vp(h), _vp(v), _vp(g), _vp(pd), _vp(td), _vp(q), _vp(xt), _vp(cost),
+                                                  _vp(iters), _vp(nfev), _vp(st), B, B, xcg, int(fi_flag), int(flags), int(maxiter),
+                                                  int(runs), stream), ctx.lib)
         return xt.t(), dict(cost=cost, iters=iters, nfev=nfev, status=st, context=ctx)
 
     @classmethod
     def from_trim(cls, h_t, v_t, **kw):
         """env.py:42-44: construct the batch at its trim points (x.initial_condition = trim, u = x[12:16])."""
-        tk = {k: kw[k] for k in ("stab_flag", "xcg", "fi_flag", "device", "flags") if k in kw}
+        man = ("gamma", "turn_rate", "pullup_rate", "runs", "q0")     # the manoeuvre of F16Batch.trim, passed through
+        tk = {k: kw[k] for k in ("stab_flag", "xcg", "fi_flag", "device", "flags") + man if k in kw}
         x, info = cls.trim(h_t, v_t, **tk)            # [B,18] view of the device-resident [18,B] result
-        env = cls(x, None, context=info["context"], **{k: v for k, v in kw.items() if k != "maxiter"})
+        env = cls(x, None, context=info["context"], **{k: v for k, v in kw.items() if k != "maxiter" and k not in man})
         env.trim_info = info
         return env
 

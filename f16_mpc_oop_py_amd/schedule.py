@@ -98,17 +98,19 @@ class GainSchedule:
     # ------------------------------------------------------------------ the table from the plant
     @classmethod
     def build(cls, h0, dh, nh, v0, dv, nv, *, stab_flag=None, xcg=None, fi_flag=None, dt=None, Q=None, R=None, device="cuda:0",
-              max_trim_cost=1e-4, strict=True):
+              max_trim_cost=1e-4, strict=True, **trim_kw):
         """Trim, linearise, discretise and solve the LQR problem at every node, as ONE batch (node (ih, iv) = aircraft ih * nv + iv):
         `F16Batch.from_trim` then `_calc_LQR_gain(Q, R)`; K[:, :, 4:7] and the trim x[13:16] go into the table.  A node is bad when
         its trim cost exceeds max_trim_cost (the reference's Nelder-Mead is a knife edge at some conditions) or its trim or LQR status
-        word is non-zero: strict=True raises a ValueError naming the bad nodes, strict=False returns the schedule with `ok` set."""
+        word is non-zero: strict=True raises a ValueError naming the bad nodes, strict=False returns the schedule with `ok` set.
+        trim_kw (gamma, turn_rate, pullup_rate, runs, q0) goes to `F16Batch.from_trim`: the table is then derived about that climb,
+        turn or pull-up at every node."""
         import torch
         from .env import F16Batch
         nh, nv = int(nh), int(nv)
         hh, vv = np.meshgrid(float(h0) + float(dh) * np.arange(nh), float(v0) + float(dv) * np.arange(nv), indexing="ij")
         kw = {k: val for k, val in dict(stab_flag=stab_flag, xcg=xcg, fi_flag=fi_flag, dt=dt).items() if val is not None}
-        env = F16Batch.from_trim(hh.ravel(), vv.ravel(), device=device, **kw)
+        env = F16Batch.from_trim(hh.ravel(), vv.ravel(), device=device, **kw, **trim_kw)
         K = env._calc_LQR_gain(Q, R)                                         # [B, 3, 9]
         lqr_status = env.last_status
         table = torch.cat((K[:, :, 4:7].reshape(env.B, 9), env.x_values[:, 13:16]), 1).reshape(nh, nv, ENTRIES).cpu().numpy()

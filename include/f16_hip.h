@@ -624,6 +624,47 @@ int f16_xdot_na_batch(f16_ctx *ctx, const double *x_full, const double *x9, cons
 int f16_trim_batch(f16_ctx *ctx, const double *h, const double *v, double *x_trim, double *cost, int32_t *iters,
                    int32_t *nfev, int32_t *status, long B, long ld, double xcg, int fi_flag, unsigned flags,
                    int maxiter, const double *h_x0, void *stream);
+/* STEADY-STATE TRIM IN A MANOEUVRE (Stevens & Lewis, section 3.6): a climb or descent at flight-path angle gamma, a coordinated
+ * turn at rate psi_dot, a pull-up at rate theta_dot, or any sum of them, at zero roll rate -- for B conditions in one launch.  The
+ * rule is stated HERE ONCE; csrc/f16_trim.hip (`trim_man_cost`) and tests/trim_man_cases.py restate it.
+ *   Unknowns.  q = (P3, dh, da, dr, alpha, beta): the level trim's five in its order, and the sideslip.
+ *   Givens per condition (device arrays [B], each may be NULL = 0 for every condition): h, V, gamma (rad), psi_dot (rad/s),
+ *     theta_dot (rad/s).
+ *   Clipped copies.  The four commands and alpha are clipped as the level trim's objective clips them (1000 .. 19000, +-25, +-21.5,
+ *     +-30, -20 .. 90 deg); beta to +-30 deg, the table range.  The flap states x[16] (the level trim's formula) and x[17] =
+ *     -alpha 180 / pi come from the UNCLIPPED alpha.
+ *   Constraints, at the clipped alpha and beta, g = 32.17 (the plant's own constant in the force equations):
+ *         G = psi_dot V / g
+ *         a = 1 - G tan(alpha) sin(beta);   b = sin(gamma) / cos(beta);   c = 1 + G^2 cos^2(beta)
+ *         tan(phi)   = G (cos(beta) / cos(alpha)) [ (a - b^2) + b tan(alpha) sqrt(c (1 - b^2) + G^2 sin^2(beta)) ]
+ *                      / [ a^2 - b^2 (1 + c tan^2(alpha)) ]
+ *         a' = cos(alpha) cos(beta);        b' = sin(phi) sin(beta) + cos(phi) sin(alpha) cos(beta)
+ *         tan(theta) = [ a' b' + sin(gamma) sqrt(a'^2 - sin^2(gamma) + b'^2) ] / (a'^2 - sin^2(gamma))
+ *         p = -psi_dot sin(theta)
+ *         q =  theta_dot cos(phi) + psi_dot sin(phi) cos(theta)
+ *         r = -theta_dot sin(phi) + psi_dot cos(phi) cos(theta)
+ *     phi and theta by atan of the quotients.
+ *   The plant state is x = (0, 0, h, phi, theta, 0, V, alpha, beta, p, q, r, P3, dh, da, dr, lef, -alpha 180 / pi) with the clipped
+ *     copies, the commands u = x[12..15], and
+ *         cost = sum_k w_k (xdot_k - target_k)^2,   w = (0, 0, 5, 10, 10, 10, 2, 10, 10, 10, 10, 10)   (the level trim's weights)
+ *         target = 0 except target[2] = V sin(gamma), target[4] = theta_dot, target[5] = psi_dot.
+ *   Returned.  x_trim[18][ld] is that x with the six unknowns written back UNCLIPPED into x[12..15], x[7], x[8] (as the level trim
+ *     does for its five): q = x[12, 13, 14, 15, 7, 8] reads the optimiser's point back.  cost[B], iters[B], nfev[B], status[B] may
+ *     be NULL; status is OR-ed into; columns B .. ld - 1 are not written.
+ *   Not iterated.  A condition whose gamma is not finite or |gamma| >= pi / 2, whose psi_dot or theta_dot is not finite, or whose
+ *     constraints (phi, theta, p, q, r) are not finite at its start point returns x_trim and cost NaN, iters 0, nfev 0 and
+ *     F16_ST_NONFINITE.
+ *   The optimiser is f16_trim_batch's -- scipy's Nelder-Mead, tol 1e-10, the same counter, cap, termination, tie rule and fixed-point
+ *     fast-forward -- in six dimensions: seven vertices; nfev is 7 for the initial simplex, then 1, 2 or 8 per iteration.
+ *   Runs.  One Nelder-Mead run in six unknowns stalls (cost 1e-6 .. 1e-2); a second run from its best point converges (1e-27).  A call
+ *     makes runs >= 1 runs (runs <= 0: F16_EINVAL).  Run k + 1 starts from the best vertex of run k with a fresh initial simplex (5 %
+ *     of each coordinate, 0.00025 on a zero); each run has a counter and the cap maxiter of its own (maxiter <= 0: 50,000); iters
+ *     and nfev are totals over the runs; F16_ST_QP_MAXITER is set when any run ended on its cap.
+ *   q0[6][ld] (device) is a start per condition; NULL is the level trim's start with beta = 0. */
+int f16_trim_man_batch(f16_ctx *ctx, const double *h, const double *v, const double *gamma, const double *psi_dot,
+                       const double *theta_dot, const double *q0, double *x_trim, double *cost, int32_t *iters,
+                       int32_t *nfev, int32_t *status, long B, long ld, double xcg, int fi_flag, unsigned flags,
+                       int maxiter, int runs, void *stream);
 
 /* ---- (2) batched control chain ---------------------------------------------------------- */
 /* env.py:294-342 with _calc_xdot_na/_get_obs_na at each aircraft's own point: x9 = x[mpc idx] of x[18][ld],
