@@ -707,7 +707,8 @@ int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, const double
  * per aircraft with the KKT inverse in the HBM workspace (the stream of its symmetric half, 0.93 MB per iteration at hzn = 150,
  * sets the pace; f16_mpc_hzn_sweep below solves all horizons of a sweep in one launch).
  * u_seq (may be NULL) gets the full [3*hzn][ld] sequence, info (may be NULL) gets [4][ld] = iterations, r_prim, r_dual
- * (unscaled), rho.
+ * (unscaled), rho.  status[ld] (may be NULL) is OR-ed into, never cleared, by f16_mpc_batch(_w) and f16_mpc_plan_solve(_w) alike:
+ * the caller zeroes it, and a bit that is already set survives the call.
  * Nothing the results depend on is retained between calls: the QP workspace is allocated and freed per call, stream-ordered
  * on `stream`; calls on different streams of one context do not share buffers.  Under stream capture the call returns
  * F16_EINVAL (graph replays of the stream-ordered allocation were measured unreliable on ROCm 7.2): capture
