@@ -74,10 +74,13 @@ __global__ __launch_bounds__(BLOCK) void k_linearise(LinArgs a) {
     calc_xdot_na((const double *)tab, a.lofi, svp, f1, a.xcg, a.fi, a.flags, st);
     calc_xdot_na((const double *)tab, a.lofi, sv, f0, a.xcg, a.fi, a.flags, st);   // base point re-evaluated per column
     if (c < 9) {
+      // env.py:331 with _get_obs_na: row r of C is (x9[r] + dx[r] - x9[r]) / eps.  Off the diagonal dx[r] = 0: x - x is an exact
+      // zero for a finite state and NaN for a NaN or infinite one (the whole row of such a state is NaN in the reference)
+      const int ROW[9] = {3, 4, 7, 8, 9, 10, 11, 17, 16};
 #pragma unroll
       for (int r = 0; r < 9; ++r) {
         a.Ac[(r * 9 + c) * a.ld + b] = (f1[r] - f0[r]) / a.eps;
-        a.Cc[(r * 9 + c) * a.ld + b] = r == c ? (pert - base) / a.eps : 0.0;       // env.py:331 with _get_obs_na
+        a.Cc[(r * 9 + c) * a.ld + b] = r == c ? (pert - base) / a.eps : sv[ROW[r]] - sv[ROW[r]];
       }
     } else {
 #pragma unroll

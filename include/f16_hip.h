@@ -669,7 +669,8 @@ int f16_trim_man_batch(f16_ctx *ctx, const double *h, const double *v, const dou
 /* ---- (2) batched control chain ---------------------------------------------------------- */
 /* env.py:294-342 with _calc_xdot_na/_get_obs_na at each aircraft's own point: x9 = x[mpc idx] of x[18][ld],
  * u3 = u[1..3] of u[4][ld] (self.u._get_mpc_u(), env.py:348): Ac[81][ld] Bc[27][ld] Cc[81][ld]
- * (row-major element index = r*ncols+c); eps = 1e-5 in the reference (env.py:319). */
+ * (row-major element index = r*ncols+c); eps = 1e-5 in the reference (env.py:319).  Cc[r][c] = (x9[r] + dx[r] - x9[r]) / eps with
+ * dx = eps e_c: off the diagonal an exact zero, and NaN in the whole row of a state that is NaN or infinite (as in the reference). */
 int f16_linearise_batch(f16_ctx *ctx, const double *x, const double *u, double *Ac, double *Bc, double *Cc,
                         int32_t *status, long B, long ld, double eps, double xcg, int fi_flag,
                         unsigned flags, void *stream);

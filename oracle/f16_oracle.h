@@ -1,6 +1,6 @@
 /* oracle/f16_oracle.h -- TEST INFRASTRUCTURE, NOT PRODUCT.
  *
- * CPU restatement (plain C, fp64, no fast-math, no FMA contraction) of the
+ * CPU restatement (plain C, fp64 -- or extended precision, below --, no fast-math, no FMA contraction) of the
  * reference's F-16 plant + actuator + Euler path.  Only tests/, __graft_entry__.smoke()
  * and bench.py's cpu_baseline leg may load this library.  The product
  * (f16_mpc_oop_py_amd + libf16hip.so) never links, imports or calls it.
@@ -16,6 +16,16 @@
 #define F16_ORACLE_H
 #ifdef __cplusplus
 extern "C" {
+#endif
+
+/* The type the restatement computes in: fp64, or -- compiled with -DF16O_LONG_DOUBLE into libf16_oracle_ld.so -- x87 extended
+ * precision (64-bit significand), the reference of tests/linearise_cases.py.  Every entry below that takes or returns `double`
+ * does so in both builds (the wide build widens on the way in and rounds on the way out); only the entries written on f16o_real
+ * hand the wide values over. */
+#ifdef F16O_LONG_DOUBLE
+typedef long double f16o_real;
+#else
+typedef double f16o_real;
 #endif
 
 /* status bits (sticky per aircraft in the batched calls) */
@@ -54,6 +64,20 @@ void f16o_linearise_na(const double *x_full, const double *x9, const double *u3,
 /* env.py:294-342 default (18-state): A[18*18] B[18*4] C[10*18] D[10*4] */
 void f16o_linearise_full(const double *x, const double *u, double eps,
                          double *A, double *B, double *C, double *D, int fi_flag, double xcg);
+
+/* sizeof(f16o_real) of this build (8 or 16), and the tables as the build holds them: breakpoints [5][20], the hifi tables, the
+ * lofi tables, concatenated; returns their count and writes at most n of them.  In both builds every value is an fp64 number. */
+int f16o_real_bytes(void);
+long f16o_table_image(f16o_real *out, long n);
+/* f16o_linearise_na / _full for B aircraft (x [B][18], u [B][4]; the reduced model at x9 = x[mpc idx], u3 = u[1..3], the point of
+ * f16_linearise_batch), matrices in f16o_real: A [B][81] Bm [B][27] C [B][81], 18-state A [B][324] Bm [B][72] C [B][180].  The
+ * perturbed coordinate is the fp64 sum fl64(x + eps) in both builds.  status (may be NULL) [B] receives the OR of the grid-clamp
+ * bits of the base point and of EVERY perturbed point (f16o_last_status: the last evaluation only).  OpenMP, thread count from the
+ * environment. */
+void f16o_linearise_na_batch(const double *x, const double *u, long B, double eps, f16o_real *A, f16o_real *Bm, f16o_real *C,
+                             int *status, int fi_flag, double xcg);
+void f16o_linearise_full_batch(const double *x, const double *u, long B, double eps, f16o_real *A, f16o_real *Bm, f16o_real *C,
+                               int *status, int fi_flag, double xcg);
 
 /* batched helpers (row-major [B][18] / [B][4]); nthreads<=1 => serial. traj may be NULL,
  * else [T][B][18] filled after every step. status[B] in/out (sticky). */
