@@ -8,8 +8,14 @@
 //   k_dbg_sincos  the branch-free sin/cos pair in its two forms on the same arguments: sincos_bf (constants as literals) and
 //                 sincos_bf_k (the same table loaded into scalar registers, the form of the quad rollout).  The two must agree
 //                 bit for bit; the rollouts only show that through whole trajectories.
-//   k_dbg_pow     the atmosphere's exp(0.14 log tfac) as the device library composes it and as exp_k / log_k repeat it with
-//                 the constants in scalar registers, and qbar / ps of atmos_dev through either: the same bits.
+//   k_dbg_pow     the atmosphere's exp(POW_FRAC log tfac) (POW_FRAC = 0.14, f16_plant.hpp) as the device library composes it and as
+//                 exp_k / log_k repeat it with the constants in scalar registers, and qbar / ps of atmos_dev through either: the
+//                 same bits.
+//   k_dbg_elem_*  each elementary function of the default build on its own, on given arguments, for the multiprecision comparison of
+//                 tests/test_gpu_elem.py: the sin/cos pair in its THREE forms (literals, table in scalar registers, table in vector
+//                 registers as the quad rollout's G1 role holds it); the power factor by three routes with tfac, mach, qbar and ps
+//                 at a given airspeed; f16_rcp; tan as plant_pre forms it; and the sin/cos pairs carried from step to step by
+//                 trig_advance / trig_rotate.
 //   k_dbg_gain_lookup  the gain-schedule lookup over (h, V) of f16_rollout_lqr_gs (gain_lookup, f16_gain_sched.hpp) at given points:
 //                 the same bits as the host function and the numpy restatement.
 #include <hip/hip_runtime.h>
@@ -109,9 +115,83 @@ __global__ __launch_bounds__(64) void k_dbg_pow(const double *__restrict__ alt, 
   const PowK pk = reloaded(QUAD_K.pw);
   for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
     double pw0 = 0, pw1 = 0, mach, q0, p0, q1, p1;
-    atmos_with(alt[p], 500.0, mach, q0, p0, [&](double tfac) { return pw0 = exp(0.14 * log(tfac)); });
-    atmos_with(alt[p], 500.0, mach, q1, p1, [&](double tfac) { return pw1 = exp_k(pk, 0.14 * log_k(pk, tfac)); });
+    atmos_with(alt[p], 500.0, mach, q0, p0, [&](double tfac) { return pw0 = exp(POW_FRAC * log(tfac)); });
+    atmos_with(alt[p], 500.0, mach, q1, p1, [&](double tfac) { return pw1 = exp_k(pk, POW_FRAC * log_k(pk, tfac)); });
     out[p] = pw0; out[n + p] = q0; out[2 * n + p] = p0; out[3 * n + p] = pw1; out[4 * n + p] = q1; out[5 * n + p] = p1;
+  }
+}
+#endif
+
+#ifdef F16_FAST_TRIG
+// out: [6][n] = sin, cos by sincos_bf | by sincos_bf_k<KScalar> | by sincos_bf_k<KVector>, the table loaded and moved as the quad
+// rollout's role loops do it (f16_quad_steps.inc: reloaded, table_in_vgprs)
+__global__ __launch_bounds__(64) void k_dbg_elem_sincos(const double *__restrict__ x, double *__restrict__ out, long n) {
+  const SinCosK sk = reloaded(QUAD_K.sc);
+  SinCosK sv = reloaded(QUAD_K.sc);
+  table_in_vgprs(sv);
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double s0, c0, s1, c1, s2, c2;
+    sincos_bf(x[p], &s0, &c0);
+    sincos_bf_k<KScalar>(sk, x[p], &s1, &c1);
+    sincos_bf_k<KVector>(sv, x[p], &s2, &c2);
+    out[p] = s0; out[n + p] = c0; out[2 * n + p] = s1; out[3 * n + p] = c1; out[4 * n + p] = s2; out[5 * n + p] = c2;
+  }
+}
+
+// in: [1 + n_steps][n] = start angle | one increment per step;  out: [n_steps][4][n] = sin, cos, angle, verdict (0 / 1) after every step.
+// The lane's angle is the pitch angle of a state whose other angles stay 0 (their pairs rotate (0, 1) by 0: unchanged), so that
+// trig_exact, trig_store and trig_advance themselves run, on slots in registers instead of LDS.
+__global__ __launch_bounds__(64) void k_dbg_elem_trig_carry(const double *__restrict__ in, int n_steps, double *__restrict__ out, long n) {
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double x[9] = {0, 0, 0, 0, in[p], 0, 0, 0, 0}, slots[10];
+    const TrigSlots ts = {slots, 1};
+    Trig5 g;
+    trig_exact(x, g);
+    trig_store(ts, g);
+    for (int k = 0; k < n_steps; ++k) {
+      const double xo5[5] = {0, 0, x[4], 0, 0};
+      x[4] = x[4] + in[(long)(1 + k) * n + p];               // xn = xo + d, as the Euler step leaves it in the state
+      const bool stale = trig_advance(xo5, x, ts);           // (the increment taken back as xn - xo)
+      double *o = out + (long)k * 4 * n + p;
+      o[0] = slots[4]; o[n] = slots[5]; o[2 * n] = x[4]; o[3 * n] = stale ? 1.0 : 0.0;
+    }
+  }
+}
+#endif
+
+#ifdef F16_FAST_POW
+// in: [2][n] = altitude, airspeed;  out: [13][n] = tfac | factor, mach, qbar, ps by atmos_dev (library exp / log) | the same four by
+// atmos_dev_k (exp_k / log_k, table in scalar registers) | the same four with the table in vector registers
+__global__ __launch_bounds__(64) void k_dbg_elem_atmos(const double *__restrict__ in, double *__restrict__ out, long n) {
+  const PowK pk = reloaded(QUAD_K.pw);
+  PowK pv = reloaded(QUAD_K.pw);
+  table_in_vgprs(pv);
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    const double alt = in[p], vt = in[n + p], tfac = atmos_alt(alt).tfac;
+    double m0, q0, p0, m1, q1, p1, m2, q2, p2, pw2 = 0;
+    atmos_dev(alt, vt, m0, q0, p0);
+    atmos_dev_k(pk, alt, vt, m1, q1, p1);
+    atmos_with(alt, vt, m2, q2, p2, [&](double t) { return pw2 = exp_k<KVector>(pv, POW_FRAC * log_k<KVector>(pv, t)); });
+    out[p] = tfac;
+    out[n + p] = exp(POW_FRAC * log(tfac)); out[2 * n + p] = m0; out[3 * n + p] = q0; out[4 * n + p] = p0;
+    out[5 * n + p] = exp_k<KScalar>(pk, POW_FRAC * log_k<KScalar>(pk, tfac)); out[6 * n + p] = m1; out[7 * n + p] = q1; out[8 * n + p] = p1;
+    out[9 * n + p] = pw2; out[10 * n + p] = m2; out[11 * n + p] = q2; out[12 * n + p] = p2;
+  }
+}
+#endif
+
+#ifdef F16_FAST_DIV
+// out: [n] = f16_rcp(x)
+__global__ __launch_bounds__(64) void k_dbg_elem_rcp(const double *__restrict__ x, double *__restrict__ out, long n) {
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) out[p] = f16_rcp(x[p]);
+}
+// out: [3][n] = sin theta, cos theta, tt = sin theta * f16_rcp(cos theta) as plant_pre forms it
+__global__ __launch_bounds__(64) void k_dbg_elem_tan(const double *__restrict__ theta, double *__restrict__ out, long n) {
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double st, ct;
+    F16_SINCOS(theta[p], &st, &ct);
+    const double rct = f16_rcp(ct);
+    out[p] = st; out[n + p] = ct; out[2 * n + p] = st * rct;
   }
 }
 #endif
@@ -214,5 +294,85 @@ extern "C" int f16_debug_pow(f16_ctx *ctx, const double *h_alt, long n, double *
   return rc;
 #else
   return set_error(F16_EINVAL, "f16_debug_pow: this library was built without F16_FAST_POW (libm pow, one form only)");
+#endif
+}
+
+// ---- the elementary functions on their own (tests/test_gpu_elem.py)
+// The host side the entries below share: rows_in arrays of n doubles up (h_in: contiguous), one launch of `kernel` on (in, out, n) by
+// grid-stride workgroups of 64, rows_out arrays of n doubles back.
+template <typename LAUNCH>
+static int dbg_elem_run(const char *what, const double *h_in, size_t rows_in, long n, double *h_out, size_t rows_out, LAUNCH launch) {
+  double *d = nullptr;
+  int rc;
+  if ((rc = hip_check(hipMalloc(&d, (rows_in + rows_out) * (size_t)n * sizeof(double)), what))) return rc;
+  if (!(rc = hip_check(hipMemcpy(d, h_in, rows_in * (size_t)n * sizeof(double), hipMemcpyHostToDevice), what))) {
+    const long blocks = (n + 63) / 64;
+    launch(dim3((unsigned)(blocks < 1024 ? blocks : 1024)), d, d + rows_in * (size_t)n);
+    rc = hip_check(hipGetLastError(), what);
+    if (!rc) rc = hip_check(hipMemcpy(h_out, d + rows_in * (size_t)n, rows_out * (size_t)n * sizeof(double), hipMemcpyDeviceToHost), what);
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
+extern "C" int f16_debug_elem_sincos(f16_ctx *ctx, const double *h_x, long n, double *h_out) {
+  if (!ctx || !h_x || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_elem_sincos");
+#ifdef F16_FAST_TRIG
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_elem_sincos", h_x, 1, n, h_out, 6, [&](dim3 grid, const double *in, double *out) {
+    hipLaunchKernelGGL(k_dbg_elem_sincos, grid, dim3(64), 0, nullptr, in, out, n);
+  });
+#else
+  return set_error(F16_EINVAL, "f16_debug_elem_sincos: this library was built without F16_FAST_TRIG (libm sincos, one form only)");
+#endif
+}
+
+extern "C" int f16_debug_elem_trig_carry(f16_ctx *ctx, const double *h_angle_and_steps, int n_steps, long n, double *h_out) {
+  if (!ctx || !h_angle_and_steps || !h_out || n < 0 || n_steps < 1 || n_steps > 4096)
+    return set_error(F16_EINVAL, "bad argument to f16_debug_elem_trig_carry");
+#ifdef F16_FAST_TRIG
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_elem_trig_carry", h_angle_and_steps, 1 + (size_t)n_steps, n, h_out, 4 * (size_t)n_steps,
+                      [&](dim3 grid, const double *in, double *out) {
+                        hipLaunchKernelGGL(k_dbg_elem_trig_carry, grid, dim3(64), 0, nullptr, in, n_steps, out, n);
+                      });
+#else
+  return set_error(F16_EINVAL, "f16_debug_elem_trig_carry: this library was built without F16_FAST_TRIG (libm sincos, one form only)");
+#endif
+}
+
+extern "C" int f16_debug_elem_atmos(f16_ctx *ctx, const double *h_alt_vt, long n, double *h_out) {
+  if (!ctx || !h_alt_vt || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_elem_atmos");
+#ifdef F16_FAST_POW
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_elem_atmos", h_alt_vt, 2, n, h_out, 13, [&](dim3 grid, const double *in, double *out) {
+    hipLaunchKernelGGL(k_dbg_elem_atmos, grid, dim3(64), 0, nullptr, in, out, n);
+  });
+#else
+  return set_error(F16_EINVAL, "f16_debug_elem_atmos: this library was built without F16_FAST_POW (libm pow, one form only)");
+#endif
+}
+
+extern "C" int f16_debug_elem_rcp(f16_ctx *ctx, const double *h_x, long n, double *h_out) {
+  if (!ctx || !h_x || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_elem_rcp");
+#ifdef F16_FAST_DIV
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_elem_rcp", h_x, 1, n, h_out, 1, [&](dim3 grid, const double *in, double *out) {
+    hipLaunchKernelGGL(k_dbg_elem_rcp, grid, dim3(64), 0, nullptr, in, out, n);
+  });
+#else
+  return set_error(F16_EINVAL, "f16_debug_elem_rcp: this library was built without F16_FAST_DIV (IEEE division, one form only)");
+#endif
+}
+
+extern "C" int f16_debug_elem_tan(f16_ctx *ctx, const double *h_theta, long n, double *h_out) {
+  if (!ctx || !h_theta || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_elem_tan");
+#ifdef F16_FAST_DIV
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_elem_tan", h_theta, 1, n, h_out, 3, [&](dim3 grid, const double *in, double *out) {
+    hipLaunchKernelGGL(k_dbg_elem_tan, grid, dim3(64), 0, nullptr, in, out, n);
+  });
+#else
+  return set_error(F16_EINVAL, "f16_debug_elem_tan: this library was built without F16_FAST_DIV (IEEE division, one form only)");
 #endif
 }

@@ -38,8 +38,9 @@ constexpr unsigned FLAG_FIX_CLR = 1u, FLAG_NO_ENVELOPE = 2u, FLAG_NO_CELL_CACHE 
 #define F16_DIVC(x, c) ((x) / (c))
 #endif
 
-// 1/x for a normal, finite x.  Strict build: IEEE division.  Default build: v_rcp_f64 + two Newton steps (<= 1 ulp),
-// 5 instructions instead of the ~15 of the division sequence.
+// 1/x for a normal, finite x.  Strict build: IEEE division.  Default build: v_rcp_f64 + two Newton steps (<= 1 ulp of 1/x, held by
+// tests/test_gpu_elem.py against multiprecision values over every normal exponent: 0.5 ulp measured up to 2^1022, 1 ulp above, where
+// the reciprocal is a denormal; NaN for 0, denormals and infinities), 5 instructions instead of the ~15 of the division sequence.
 __device__ __forceinline__ double f16_rcp(double x) {
 #ifdef F16_FAST_DIV
   double r = __builtin_amdgcn_rcp(x);
@@ -97,7 +98,7 @@ F16_DEV void table_in_vgprs(T &t) {
   for (unsigned i = 0; i < sizeof(T) / sizeof(double); ++i) in_vgpr(d[i]);
 }
 
-// ---- exp(0.14 log tfac) of F16_FAST_POW with its constants as uniform values
+// ---- exp(POW_FRAC log tfac), POW_FRAC = 0.14 (below), of F16_FAST_POW with its constants as uniform values
 // The device library's exp and log are inlined from bitcode, so their literals cannot be redirected; in the quad rollout they
 // cost the atmosphere wave a register move (accumulation register, 64-bit copy or a pair of scalar moves) in front of almost
 // every polynomial step.  exp_k / log_k repeat the library's operation sequence (ROCm device library, double-precision exp and
@@ -218,7 +219,14 @@ F16_DEV double exp_k(const PowK &K, double x) {
   return x < -1075.0 ? 0.0 : res;
 }
 
-// C/nlplant.c:467-490 in its two parts; pw(tfac) = exp(0.14 log tfac) of the default build (below).
+// C/nlplant.c:467-490 in its two parts; pw(tfac) = exp(POW_FRAC log tfac) of the default build (below).
+// The exponent the fast form leaves to exp / log, named once for its four users (atmos_dev, atmos_dev_k, the quad rollout's atmosphere
+// role, the debug kernels).  The double 0.14 is not 4.14 - 4.0 (0.13999999999999968, exact): 4 + fl(0.14) lies 3.3e-16 above fl(4.14),
+// the exponent of the reference's pow(tfac, 4.14), which moves the density by 3.3e-16 |log tfac| -- 2.7 x 2^-53 at 91,000 ft, nothing
+// at sea level.  Measured on the device over [0, 1e5] ft (tests/test_gpu_elem.py): qbar within 7.4 x 2^-53 of the multiprecision
+// .5 rho0 tfac^fl(4.14) vt^2 with 0.14, 4.3 with 4.14 - 4.0, both inside the rounding budget of 9 (tests/elem_cases.py); the constant
+// therefore stays as every earlier result was computed with it.
+constexpr double POW_FRAC = 0.14;
 // (1) what the altitude alone decides: the quad rollout evaluates it half a step ahead of (2), f16_quad_steps.inc
 struct AtmosAlt {
   double tfac, temp, t4;           // t4 = (tfac^2)^2, F16_FAST_POW only
@@ -229,8 +237,11 @@ F16_DEV AtmosAlt atmos_alt(double alt) {
   h.temp = 519.0 * h.tfac;
   if (alt >= 35000.0) h.temp = 390;
 #ifdef F16_FAST_POW
-  // tfac^4.14 = (tfac^2)^2 * exp(0.14 log tfac): |0.14 log tfac| < 0.2 on the flight envelope keeps the
-  // exp-of-log error below 1 ulp; two exact-to-0.5ulp squarings on top => <= 2 ulp vs libm pow.
+  // tfac^4.14 = (tfac^2)^2 * exp(POW_FRAC log tfac): |POW_FRAC log tfac| < 0.2 on the flight envelope keeps the exp-of-log
+  // error below 1 ulp of tfac^POW_FRAC (measured 0.64); the squarings (1 and 3 roundings), the factor (<= 2) and two products on top
+  // => the density within 7 x 2^-53 of rho0 tfac^4.14 in relative terms -- up to 7 ulp, not the 2 ulp once claimed here.
+  // tests/elem_cases.py writes the budget out; tests/test_gpu_elem.py holds what the device returns of it, qbar and ps, to 9 and 10 x
+  // 2^-53 (measured 7.4 and 7.1) and mach to 3.5 (2.3).
   const double t2 = h.tfac * h.tfac;
   h.t4 = t2 * t2;
 #else
@@ -257,22 +268,22 @@ F16_DEV void atmos_with(double alt, double vt, double &mach, double &qbar, doubl
   atmos_air(atmos_alt(alt), vt, mach, qbar, ps, pw);
 }
 F16_DEV void atmos_dev(double alt, double vt, double &mach, double &qbar, double &ps) {
-  atmos_with(alt, vt, mach, qbar, ps, [](double tfac) { return exp(0.14 * log(tfac)); });
+  atmos_with(alt, vt, mach, qbar, ps, [](double tfac) { return exp(POW_FRAC * log(tfac)); });
 }
 // the same with the constants of exp and log as uniform values (quad rollout)
 F16_DEV void atmos_dev_k(const PowK &K, double alt, double vt, double &mach, double &qbar, double &ps) {
-  atmos_with(alt, vt, mach, qbar, ps, [&K](double tfac) { return exp_k(K, 0.14 * log_k(K, tfac)); });
+  atmos_with(alt, vt, mach, qbar, ps, [&K](double tfac) { return exp_k(K, POW_FRAC * log_k(K, tfac)); });
 }
 
 
 // The constants of the branch-free sin/cos pair below live in ONE table: sincos_bf folds them to literals, sincos_bf_k takes the same table as uniform values
 // (scalar registers, loaded from QUAD_K below), so the two cannot drift.
 struct SinCosK {
-  double two_over_pi, npio2[3];    // 2/pi; -pi/2 in three parts
+  double two_over_pi, npio2[3];    // 2/pi; -pi/2 in three parts, each a FULL double: the double nearest pi/2, nearest the rest, and again
   double S[8], C[9];               // sin: r + r z (S0 + S1 z + ...), cos: 1 + z (C0 + C1 z + ...), z = r^2
 };
 constexpr SinCosK SINCOS_K = {
-    6.36619772367581382433e-01, {-1.57079632673412561417e+00, -6.07710050630396597660e-11, -2.02226624879595063154e-21},
+    6.36619772367581382433e-01, {-1.57079632679489655800e+00, -6.12323399573676603587e-17, 1.49738490485916983294e-33},
     {-1.66666666666666657e-01, 8.33333333333333322e-03, -1.98412698412698413e-04, 2.75573192239858925e-06, -2.50521083854417202e-08, 1.60590438368216133e-10, -7.64716373181981641e-13, 2.81145725434552060e-15},
     {-5.00000000000000000e-01, 4.16666666666666644e-02, -1.38888888888888894e-03, 2.48015873015873016e-05, -2.75573192239858883e-07, 2.08767569878681002e-09, -1.14707455977297245e-11, 4.77947733238738525e-14, -1.56192069685862253e-16}};
 
@@ -297,11 +308,17 @@ F16_DEV T reloaded(const T &t) {
 }
 
 #ifdef F16_FAST_TRIG
-// Branch-free sin/cos pair: 3-part Cody-Waite reduction by pi/2 (exact for |x| < ~1e6 rad) + Taylor polynomials on
-// |r| <= pi/4 (coefficients are the exact 1/k! values; truncation < 5e-17).  Measured <= 2 ulp from libm on
-// [-1e5, 1e5].  Unlike the libm call it contains no large-argument branch, so the five independent evaluations of a
-// plant step sit in ONE basic block and the scheduler interleaves their dependency chains (the kernel is bound by
-// fp64 dependent-issue latency at one wave per SIMD).
+// Branch-free sin/cos pair: 3-part reduction by pi/2 in fused steps + Taylor polynomials on |r| <= pi/4 (coefficients are the
+// exact 1/k! values; truncation < 5e-17).  The first step, fma(-n, fl(pi/2), x), is EXACT for every n: its result is a multiple of
+// 2^-52 below 1.  The second rounds once, relative to the reduced argument, so nothing is lost where x lies next to a multiple of
+// pi/2; the third part leaves n x 5.6e-50.  (Parts of 33 bits, as a reduction without fused steps needs them, left n x 1e-37: 3.4 ulp
+// in the cosine of the double nearest 204,551 pi/2.)  Held by tests/test_gpu_elem.py, bit for bit against the checker's host
+// restatement and through it against multiprecision values: within 1.3 ulp of the true value for |x| <= 1e6 (the test's
+// bound: the C library's own error + 2 ulp) and measured within 1.1 ulp up to 3.3e9.  From |x| >= 2^31 pi/2 (3.37e9 rad) the quadrant
+// comes from a saturated (int)n: the result is then a finite number in [-1, 1] unrelated to x, and nothing reports it -- phi, theta and
+// psi have no envelope limit, the caller keeps them in range.  Unlike the libm call it contains no large-argument branch, so the
+// five independent evaluations of a plant step sit in ONE basic block and the scheduler interleaves their dependency chains (the
+// kernel is bound by fp64 dependent-issue latency at one wave per SIMD).
 // quadrant selection shared by both forms
 F16_DEV void sincos_quadrant(double n, double s0, double c0, double *sn, double *cs) {
   const int k = (int)n & 3;
@@ -909,7 +926,10 @@ F16_DEV void trig_exact(const double *x, Trig5 &g) {
 }
 // (sin, cos)(a + d) from (sin, cos)(a) by the angle-sum formulas with sin d, cos d from their series: for |d| <= 4e-3 rad (an Euler
 // step of 1 ms moves an angle by |rate| x 1e-3) the terms dropped are d^7 / 5040 < 4e-21 and d^6 / 720 < 6e-18.  11 operations per
-// angle against ~42 for the full evaluation (range reduction, two polynomials, quadrant selects).
+// angle against ~42 for the full evaluation (range reduction, two polynomials, quadrant selects).  With its roundings a rotation adds
+// at most 1.6 x 2^-53 to the error of s and of c (the budget written out in tests/elem_cases.py; tests/test_gpu_elem.py holds the
+// pairs to it over 1, 31 and 32 rotations against the multiprecision sin / cos of the stored angle; measured after 32: 17 x 2^-53,
+// and |s^2 + c^2 - 1| = 32 x 2^-53, of 78 allowed).
 F16_DEV void trig_rotate(double &s, double &c, double d) {
   const double d2 = d * d;
   const double sd = d * fma(d2, fma(d2, 1.0 / 120.0, -1.0 / 6.0), 1.0);
@@ -928,8 +948,9 @@ F16_DEV void trig_store(const TrigSlots &ts, const Trig5 &g) {
   b[8 * n] = g.spsi; b[9 * n] = g.cpsi;
 }
 // after an Euler step: the pairs follow their angles by the EXACT increment of the stored state (xn - xo: a difference of
-// neighbouring doubles), so nothing but the rounding of the rotations (~1e-16 a step) separates them from the state.  Returns
-// whether an increment left the series' range (the caller then marks the slots stale: the next step evaluates exactly).
+// neighbouring doubles), so nothing but the rounding of the rotations (<= 1.6 x 2^-53 a step, above) separates them from the state.
+// Returns whether an increment left the series' range (the caller then marks the slots stale: the next step evaluates exactly).  fmax drops
+// a NaN beside a number: a NaN increment of ONE angle is not reported here (its pair, and with it the state, becomes NaN).
 F16_DEV bool trig_advance(const double *xo5, const double *xn, const TrigSlots &ts) {
   const double da = xn[7] - xo5[0], db = xn[8] - xo5[1], dt = xn[4] - xo5[2], dp = xn[3] - xo5[3], ds = xn[5] - xo5[4];
   const double big = fmax(fmax(fabs(da), fabs(db)), fmax(fmax(fabs(dt), fabs(dp)), fabs(ds)));

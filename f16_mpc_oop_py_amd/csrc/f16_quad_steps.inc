@@ -244,13 +244,13 @@
         double vt = xa[6];
         if (vt <= 0.01) vt = 0.01;
         double mach, qbar, ps;
-        double pw = 0;                                     // GROUPS = 1: exp(0.14 log tfac) of this altitude, shared with the flap model
+        double pw = 0;                                     // GROUPS = 1: exp(POW_FRAC log tfac) of this altitude, shared with the flap model
         if constexpr (G1) {
           // the altitude part (ah) and the quotient of the log (lq) were evaluated behind barrier B of the last step: what is left
           // needs no LDS read up to the density and runs under the wait for x[6], x[7]; only qbar takes this step's airspeed.
           // (pinned behind barrier A too: the compiler moved the rest of the chain in front of it, into the half wave 3 then paced)
           quad_taken_here(ah.tfac, lq.h, lq.l, lq.e, lp.z, lp.c);
-          pw = exp_k(kpw, 0.14 * log_k_tail(kpw, ah.tfac, lq, lp));   // (the table loaded in front of the loop)
+          pw = exp_k(kpw, POW_FRAC * log_k_tail(kpw, ah.tfac, lq, lp));   // (the table loaded in front of the loop)
           atmos_air(ah, vt, mach, qbar, ps, [pw](double) { return pw; });
         } else
           atmos_dev(xa[2], vt, mach, qbar, ps);

@@ -18,8 +18,12 @@ SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_control.hip", "f16_mpc_solve.
 # reproduce the reference bit for bit where no libm call is involved (tests/test_gpu_dynamics.py); never used by the product
 STRICT_SO_PATH = os.path.join(HERE, "libf16hip_strict.so")
 STRICT_SOURCES = ["f16_api.hip", "f16_dynamics.hip", "f16_debug.hip", "f16_tables.cpp"]
-# Default build: FMA contraction on, tan = sin/cos, tfac^4.14 = tfac^4 * exp(0.14 log tfac), branch-free sincos (each <= 2 ulp away from
-# the strict form; measured: xdot max rel. error vs the CPU restatement unchanged at 5e-14, -16 % kernel time).
+# Default build: FMA contraction on, tan = sin/cos, tfac^4.14 = tfac^4 * exp(0.14 log tfac), branch-free sincos.  Held against
+# multiprecision values by tests/test_gpu_elem.py: sin / cos within 1.3 ulp of the true value for |x| <= 1e6 (bound: libm's own error
+# + 2 ulp), the reciprocal within 1 ulp, exp(0.14 log tfac) within 1 ulp (measured 0.64), qbar and ps within 9 and 10 x 2^-53 relative of
+# their multiprecision values (measured 7.4 and 7.1; the density's share of that budget is 7 x 2^-53, up to 7 ulp of rho0 tfac^4.14),
+# tan = sin * rcp(cos) within 13 x 2^-53.  Measured: xdot max rel. error vs the CPU restatement unchanged at
+# 5e-14, -16 % kernel time.
 # F16_STRICT=1 builds the expression-by-expression variant (no contraction, libm tan/pow): 97 % of xdot outputs
 # then agree with the reference restatement bit for bit.
 if os.environ.get("F16_STRICT"):

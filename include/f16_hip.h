@@ -104,6 +104,36 @@ int f16_debug_sincos(f16_ctx *ctx, const double *h_x, long n, double *h_out);
  * form, then of the second.  The two agree bit for bit.  F16_EINVAL from a library built without F16_FAST_POW. */
 int f16_debug_pow(f16_ctx *ctx, const double *h_alt, long n, double *h_out);
 
+/* Tests (tests/test_gpu_elem.py): each elementary function of the default build on its own, on n arguments given on the HOST, for
+ * the comparison with a multiprecision reference.  All are synchronous, accept n == 0, and return F16_EINVAL from a library built
+ * without the F16_FAST_* form they expose.
+ *   f16_debug_elem_sincos      the branch-free sin/cos pair in its THREE forms: constants as literals, the table in scalar registers,
+ *                              the table in vector registers (the quad rollout's alpha / beta role).  h_out [6][n]: sin, cos of each.
+ *                              Domain of the pair: within 1.3 ulp of the true value for |x| <= 1e6 rad (held by the tests at the C
+ *                              library's own error + 2 ulp) and, measured, within 1.1 ulp up to 3.3e9; from |x| >= 2^31 pi/2
+ *                              (3.37e9 rad) the quadrant is taken from a saturated integer and the result is a finite number in
+ *                              [-1, 1] that has nothing to do with the argument.  No status bit reports it: phi, theta and psi have
+ *                              no envelope limit, and the caller keeps them in range.  NaN for a NaN or infinite argument.
+ *   f16_debug_elem_trig_carry  the pairs the rollouts carry from step to step: h_angle_and_steps [1 + n_steps][n] = a start angle per
+ *                              lane, then one increment per step and lane.  Full evaluation at the start angle, then per step
+ *                              angle += increment and one trig_advance (rotation by the increment taken back from the stored
+ *                              angle).  h_out [n_steps][4][n]: sin, cos, the stored angle, and trig_advance's verdict (1.0: the
+ *                              increment left the series' range |d| <= 4e-3, the caller re-evaluates) after every step.  The
+ *                              lane's other four angles stay 0, so a NaN increment gives the verdict 0.0: fmax drops a NaN beside a
+ *                              number.  1 <= n_steps <= 4096.
+ *   f16_debug_elem_atmos       h_alt_vt [2][n] = altitude [ft], airspeed [ft/s] (used as given: no 0.01 floor).  h_out [13][n]:
+ *                              tfac; then the factor exp(0.14 log tfac), mach, qbar, ps by the device library's exp / log
+ *                              (atmos_dev), by their restatement with the table in scalar registers (atmos_dev_k), and by the same
+ *                              with the table in vector registers.  The three routes agree bit for bit.
+ *   f16_debug_elem_rcp         h_out [n] = f16_rcp(x): the hardware reciprocal and two Newton steps, <= 1 ulp of 1/x for every normal
+ *                              finite x (NaN for 0, denormals and infinities).
+ *   f16_debug_elem_tan         h_out [3][n] = sin theta, cos theta, and tan theta as the plant forms it: sin theta * f16_rcp(cos theta). */
+int f16_debug_elem_sincos(f16_ctx *ctx, const double *h_x, long n, double *h_out);
+int f16_debug_elem_trig_carry(f16_ctx *ctx, const double *h_angle_and_steps, int n_steps, long n, double *h_out);
+int f16_debug_elem_atmos(f16_ctx *ctx, const double *h_alt_vt, long n, double *h_out);
+int f16_debug_elem_rcp(f16_ctx *ctx, const double *h_x, long n, double *h_out);
+int f16_debug_elem_tan(f16_ctx *ctx, const double *h_theta, long n, double *h_out);
+
 /* ---- (1) drop-in symbols of the reference .so ---------------------------------------------- */
 /* replaces C/nlplant.c:23  void Nlplant(double *xu, double *xdot, int fidelity)
  * host pointers; reads xu[0..16], writes xdot[0..17]; runs ONE aircraft on the GPU. */
