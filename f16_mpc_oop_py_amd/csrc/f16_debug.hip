@@ -16,6 +16,9 @@
 //                 registers as the quad rollout's G1 role holds it); the power factor by three routes with tfac, mach, qbar and ps
 //                 at a given airspeed; f16_rcp; tan as plant_pre forms it; and the sin/cos pairs carried from step to step by
 //                 trig_advance / trig_rotate.
+//   k_dbg_air_triple  the air triple of the plant in moving air (air_triple, f16_wind.hpp: what calc_xdot_wind evaluates in front of
+//                 its lookups) on given attitudes, ground triples, winds and gusts, for the multiprecision comparison of
+//                 tests/test_gpu_air.py: the cancellation in U - wb - g and the device's sqrt, atan2 and asin on their own.
 //   k_dbg_gain_lookup  the gain-schedule lookup over (h, V) of f16_rollout_lqr_gs (gain_lookup, f16_gain_sched.hpp) at given points:
 //                 the same bits as the host function and the numpy restatement.
 #include <hip/hip_runtime.h>
@@ -24,6 +27,7 @@
 #include "f16_ctx.h"
 #include "f16_plant.hpp"
 #include "f16_gain_sched.hpp"
+#include "f16_wind.hpp"
 
 namespace f16 {
 
@@ -195,6 +199,18 @@ __global__ __launch_bounds__(64) void k_dbg_elem_tan(const double *__restrict__ 
   }
 }
 #endif
+
+// in [12][n] = phi theta psi vt alpha beta | wN wE wD | g_x g_y g_z; out [6][n] = Ua Va Wa vt_a alpha_a beta_a
+__global__ __launch_bounds__(64) void k_dbg_air_triple(const double *__restrict__ in, double *__restrict__ out, long n) {
+  for (long p = (long)blockIdx.x * 64 + threadIdx.x; p < n; p += (long)gridDim.x * 64) {
+    double x[9], w[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { x[3 + k] = in[k * n + p]; w[k] = in[(6 + k) * n + p]; }
+    AirTriple a;
+    air_triple(x, [&](int k) { return w[k]; }, a);
+    out[p] = a.Ua; out[n + p] = a.Va; out[2 * n + p] = a.Wa; out[3 * n + p] = a.vt; out[4 * n + p] = a.alpha; out[5 * n + p] = a.beta;
+  }
+}
 
 // the gain-schedule lookup of the scheduled-gain rollouts (gain_lookup, f16_gain_sched.hpp) on its own: out [n][12]
 __global__ __launch_bounds__(64) void k_dbg_gain_lookup(f16_gain_grid g, const double *__restrict__ tab, const double *__restrict__ h,
@@ -375,4 +391,12 @@ extern "C" int f16_debug_elem_tan(f16_ctx *ctx, const double *h_theta, long n, d
 #else
   return set_error(F16_EINVAL, "f16_debug_elem_tan: this library was built without F16_FAST_DIV (IEEE division, one form only)");
 #endif
+}
+
+extern "C" int f16_debug_air_triple(f16_ctx *ctx, const double *h_in, long n, double *h_out) {
+  if (!ctx || !h_in || !h_out || n < 0) return set_error(F16_EINVAL, "bad argument to f16_debug_air_triple");
+  if (n == 0) return F16_OK;
+  return dbg_elem_run("f16_debug_air_triple", h_in, 12, n, h_out, 6, [&](dim3 grid, const double *in, double *out) {
+    hipLaunchKernelGGL(k_dbg_air_triple, grid, dim3(64), 0, nullptr, in, out, n);
+  });
 }

@@ -20,6 +20,26 @@
 
 namespace f16 {
 
+// The air triple of the rule above, alone: the statements calc_xdot_wind has always had, in their order (f16_debug_air_triple
+// launches it on its own against a multiprecision reference, tests/test_gpu_air.py).  x[3..8] are read; w(k) as in calc_xdot_wind.
+struct AirTriple { double Ua, Va, Wa, vt, alpha, beta; };
+template <typename W>
+F16_DEV void air_triple(const double *x, W w, AirTriple &a) {
+  Trig5 g;
+  trig_exact(x, g);
+  double vt = x[6];
+  if (vt <= 0.01) vt = 0.01;
+  const double U = vt * g.ca * g.cb, V = vt * g.sb, W_ = vt * g.sa * g.cb;
+  const double wn = w(0), we = w(1), wd = w(2);
+  const double wbx = g.ct * g.cpsi * wn + g.ct * g.spsi * we - g.st * wd;
+  const double wby = (g.sphi * g.st * g.cpsi - g.cphi * g.spsi) * wn + (g.sphi * g.st * g.spsi + g.cphi * g.cpsi) * we + g.sphi * g.ct * wd;
+  const double wbz = (g.cphi * g.st * g.cpsi + g.sphi * g.spsi) * wn + (g.cphi * g.st * g.spsi - g.sphi * g.cpsi) * we + g.cphi * g.ct * wd;
+  a.Ua = U - wbx - w(3); a.Va = V - wby - w(4); a.Wa = W_ - wbz - w(5);
+  a.vt = sqrt(a.Ua * a.Ua + a.Va * a.Va + a.Wa * a.Wa);
+  a.alpha = atan2(a.Wa, a.Ua);
+  a.beta = asin(a.Va / a.vt);
+}
+
 // env.py:65-103 `_calc_xdot` in moving air.  w(k), k = 0..5: {wN, wE, wD, g_x, g_y, g_z} of the lane, read where they are used (the
 // rollout kernels keep them in LDS slots).  The five sin / cos pairs are evaluated in front of the lookups, for the air triple, and
 // AGAIN behind them by plant_pre: ten doubles carried across the lookups were what pushed the Runge-Kutta step (72 doubles of state
@@ -32,19 +52,9 @@ F16_DEV void calc_xdot_wind(TP T, const double *__restrict__ LT, const double *x
 #pragma unroll
   for (int k = 0; k < 18; ++k) xa[k] = x[k];
   {
-    Trig5 g;
-    trig_exact(x, g);
-    double vt = x[6];
-    if (vt <= 0.01) vt = 0.01;
-    const double U = vt * g.ca * g.cb, V = vt * g.sb, W_ = vt * g.sa * g.cb;
-    const double wn = w(0), we = w(1), wd = w(2);
-    const double wbx = g.ct * g.cpsi * wn + g.ct * g.spsi * we - g.st * wd;
-    const double wby = (g.sphi * g.st * g.cpsi - g.cphi * g.spsi) * wn + (g.sphi * g.st * g.spsi + g.cphi * g.cpsi) * we + g.sphi * g.ct * wd;
-    const double wbz = (g.cphi * g.st * g.cpsi + g.sphi * g.spsi) * wn + (g.cphi * g.st * g.spsi - g.sphi * g.cpsi) * we + g.cphi * g.ct * wd;
-    const double Ua = U - wbx - w(3), Va = V - wby - w(4), Wa = W_ - wbz - w(5);
-    xa[6] = sqrt(Ua * Ua + Va * Va + Wa * Wa);
-    xa[7] = atan2(Wa, Ua);
-    xa[8] = asin(Va / xa[6]);
+    AirTriple a;
+    air_triple(x, w, a);
+    xa[6] = a.vt; xa[7] = a.alpha; xa[8] = a.beta;
   }
   Totals t;
   aero_totals<FI>(T, LT, xa, xcg, fi_flag, flags, t, status);

@@ -133,6 +133,11 @@ int f16_debug_elem_trig_carry(f16_ctx *ctx, const double *h_angle_and_steps, int
 int f16_debug_elem_atmos(f16_ctx *ctx, const double *h_alt_vt, long n, double *h_out);
 int f16_debug_elem_rcp(f16_ctx *ctx, const double *h_x, long n, double *h_out);
 int f16_debug_elem_tan(f16_ctx *ctx, const double *h_theta, long n, double *h_out);
+/* Tests (tests/test_gpu_air.py): the air triple of the plant in moving air (the rule under "STEADY WIND" below; csrc/f16_wind.hpp
+ * air_triple, the function calc_xdot_wind evaluates in front of its lookups) on its own, on n cases given on the HOST, for the
+ * comparison with a multiprecision reference.  h_in [12][n] = phi theta psi vt alpha beta (x[3..8]), then wN wE wD, then g_x g_y g_z;
+ * h_out [6][n] = Ua Va Wa vt_a alpha_a beta_a.  Synchronous; n == 0 is a no-op; every build has it. */
+int f16_debug_air_triple(f16_ctx *ctx, const double *h_in, long n, double *h_out);
 
 /* ---- (1) drop-in symbols of the reference .so ---------------------------------------------- */
 /* replaces C/nlplant.c:23  void Nlplant(double *xu, double *xdot, int fidelity)
@@ -436,7 +441,11 @@ int f16_rollout_mppi(f16_ctx *ctx, double *x, double *u, double *u_nom, const do
  *     velocity plus -omega x (wb + g_b), which is the body-axis derivative of a wind that is constant over the ground.
  *     The grid bits F16_ST_ALPHA1 .. F16_ST_EL come from the lookups, so from the air triple.  The 0.01 clamp applies to vt_a where
  *     the still-air code applies it to vt.  vt_a == 0 gives NaN by ordinary arithmetic (F16_ST_NONFINITE at write-back); a NaN wind
- *     or gust component propagates the same way.  Wind and gust are held over the four stages of a Runge-Kutta step, as the command is.
+ *     or gust component propagates the same way.  Where the flap model takes its V (utils.py:291) it takes the RAW vt_a, and clamps
+ *     for itself.  The default build's sin / cos pair gives sin(-0.0) = +0.0 (its fused reduction adds the -0.0 to a +0.0 product), so an
+ *     angle of -0.0 acts as +0.0; the one place the sign of that zero could show is the cut of atan2: flying backwards through the air
+ *     (Ua < 0) with alpha = -0.0 and Wa otherwise exactly zero gives alpha_a = +pi where a libm sine gives -pi.
+ *     Wind and gust are held over the four stages of a Runge-Kutta step, as the command is.
  *   f16_xdot_wind_batch: env.py:65-103 `_calc_xdot` under the rule.  wind[3][ld], gust[3][ld]: DEVICE, either may be NULL (= 0); both
  *     NULL forwards to f16_xdot_batch (that call's kernel, its bits).  F16_EINVAL as f16_xdot_batch.
  *   f16_rollout_wind is f16_rollout_rk, f16_rollout_lqr_wind is f16_rollout_lqr_rk under the rule (the controller reads the state,

@@ -172,7 +172,9 @@ double f16o_table(int tid, double alpha, double beta, double el) {
 
 /* ------------------------------------------------------------------ lofi */
 static int sgn(real v) { return (v > 0) - (v < 0); }
-static int fixi(real v) { return (int)trunc(v); }
+/* a NaN converts to 0, as the device's conversion does (the C conversion is undefined there, and on x86 gives INT_MIN: an index
+ * far outside every table).  csrc/f16_plant.hpp aero_lofi: "k, L and m, n stay inside ... for any input, NaN included". */
+static int fixi(real v) { return isnan(v) ? 0 : (int)trunc(v); }
 
 /* shared alpha index arithmetic, lofi_F16_AeroData.c:31-45 */
 static void lofi_alpha(real alpha, int *k, int *L, real *da) {
@@ -208,6 +210,7 @@ static void lofi_dmomdcon(real alpha, real beta, real *c) { /* :59-183 */
   int n = m + 1;
   m = m + 1; n = n + 1;
   if (n > 7) { n = 7; t_status |= F16O_ST_BETA; }  /* reference reads past the 7-row table at |beta|>=30 */
+  if (isnan(beta)) t_status |= F16O_ST_BETA;        /* the product's rule (aero_lofi): a NaN beta raises the bit as well */
   c[0] = lofi_bilin(L_dlda, m, n, k, L, da, db);
   c[1] = lofi_bilin(L_dldr, m, n, k, L, da, db);
   c[2] = lofi_bilin(L_dnda, m, n, k, L, da, db);
@@ -303,7 +306,12 @@ void accels(double *state, double *xdot, double *y) {
   for (int i = 0; i < 3; ++i) y[i] = (double)yy[i];
 }
 
-static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* nlplant.c:23-457 */
+/* nlplant.c:23-457 with each consumer of the velocity through the AIR handed its own number (include/f16_hip.h "STEADY WIND"):
+ *   vt_air    the speed of the atmosphere call (mach, qbar, ps)            vt_damp   the speed of the damping quotients cbar / (2 vt), B / (2 vt)
+ *   alpha_air, beta_air (rad)   the coordinates of the table lookups and of the coefficient build-up
+ * The GROUND triple xu[6..8] stays in the navigation equations and in the force equations.  In still air the four are the ground
+ * triple's (nlplant_r below: the same expressions on the same operands, so the fp64 build keeps its bits). */
+static void nlplant_air_r(const real *xu, real vt_air, real vt_damp, real alpha_air, real beta_air, real *xdot, int fi_flag, double xcg) {
   t_status = 0;
   const real g = 32.17, m = 636.94, B = 30.0, S = 300.0, cbar = 11.32, xcgr = 0.35;
   const real Heng = 0.0;
@@ -313,7 +321,7 @@ static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* 
 
   real alt = xu[2], phi = xu[3], theta = xu[4], psi = xu[5];
   real vt = xu[6];
-  real alpha = xu[7] * r2d, beta = xu[8] * r2d;
+  real alpha = alpha_air * r2d, beta = beta_air * r2d;
   real P = xu[9], Q = xu[10], R = xu[11];
   real sa = sin(xu[7]), ca = cos(xu[7]);
   real sb = sin(xu[8]), cb = cos(xu[8]);
@@ -327,7 +335,7 @@ static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* 
   real dlef = (1 - lef / 25.0);
 
   real at[3];
-  atmos_r(alt, vt, at);
+  atmos_r(alt, vt_air, at);
   real mach = at[0], qbar = at[1], ps = at[2];
 
   real U = vt * ca * cb, V = vt * sb, W = vt * sa * cb;
@@ -400,25 +408,25 @@ static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* 
   }
 
   /* totals, NASA TP-1538 p37-40 as written at nlplant.c:333-377 (quirk: dZdQ uses delta_Cz_lef) */
-  real dXdQ = (cbar / (2 * vt)) * (Cxq + delta_Cxq_lef * dlef);
+  real dXdQ = (cbar / (2 * vt_damp)) * (Cxq + delta_Cxq_lef * dlef);
   real Cx_tot = Cx + delta_Cx_lef * dlef + dXdQ * Q;
-  real dZdQ = (cbar / (2 * vt)) * (Czq + delta_Cz_lef * dlef);
+  real dZdQ = (cbar / (2 * vt_damp)) * (Czq + delta_Cz_lef * dlef);
   (void)delta_Czq_lef;
   real Cz_tot = Cz + delta_Cz_lef * dlef + dZdQ * Q;
-  real dMdQ = (cbar / (2 * vt)) * (Cmq + delta_Cmq_lef * dlef);
+  real dMdQ = (cbar / (2 * vt_damp)) * (Cmq + delta_Cmq_lef * dlef);
   real Cm_tot = Cm * eta_el + Cz_tot * (xcgr - xcg) + delta_Cm_lef * dlef + dMdQ * Q + delta_Cm + delta_Cm_ds;
   real dYdail = delta_Cy_a20 + delta_Cy_a20_lef * dlef;
-  real dYdR = (B / (2 * vt)) * (Cyr + delta_Cyr_lef * dlef);
-  real dYdP = (B / (2 * vt)) * (Cyp + delta_Cyp_lef * dlef);
+  real dYdR = (B / (2 * vt_damp)) * (Cyr + delta_Cyr_lef * dlef);
+  real dYdP = (B / (2 * vt_damp)) * (Cyp + delta_Cyp_lef * dlef);
   real Cy_tot = Cy + delta_Cy_lef * dlef + dYdail * dail + delta_Cy_r30 * drud + dYdR * R + dYdP * P;
   real dNdail = delta_Cn_a20 + delta_Cn_a20_lef * dlef;
-  real dNdR = (B / (2 * vt)) * (Cnr + delta_Cnr_lef * dlef);
-  real dNdP = (B / (2 * vt)) * (Cnp + delta_Cnp_lef * dlef);
+  real dNdR = (B / (2 * vt_damp)) * (Cnr + delta_Cnr_lef * dlef);
+  real dNdP = (B / (2 * vt_damp)) * (Cnp + delta_Cnp_lef * dlef);
   real Cn_tot = Cn + delta_Cn_lef * dlef - Cy_tot * (xcgr - xcg) * (cbar / B) + dNdail * dail + delta_Cn_r30 * drud
                   + dNdR * R + dNdP * P + delta_Cnbeta * beta;
   real dLdail = delta_Cl_a20 + delta_Cl_a20_lef * dlef;
-  real dLdR = (B / (2 * vt)) * (Clr + delta_Clr_lef * dlef);
-  real dLdP = (B / (2 * vt)) * (Clp + delta_Clp_lef * dlef);
+  real dLdR = (B / (2 * vt_damp)) * (Clr + delta_Clr_lef * dlef);
+  real dLdP = (B / (2 * vt_damp)) * (Clp + delta_Clp_lef * dlef);
   real Cl_tot = Cl + delta_Cl_lef * dlef + dLdail * dail + delta_Cl_r30 * drud + dLdR * R + dLdP * P + delta_Clbeta * beta;
 
   real Udot = R * V - Q * W - g * st + qbar * S * Cx_tot / m + T / m;
@@ -440,6 +448,12 @@ static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* 
   accels_r(xu, xdot, y);
   xdot[12] = y[0]; xdot[13] = y[1]; xdot[14] = y[2];
   xdot[15] = mach; xdot[16] = qbar; xdot[17] = ps;
+}
+
+static void nlplant_r(const real *xu, real *xdot, int fi_flag, double xcg) { /* nlplant.c:23-457: still air */
+  real vt = xu[6];
+  if (vt <= 0.01) vt = 0.01;
+  nlplant_air_r(xu, vt, vt, xu[7], xu[8], xdot, fi_flag, xcg);
 }
 
 void f16o_nlplant(const double *xu, double *xdot, int fi_flag, double xcg) {
@@ -742,6 +756,155 @@ void f16o_rollout_lqr(double *x, const double *u0, const double *K, const double
       if (traj) memcpy(traj + ((long)t * B + b) * 18, x + 18 * b, 18 * sizeof(double));
     }
     if (u_out) memcpy(u_out + 4 * b, u, sizeof u);
+    if (status) status[b] = st;
+  }
+}
+
+/* ------------------------------------------------------------- moving air */
+/* include/f16_hip.h "STEADY WIND" / csrc/f16_wind.hpp: calc_xdot_wind, on `real`.  air = {wN, wE, wD, g_x, g_y, g_z}.
+ * tri <- {Ua, Va, Wa, vt_a, alpha_a, beta_a}: the ground velocity in body axes from the clamped vt, minus C w_ned, minus the gust. */
+static void air_triple_r(const real *x, const real *air, real *tri) {
+  real sa = sin(x[7]), ca = cos(x[7]), sb = sin(x[8]), cb = cos(x[8]);
+  real st = sin(x[4]), ct = cos(x[4]), sphi = sin(x[3]), cphi = cos(x[3]), spsi = sin(x[5]), cpsi = cos(x[5]);
+  real vt = x[6];
+  if (vt <= 0.01) vt = 0.01;
+  real U = vt * ca * cb, V = vt * sb, W = vt * sa * cb;
+  real wn = air[0], we = air[1], wd = air[2];
+  real wbx = ct * cpsi * wn + ct * spsi * we - st * wd;
+  real wby = (sphi * st * cpsi - cphi * spsi) * wn + (sphi * st * spsi + cphi * cpsi) * we + sphi * ct * wd;
+  real wbz = (cphi * st * cpsi + sphi * spsi) * wn + (cphi * st * spsi - sphi * cpsi) * we + cphi * ct * wd;
+  real Ua = U - wbx - air[3], Va = V - wby - air[4], Wa = W - wbz - air[5];
+  tri[0] = Ua; tri[1] = Va; tri[2] = Wa;
+  tri[3] = sqrt(Ua * Ua + Va * Va + Wa * Wa);
+  tri[4] = atan2(Wa, Ua);
+  tri[5] = asin(Va / tri[3]);
+}
+
+/* env.py:65-103 with every consumer of the air triple given its own copy: parts = {vt of the atmosphere call, vt of the damping
+ * quotients, alpha and beta of the lookups, V and alpha of the leading-edge-flap model}.  THE RULE is parts_of_rule() below; the
+ * tests state deliberately wrong rules through the same entry (tests/test_air_cpu.py). */
+static void calc_xdot_parts_r(const real *x, const real *u, const real *parts, real *xdot, int fi_flag, double xcg) {
+  real t0 = clipd(clipd(u[0], 1000, 19000) - x[12], -10000, 10000);
+  real t1 = clipd(20.2 * (clipd(u[1], -25, 25) - x[13]), -60, 60);
+  real t2 = clipd(20.2 * (clipd(u[2], -21.5, 21.5) - x[14]), -80, 80);
+  real t3 = clipd(20.2 * (clipd(u[3], -30., 30) - x[15]), -120, 120);
+  real lf1_dot, lf2_dot;
+  upd_lef(x[2], parts[4], parts[5], x[17], x[16], &lf1_dot, &lf2_dot);
+  nlplant_air_r(x, parts[0], parts[1], parts[2], parts[3], xdot, fi_flag, xcg);
+  xdot[12] = t0; xdot[13] = t1; xdot[14] = t2; xdot[15] = t3;
+  xdot[16] = lf2_dot; xdot[17] = lf1_dot;
+}
+
+/* the 0.01 clamp applies to vt_a where the still-air code applies it to vt: the atmosphere call and the damping quotients take the
+ * clamped speed, the flap model the raw one (upd_lef takes its V as it is, utils.py:291) */
+static void parts_of_rule(const real *tri, real *parts) {
+  real vc = tri[3];
+  if (vc <= 0.01) vc = 0.01;
+  parts[0] = vc; parts[1] = vc; parts[2] = tri[4]; parts[3] = tri[5]; parts[4] = tri[3]; parts[5] = tri[4];
+}
+
+static void calc_xdot_wind_r(const real *x, const real *u, const real *air, real *xdot, real *tri_out, int fi_flag, double xcg) {
+  real tri[6], parts[6];
+  air_triple_r(x, air, tri);
+  parts_of_rule(tri, parts);
+  calc_xdot_parts_r(x, u, parts, xdot, fi_flag, xcg);
+  if (tri_out) memcpy(tri_out, tri, sizeof tri);
+}
+
+void f16o_xdot_wind_batch(const double *x, const double *u, const double *air, long B, f16o_real *out, f16o_real *triple, int *status,
+                          int fi_flag, double xcg) {
+  f16o_init();
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (long b = 0; b < B; ++b) {
+    real xr[18], ur[4], ar[6];
+    for (int i = 0; i < 18; ++i) xr[i] = x[18 * b + i];
+    for (int i = 0; i < 4; ++i) ur[i] = u[4 * b + i];
+    for (int i = 0; i < 6; ++i) ar[i] = air[6 * b + i];
+    calc_xdot_wind_r(xr, ur, ar, out + 18 * b, triple ? triple + 6 * b : NULL, fi_flag, xcg);
+    if (status) status[b] = t_status;
+  }
+}
+
+void f16o_xdot_air_parts_batch(const double *x, const double *u, const f16o_real *parts, long B, f16o_real *out, int *status, int fi_flag,
+                               double xcg) {
+  f16o_init();
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (long b = 0; b < B; ++b) {
+    real xr[18], ur[4];
+    for (int i = 0; i < 18; ++i) xr[i] = x[18 * b + i];
+    for (int i = 0; i < 4; ++i) ur[i] = u[4 * b + i];
+    calc_xdot_parts_r(xr, ur, parts + 6 * b, out + 18 * b, fi_flag, xcg);
+    if (status) status[b] = t_status;
+  }
+}
+
+static int envelope_bits_r(const real *x) {   /* f16o_envelope_bits on `real` */
+  int out = 0;
+  for (int i = 0; i < 18; ++i)
+    if (x[i] < X_LB[i] || x[i] > X_UB[i]) out |= F16O_ST_ENVELOPE | (1 << (8 + i));
+  return out;
+}
+
+void f16o_rollout_wind(const double *x0, const double *rows, const double *K, const double *u0, const double *wind, const double *gust,
+                       long B, int nsteps, int hold, int gust_hold, double dt, int method, int fi_flag, double xcg,
+                       f16o_real *x_out, f16o_real *traj, f16o_real *u_out, int *status) {
+  f16o_init();
+  const int nr = K ? 3 : 4;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static)
+#endif
+  for (long b = 0; b < B; ++b) {
+    real x[18], u[4], ul[4], air[6] = {0, 0, 0, 0, 0, 0};
+    int st = status ? status[b] : 0;
+    for (int i = 0; i < 18; ++i) x[i] = x0[18 * b + i];
+    for (int i = 0; i < 4; ++i) ul[i] = K ? u0[4 * b + i] : rows[4 * b + i];
+    if (wind) for (int i = 0; i < 3; ++i) air[i] = wind[3 * b + i];
+    for (int t = 0; t < nsteps; ++t) {
+      if (!(st & F16O_ST_ENVELOPE)) st |= envelope_bits_r(x);
+      if (!(st & F16O_ST_ENVELOPE)) {
+        const double *row = rows + ((long)(t / hold) * B + b) * nr;
+        if (gust) for (int i = 0; i < 3; ++i) air[3 + i] = gust[((long)(t / gust_hold) * B + b) * 3 + i];
+        if (K) {   /* env.py:360-371 as the kernels form it: the three demanded rates against x[9..11] */
+          real e0 = row[0] - x[9], e1 = row[1] - x[10], e2 = row[2] - x[11];
+          u[0] = u0[4 * b];
+          for (int i = 0; i < 3; ++i)
+            u[1 + i] = (((-K[27 * b + 9 * i + 4]) * e0 + (-K[27 * b + 9 * i + 5]) * e1) + (-K[27 * b + 9 * i + 6]) * e2) + u0[4 * b + 1 + i];
+        } else {
+          for (int i = 0; i < 4; ++i) u[i] = row[i];
+        }
+        memcpy(ul, u, sizeof ul);
+        real xd[18];
+        if (method == 4) {
+          const real h2 = (real)0.5 * dt, h6 = (real)dt / 6.0;
+          real xs[18], s1[18], s2[18];
+          memcpy(xs, x, sizeof xs);
+          for (int s = 0; s < 4; ++s) {
+            calc_xdot_wind_r(xs, u, air, xd, NULL, fi_flag, xcg);
+            st |= t_status;
+            const real c = s == 2 ? (real)dt : h2;
+            for (int k = 0; k < 18; ++k) {
+              if (s == 0) s1[k] = xd[k];
+              else if (s == 1) s1[k] += 2.0 * xd[k];
+              else if (s == 2) s2[k] = 2.0 * xd[k];
+              else s2[k] += xd[k];
+              xs[k] = x[k] + c * xd[k];
+            }
+          }
+          for (int k = 0; k < 18; ++k) x[k] += h6 * (s1[k] + s2[k]);
+        } else {
+          calc_xdot_wind_r(x, u, air, xd, NULL, fi_flag, xcg);
+          st |= t_status;
+          for (int k = 0; k < 18; ++k) x[k] += xd[k] * dt;
+        }
+      }
+      if (traj) memcpy(traj + ((long)t * B + b) * 18, x, sizeof x);
+    }
+    memcpy(x_out + 18 * b, x, sizeof x);
+    if (u_out) memcpy(u_out + 4 * b, ul, sizeof ul);
     if (status) status[b] = st;
   }
 }

@@ -79,6 +79,32 @@ void f16o_linearise_na_batch(const double *x, const double *u, long B, double ep
 void f16o_linearise_full_batch(const double *x, const double *u, long B, double eps, f16o_real *A, f16o_real *Bm, f16o_real *C,
                                int *status, int fi_flag, double xcg);
 
+/* The plant in MOVING AIR (include/f16_hip.h "STEADY WIND", csrc/f16_wind.hpp: calc_xdot_wind), written on f16o_real like the rest:
+ * the ground U, V, W from the clamped vt, wb = C w_ned, (Ua, Va, Wa), vt_a = sqrt(..), alpha_a = atan2(Wa, Ua), beta_a = asin(Va /
+ * vt_a); the air triple feeds the lookups and the coefficient build-up, the damping quotients and the atmosphere call (vt_a clamped
+ * at 0.01) and the flap model (the raw vt_a); the ground triple stays in the kinematics and the force equations.  ONE evaluation of
+ * the plant, not two still-air evaluations and a reconstruction.
+ *   x [B][18], u [B][4], air [B][6] = wN wE wD g_x g_y g_z -> out [B][18]; triple (may be NULL) [B][6] = Ua Va Wa vt_a alpha_a beta_a;
+ *   status (may be NULL) [B] = the grid bits of the lookups.  Results in the build's own type, never rounded on the way. */
+void f16o_xdot_wind_batch(const double *x, const double *u, const double *air, long B, f16o_real *out, f16o_real *triple, int *status,
+                          int fi_flag, double xcg);
+/* The same derivative with every consumer of the air triple handed its own copy: parts [B][6] = {vt of the atmosphere call, vt of
+ * the damping quotients, alpha and beta of the lookups, V and alpha of the flap model}.  The rule is (max(vt_a, 0.01), max(vt_a,
+ * 0.01), alpha_a, beta_a, vt_a, alpha_a); tests/test_air_cpu.py states deliberately WRONG rules through this entry to show that the
+ * comparison can fail. */
+void f16o_xdot_air_parts_batch(const double *x, const double *u, const f16o_real *parts, long B, f16o_real *out, int *status, int fi_flag,
+                               double xcg);
+/* nsteps steps of B aircraft in moving air, method 1 = Euler (env.py:126), 4 = classical Runge-Kutta (x + (dt/6) ((k1 + 2 k2) + (2 k3
+ * + k4))), the box test of env.py:117-124 in front of every step as in f16o_step (a frozen aircraft keeps its state).  x0 [B][18];
+ * rows [S][B][4] commands, step t reads row t / hold -- or, with K [B][27] and u0 [B][4] given, rows [S][B][3] demanded rates and the
+ * action of env.py:360-371 from the state at the start of the step; wind [B][3] (NULL = 0) constant; gust [Sg][B][3] (NULL = 0), step
+ * t reads row t / gust_hold; wind, gust and command held over the four stages.  The state stays in f16o_real between steps and is
+ * handed back so: x_out [B][18], traj (may be NULL) [nsteps][B][18], u_out (may be NULL) [B][4] the action of the last step taken.
+ * status [B] in / out, sticky: grid bits of every evaluation | f16o_envelope_bits. */
+void f16o_rollout_wind(const double *x0, const double *rows, const double *K, const double *u0, const double *wind, const double *gust,
+                       long B, int nsteps, int hold, int gust_hold, double dt, int method, int fi_flag, double xcg,
+                       f16o_real *x_out, f16o_real *traj, f16o_real *u_out, int *status);
+
 /* batched helpers (row-major [B][18] / [B][4]); nthreads<=1 => serial. traj may be NULL,
  * else [T][B][18] filled after every step. status[B] in/out (sticky). */
 void f16o_xdot_batch(const double *x, const double *u, double *xdot, long B, int fi_flag, double xcg, int nthreads);

@@ -26,7 +26,7 @@ def test_every_entry_point_with_a_leading_dimension_has_a_row_or_a_named_test():
     syms = lc.contract_symbols(fns)
     assert "f16_rollout" in syms and "f16_mpc_plan_solve" in syms and "f16_rollout_mpc" in syms and len(syms) >= 52
     assert "f16_mpc_plan_warm_start" not in syms and "f16_mpc_plan_soft_rows" not in syms and "f16_debug_sincos" not in syms
-    assert not [s for s in syms if s.startswith("f16_debug_elem_")]               # host-pointer test entries: no leading dimension
+    assert not [s for s in syms if s.startswith("f16_debug_elem_") or s == "f16_debug_air_triple"]   # host-pointer test entries: no leading dimension
     assert not uncovered(fns), f"no row in tests/layout_cases.py and no padded test named for: {uncovered(fns)}"
     assert not set(lc.ROWS) & set(lc.COVERED_ELSEWHERE)
     stray = [s for s in list(lc.ROWS) + list(lc.COVERED_ELSEWHERE) if s not in syms]

@@ -20,8 +20,9 @@ def test_library_exports_every_declared_symbol():
     so = lib.build()
     L = ctypes.CDLL(so)
     syms = declared_symbols()
-    assert "Nlplant" in syms and "atmos" in syms and "f16_rollout" in syms and len(syms) >= 76
-    assert {"f16_debug_elem_sincos", "f16_debug_elem_trig_carry", "f16_debug_elem_atmos", "f16_debug_elem_rcp", "f16_debug_elem_tan"} <= set(syms)
+    assert "Nlplant" in syms and "atmos" in syms and "f16_rollout" in syms and len(syms) >= 77
+    assert {"f16_debug_elem_sincos", "f16_debug_elem_trig_carry", "f16_debug_elem_atmos", "f16_debug_elem_rcp", "f16_debug_elem_tan",
+            "f16_debug_air_triple"} <= set(syms)
     missing = [s for s in syms if not hasattr(L, s)]
     assert not missing, missing
     assert set(cabi.functions()) == set(syms)

@@ -13,6 +13,8 @@ wind_cases.band: the factor 1 + e_rec / 2^-52 with e_rec = |twin(zero wind) - or
 CPU number, reference against reference.  Over the batches used here e_rec has median 6e-16..9e-16 and maximum 8.6e-14 (tests/
 test_wind_cpu.py prints them), so the factors are 4 to 5 for the typical aircraft and at most 390: 5e-9 typical, 3.9e-7 at most for
 a rollout.  At least 90 % of every batch is compared (asserted; the twin alone gives 98 % and more).
+The numerical pin of the moving-air derivative is tests/test_gpu_air.py (the `long double` plant, 8 Y, no row left out); this module
+keeps the contracts between kernels and the comparison with the twin.
 """
 import ctypes
 import os
