@@ -48,6 +48,7 @@ extern "C" int f16_create(f16_ctx **out, int device) {
   build_table_image_i32(img32.data());
   f16_ctx *c = new f16_ctx();
   c->device = device;
+  if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) c->cus = 0;
   if ((rc = hip_check(hipMalloc(&c->d_tab, sizeof(double) * TABLE_IMAGE_DOUBLES), "hipMalloc tables")) ||
       (rc = hip_check(hipMalloc(&c->d_lofi, sizeof(double) * LOFI_IMAGE_DOUBLES), "hipMalloc lofi")) ||
       (rc = hip_check(hipMalloc(&c->d_tab32, sizeof(int32_t) * i32::IMAGE_INTS), "hipMalloc tables (int)")) ||

@@ -6,7 +6,9 @@
 //   k_rollout_lqr_relin  test_env.py:625-687: the four above + step, per step, T steps       f16_rollout_lqr_relin
 //   k_mpc         utils.py:21-167 setup_OSQP + the OSQP solve of env.py:420-424            f16_mpc_batch
 //
-// Mapping.  k_linearise: one lane per (aircraft, perturbed column), tables in LDS as in the dynamics kernels.
+// Mapping.  k_linearise: one lane per (aircraft, perturbed column), tables in LDS as in the dynamics kernels.  The rule of the reduced
+// model -- the MPC-state map, the column map, and for the per-step loops the whole wave-level linearisation -- is f16_linearise.hpp's,
+// one definition for k_linearise, k_rollout_lqr_relin, k_mpc and the re-linearising MPC loop of f16_mpc_wave.hip.
 // The other three: ONE WAVEFRONT PER AIRCRAFT (workgroup = 64 lanes); all per-aircraft matrices live in LDS:
 // 9x9 blocks row-major, the 3N x 3N KKT inverse as a packed lower triangle (conflict-free row reads, see
 // f16_smallmat.hpp).  The 9N x 3N prediction matrix CC of utils.py:171-197 is never formed: CC[i,j] = A^(i-j) B,
@@ -29,6 +31,7 @@
 #include "f16_mpc_model.hpp"
 #include "f16_mpc_state.hpp"
 #include "f16_osqp_rules.hpp"
+#include "f16_linearise.hpp"
 
 namespace f16 {
 
@@ -46,12 +49,7 @@ struct LinArgs {
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_linearise(LinArgs a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
-  if (a.fi == 1) {
-    const double2 *src = reinterpret_cast<const double2 *>(a.tab);
-    double2 *dst = reinterpret_cast<double2 *>(tab);
-    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += BLOCK) dst[i] = src[i];
-    __syncthreads();
-  }
+  if (a.fi == 1) stage_tables<BLOCK>(tab, a.tab);
   const long total = a.B * 12;
   for (long e = (long)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (long)gridDim.x * BLOCK) {
     const int c = (int)(e / a.B);          // perturbed column: 0..8 MPC states, 9..11 inputs
@@ -61,9 +59,7 @@ __global__ __launch_bounds__(BLOCK) void k_linearise(LinArgs a) {
     for (int k = 0; k < 18; ++k) sv[k] = a.x[k * a.ld + b];
     // env.py:175-177: the three MPC inputs (u.values[1:4]) overwrite the actuator positions
     sv[13] = a.u[1 * a.ld + b]; sv[14] = a.u[2 * a.ld + b]; sv[15] = a.u[3 * a.ld + b];
-    // column -> full-state index: mpc_x_idx = [3,4,7,8,9,10,11,17,16], inputs -> [13,14,15]
-    const int idx = c == 0 ? 3 : c == 1 ? 4 : c == 2 ? 7 : c == 3 ? 8 : c == 4 ? 9 : c == 5 ? 10 : c == 6 ? 11
-                  : c == 7 ? 17 : c == 8 ? 16 : 13 + (c - 9);
+    const int idx = lin_na_index(c);       // column -> full-state index (f16_linearise.hpp)
     double base = 0.0, pert = 0.0;
 #pragma unroll
     for (int k = 0; k < 18; ++k) {
@@ -76,11 +72,10 @@ __global__ __launch_bounds__(BLOCK) void k_linearise(LinArgs a) {
     if (c < 9) {
       // env.py:331 with _get_obs_na: row r of C is (x9[r] + dx[r] - x9[r]) / eps.  Off the diagonal dx[r] = 0: x - x is an exact
       // zero for a finite state and NaN for a NaN or infinite one (the whole row of such a state is NaN in the reference)
-      const int ROW[9] = {3, 4, 7, 8, 9, 10, 11, 17, 16};
 #pragma unroll
       for (int r = 0; r < 9; ++r) {
         a.Ac[(r * 9 + c) * a.ld + b] = (f1[r] - f0[r]) / a.eps;
-        a.Cc[(r * 9 + c) * a.ld + b] = r == c ? (pert - base) / a.eps : sv[ROW[r]] - sv[ROW[r]];
+        a.Cc[(r * 9 + c) * a.ld + b] = r == c ? (pert - base) / a.eps : sv[mpc_x_index(r)] - sv[mpc_x_index(r)];
       }
     } else {
 #pragma unroll
@@ -94,12 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_linearise(LinArgs a) {
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_linearise_full(LinArgs a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
-  if (a.fi == 1) {
-    const double2 *src = reinterpret_cast<const double2 *>(a.tab);
-    double2 *dst = reinterpret_cast<double2 *>(tab);
-    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += BLOCK) dst[i] = src[i];
-    __syncthreads();
-  }
+  if (a.fi == 1) stage_tables<BLOCK>(tab, a.tab);
   const long total = a.B * 22;
   for (long e = (long)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (long)gridDim.x * BLOCK) {
     const int c = (int)(e / a.B);          // 0..17 states, 18..21 inputs
@@ -186,8 +176,7 @@ __global__ __launch_bounds__(64, 3) void k_lqr(LqrArgs a) {
     load_soa(A, a.Ad, 81, a.ld, b);
     load_soa(Bm, a.Bd, 27, a.ld, b);
     load_soa(C, a.Cd, 81, a.ld, b);
-    if (a.pb.custom_q) { for (int e = lane_id(); e < 81; e += F16_WAVE) Q[e] = a.pb.Q[e]; __syncthreads(); }      // utils.py:219 `Q`
-    else mm<true, false>(Q, C, C, 9, 9, 9);            // Q = C'C (env.py:353)
+    mpc_model_q(Q, C, a, lane_id());                   // Q = C'C (env.py:353) or utils.py:219 `Q`
     const int it = dare_sda_wave(A, Bm, Q, X, scr, a.pb.custom_r ? a.pb.Rinv : nullptr);
     lqr_gain_wave(A, Bm, X, K, scr, a.pb.custom_r ? a.pb.R : nullptr);
     for (int e = lane_id(); e < 27; e += F16_WAVE) a.K[e * a.ld + b] = -K[e];   // K = -dlqr(...) (env.py:356)
@@ -233,9 +222,6 @@ __global__ __launch_bounds__(64, F16_RELIN_MIN_WAVES) void k_rollout_lqr_relin(R
   double *F = al.take(13 * 9), *A = al.take(81), *Bm = al.take(27), *Ad = al.take(81), *Bd = al.take(27), *Q = al.take(81);
   double *X = al.take(81), *K = al.take(27), *cd = al.take(9), *scr = al.take(RELIN_SCRATCH);
   const int l = lane_id();
-  // column -> full-state index (k_linearise): mpc_x_idx = [3,4,7,8,9,10,11,17,16], inputs -> [13,14,15]; lane 12: the base point
-  const int idx = l == 0 ? 3 : l == 1 ? 4 : l == 2 ? 7 : l == 3 ? 8 : l == 4 ? 9 : l == 5 ? 10 : l == 6 ? 11
-                : l == 7 ? 17 : l == 8 ? 16 : l < 12 ? 13 + (l - 9) : -1;
   for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
     if (l < 18) xs[l] = a.x[l * a.ld + b];
     if (l < 4) us[l] = a.u[l * a.ld + b];
@@ -259,26 +245,7 @@ __global__ __launch_bounds__(64, F16_RELIN_MIN_WAVES) void k_rollout_lqr_relin(R
       if (!(a.flags & FLAG_NO_ENVELOPE) && outside_envelope(xs)) st |= ST_ENVELOPE;      // env.py:117-124
       if (!(st & ST_ENVELOPE)) {
         // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps)
-        if (l < 13) {
-          double sv[18], f[9];
-#pragma unroll
-          for (int k = 0; k < 18; ++k) sv[k] = xs[k];
-          sv[13] = us[1]; sv[14] = us[2]; sv[15] = us[3];      // env.py:175-177
-          double base = 0.0, pert = 0.0;
-#pragma unroll
-          for (int k = 0; k < 18; ++k)
-            if (k == idx) { base = sv[k]; pert = sv[k] + a.eps; sv[k] = pert; }
-          int sl = 0;      // (the grid bits of the perturbed points are not the aircraft's: _calc_LQR_gain does not keep them)
-          xdot_na_exact(a.tab, a.lofi, sv, f, a.xcg, a.fi, a.flags, &sl);
-#pragma unroll
-          for (int r = 0; r < 9; ++r) F[l * 9 + r] = f[r];
-          if (l < 9) cd[l] = (pert - base) / a.eps;
-        }
-        __syncthreads();
-        for (int e = l; e < 108; e += F16_WAVE) {
-          if (e < 81) { const int r = e / 9, c = e - r * 9; A[e] = (F[c * 9 + r] - F[12 * 9 + r]) / a.eps; }
-          else { const int e2 = e - 81, r = e2 / 3, c = e2 - r * 3; Bm[e2] = (F[(9 + c) * 9 + r] - F[12 * 9 + r]) / a.eps; }
-        }
+        linearise_na_wave(a.tab, a.lofi, xs, us[1], us[2], us[3], a.eps, a.xcg, a.fi, a.flags, F, A, Bm, cd, l);
         for (int e = l; e < 81; e += F16_WAVE) {
           const int i = e / 9, j = e - i * 9;
           Q[e] = a.pb.custom_q ? a.pb.Q[e] : (i == j ? cd[i] * cd[i] : 0.0);              // Q = C'C (env.py:353), C diagonal
@@ -293,8 +260,7 @@ __global__ __launch_bounds__(64, F16_RELIN_MIN_WAVES) void k_rollout_lqr_relin(R
           double s = 0.0;
 #pragma unroll
           for (int j = 0; j < 9; ++j) {
-            const int k = j == 0 ? 3 : j == 1 ? 4 : j == 2 ? 7 : j == 3 ? 8 : j == 4 ? 9 : j == 5 ? 10 : j == 6 ? 11 : j == 7 ? 17 : 16;
-            const double x9 = xs[k];
+            const double x9 = xs[mpc_x_index(j)];
             s += K[l * 9 + j] * (x9 - (((a.track >> j) & 1u) ? xr[j] : x9));
           }
           us[1 + l] = -s + u0[l];
@@ -411,8 +377,7 @@ __global__ __launch_bounds__(64, SETUP_ONLY ? 2 : 1) void k_mpc(MpcArgs a) {
     mpc_model_q(Q, Qb, a, l);                                // Q = C'C (env.py:389) or utils.py:21 `Q`; the model part: f16_mpc_model.hpp
     }
     if (l < 9) {
-      const int MX[9] = {3, 4, 7, 8, 9, 10, 11, 17, 16};
-      const double v = a.x ? a.x[MX[l] * a.ld + b] : 0.0;            // (no state when a plan is prepared)
+      const double v = a.x ? a.x[mpc_x_index(l) * a.ld + b] : 0.0;   // (no state when a plan is prepared)
       x9[l] = v;
       xref[l] = a.xref ? a.xref[l * a.ld + b]                                  // utils.py:21 `x_ref` as the caller gives it
                        : ((l >= 5 && l < 8 && a.dem) ? a.dem[(l - 5) * a.ld + b] : v);   // env.py:380-383 (x_ref[5:8] = demands)
@@ -715,56 +680,73 @@ static size_t mpc_lds_doubles(int N, bool setup_only, bool big = false) {      /
 
 using namespace f16;
 
+// F16_EINVAL with a formatted message (the entry points that share a launcher name themselves in theirs)
+__attribute__((format(printf, 1, 2))) static int einval(const char *fmt, ...) {
+  char msg[384];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, sizeof msg, fmt, ap);
+  va_end(ap);
+  return set_error(F16_EINVAL, msg);
+}
+
+// the launch of `name` as hip_check reports it: "<name> launch"
+static int launch_check(const char *name) {
+  char msg[64];
+  snprintf(msg, sizeof msg, "%s launch", name);
+  return hip_check(hipGetLastError(), msg);
+}
+
+// One lane per (aircraft, column): up to 64 x 256 lanes workgroups of 64, beyond that at most 256 workgroups of 256 in a grid-stride loop.
+static int linearise_launch(const char *name, void (*k64)(LinArgs), void (*k256)(LinArgs), int cols, f16_ctx *ctx, const double *x,
+                            const double *u, double *Ac, double *Bc, double *Cc, int32_t *status, long B, long ld, double eps,
+                            double xcg, int fi_flag, unsigned flags, void *stream) {
+  if (!ctx || !x || !u || !Ac || !Bc || !Cc || B < 0 || ld < B) return einval("bad argument to %s", name);
+  if (B == 0) return F16_OK;
+  LinArgs a{ctx->d_tab, ctx->d_lofi, x, u, Ac, Bc, Cc, status, B, ld, eps, xcg, fi_flag, flags};
+  const long lanes = B * cols;
+  if (lanes <= 64L * 256) {
+    hipLaunchKernelGGL(k64, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  } else {
+    long blocks = (lanes + 255) / 256;
+    hipLaunchKernelGGL(k256, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, (hipStream_t)stream, a);
+  }
+  return launch_check(name);
+}
+
 extern "C" int f16_linearise_batch(f16_ctx *ctx, const double *x, const double *u, double *Ac, double *Bc, double *Cc,
                                    int32_t *status, long B, long ld, double eps, double xcg, int fi_flag, unsigned flags,
                                    void *stream) {
-  if (!ctx || !x || !u || !Ac || !Bc || !Cc || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_linearise_batch");
-  if (B == 0) return F16_OK;
-  LinArgs a{ctx->d_tab, ctx->d_lofi, x, u, Ac, Bc, Cc, status, B, ld, eps, xcg, fi_flag, flags};
-  const long lanes = B * 12;
-  if (lanes <= 64L * 256) {
-    hipLaunchKernelGGL(k_linearise<64>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  } else {
-    long blocks = (lanes + 255) / 256;
-    hipLaunchKernelGGL(k_linearise<256>, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  return hip_check(hipGetLastError(), "f16_linearise_batch launch");
-}
-
-static unsigned wave_grid(long B) { return (unsigned)(B < 256L * 32 ? B : 256L * 32); }
-
-extern "C" int f16_c2d_batch(f16_ctx *ctx, const double *Ac, const double *Bc, double *Ad, double *Bd, long B, long ld,
-                             double dt, void *stream) {
-  if (!ctx || !Ac || !Bc || !Ad || !Bd || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_c2d_batch");
-  if (B == 0) return F16_OK;
-  C2dArgs a{Ac, Bc, Ad, Bd, B, ld, dt};
-  hipLaunchKernelGGL((k_c2d<9, 3>), dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
-  return hip_check(hipGetLastError(), "f16_c2d_batch launch");
+  return linearise_launch("f16_linearise_batch", k_linearise<64>, k_linearise<256>, 12, ctx, x, u, Ac, Bc, Cc, status, B, ld, eps, xcg,
+                          fi_flag, flags, stream);
 }
 
 extern "C" int f16_linearise_full_batch(f16_ctx *ctx, const double *x, const double *u, double *Ac, double *Bc, double *Cc,
                                         int32_t *status, long B, long ld, double eps, double xcg, int fi_flag, unsigned flags,
                                         void *stream) {
-  if (!ctx || !x || !u || !Ac || !Bc || !Cc || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_linearise_full_batch");
+  return linearise_launch("f16_linearise_full_batch", k_linearise_full<64>, k_linearise_full<256>, 22, ctx, x, u, Ac, Bc, Cc, status, B,
+                          ld, eps, xcg, fi_flag, flags, stream);
+}
+
+static unsigned wave_grid(long B) { return (unsigned)(B < 256L * 32 ? B : 256L * 32); }
+
+static int c2d_launch(const char *name, void (*k)(C2dArgs), f16_ctx *ctx, const double *Ac, const double *Bc, double *Ad, double *Bd,
+                      long B, long ld, double dt, void *stream) {
+  if (!ctx || !Ac || !Bc || !Ad || !Bd || B < 0 || ld < B) return einval("bad argument to %s", name);
   if (B == 0) return F16_OK;
-  LinArgs a{ctx->d_tab, ctx->d_lofi, x, u, Ac, Bc, Cc, status, B, ld, eps, xcg, fi_flag, flags};
-  const long lanes = B * 22;
-  if (lanes <= 64L * 256) {
-    hipLaunchKernelGGL(k_linearise_full<64>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
-  } else {
-    long blocks = (lanes + 255) / 256;
-    hipLaunchKernelGGL(k_linearise_full<256>, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(256), 0, (hipStream_t)stream, a);
-  }
-  return hip_check(hipGetLastError(), "f16_linearise_full_batch launch");
+  C2dArgs a{Ac, Bc, Ad, Bd, B, ld, dt};
+  hipLaunchKernelGGL(k, dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
+  return launch_check(name);
+}
+
+extern "C" int f16_c2d_batch(f16_ctx *ctx, const double *Ac, const double *Bc, double *Ad, double *Bd, long B, long ld,
+                             double dt, void *stream) {
+  return c2d_launch("f16_c2d_batch", k_c2d<9, 3>, ctx, Ac, Bc, Ad, Bd, B, ld, dt, stream);
 }
 
 extern "C" int f16_c2d_full_batch(f16_ctx *ctx, const double *Ac, const double *Bc, double *Ad, double *Bd, long B, long ld,
                                   double dt, void *stream) {
-  if (!ctx || !Ac || !Bc || !Ad || !Bd || B < 0 || ld < B) return set_error(F16_EINVAL, "bad argument to f16_c2d_full_batch");
-  if (B == 0) return F16_OK;
-  C2dArgs a{Ac, Bc, Ad, Bd, B, ld, dt};
-  hipLaunchKernelGGL((k_c2d<18, 4>), dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
-  return hip_check(hipGetLastError(), "f16_c2d_full_batch launch");
+  return c2d_launch("f16_c2d_full_batch", k_c2d<18, 4>, ctx, Ac, Bc, Ad, Bd, B, ld, dt, stream);
 }
 
 // Weights and bounds as the caller gives them (utils.py:21, :219) -> the kernels' MpcProb; null = env.py's constants.
@@ -855,16 +837,6 @@ extern "C" int f16_lqr_batch(f16_ctx *ctx, const double *Ad, const double *Bd, c
   return f16_lqr_batch_w(ctx, Ad, Bd, Cd, nullptr, K, Pare, status, B, ld, stream);
 }
 
-// F16_EINVAL with a formatted message (the closed-loop entry points name themselves in theirs)
-__attribute__((format(printf, 1, 2))) static int einval(const char *fmt, ...) {
-  char msg[384];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(msg, sizeof msg, fmt, ap);
-  va_end(ap);
-  return set_error(F16_EINVAL, msg);
-}
-
 static int rollout_lqr_relin_launch(const char *name, f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
                                     const f16_mpc_weights *h_w, double *traj, double *u_traj, double *K_traj, int32_t *status,
                                     long B, long ld, int nsteps, int hold, int traj_every, unsigned track_mask, double eps, double dt,
@@ -885,9 +857,7 @@ static int rollout_lqr_relin_launch(const char *name, f16_ctx *ctx, double *x, d
   a.B = B; a.ld = ld; a.nsteps = nsteps; a.every = traj_every; a.hold = hold < nsteps ? hold : nsteps; a.track = track_mask & 0x1FFu;
   a.eps = eps; a.dt = dt; a.xcg = xcg; a.fi = fi_flag; a.flags = flags;
   hipLaunchKernelGGL(k_rollout_lqr_relin, dim3(wave_grid(B)), dim3(64), 0, (hipStream_t)stream, a);
-  char msg[64];
-  snprintf(msg, sizeof msg, "%s launch", name);
-  return hip_check(hipGetLastError(), msg);
+  return launch_check(name);
 }
 
 extern "C" int f16_rollout_lqr_relin(f16_ctx *ctx, double *x, double *u, const double *x_ref, const double *u0,
@@ -955,11 +925,6 @@ static int mpc_check_settings(const f16_qp_settings &s, bool need_iterations, co
   if (s.adaptive_rho && s.rho_every % s.check_every != 0) return einval("%s: with adaptive_rho, rho_every must be a multiple of check_every", entry);
   if (need_iterations && s.max_iter < 1) return einval("%s: max_iter must be >= 1", entry);
   return F16_OK;
-}
-
-static bool stream_capturing(void *stream) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
 // Per-call workspace of `entry`, stream-ordered (see f16_ctx.h) -- and therefore refused under stream capture, here and nowhere

@@ -5,6 +5,7 @@
 
 struct f16_ctx {
   int device;
+  int cus;          // compute units of `device`, asked once at f16_create (0: the query failed): the resident grids of the MPC launches
   double *d_tab;    // [TABLE_IMAGE_DOUBLES] hifi node-major image
   double *d_lofi;   // [LOFI_IMAGE_DOUBLES]
   int *d_tab32;     // [i32::IMAGE_INTS] hifi image as scaled integers (large-batch rollout)

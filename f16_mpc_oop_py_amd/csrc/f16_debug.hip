@@ -46,12 +46,7 @@ __host__ __device__ inline TabLoc table_location(int tid) {
 __global__ __launch_bounds__(64) void k_dbg_table(const double *__restrict__ tab, int tid, const double *alpha,
                                                   const double *beta, const double *el, double *out, int32_t *status, int n) {
   __shared__ __attribute__((aligned(16))) double T[TABLE_IMAGE_DOUBLES];
-  {
-    const double2 *src = reinterpret_cast<const double2 *>(tab);
-    double2 *dst = reinterpret_cast<double2 *>(T);
-    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += 64) dst[i] = src[i];
-    __syncthreads();
-  }
+  stage_tables<64>(T, tab);
   const TabLoc L = table_location(tid);
   for (int p = blockIdx.x * 64 + threadIdx.x; p < n; p += gridDim.x * 64) {
     const double a = alpha[p], b = beta[p], e = el[p];

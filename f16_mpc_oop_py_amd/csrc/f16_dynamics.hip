@@ -35,7 +35,7 @@
 
 namespace f16 {
 
-// (DynArgs, SchedArgs, RowAhead, lqr_action, stage_tables and the launch geometry: f16_rollout_common.hpp, shared with f16_wind.hip)
+// (DynArgs, SchedArgs, RowAhead, lqr_action and the launch geometry: f16_rollout_common.hpp, shared with f16_wind.hip; stage_tables: f16_plant.hpp)
 // The COST instantiations (f16_rollout_cost) score the scheduled rollout: a third type, DynArgs and SchedArgs stay what they are.  Lane b is
 // sample b / B0 of aircraft b % B0: its state comes from column b % B0 of x0 (read-only) and nothing is integrated in place -- `out`
 // is the cost column [ld], the per-lane array the schedule rows are addressed from (RowAhead); x_end may be null.  The weights are

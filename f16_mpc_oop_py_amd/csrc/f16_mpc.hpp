@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/f16_hip.h"
 #include "f16_ctx.h"
@@ -158,6 +159,22 @@ struct RolloutMpcCall {
   const double *soft6;        // the plan's soft state rows (host: six penalty weights, SROW order), or null: hard rows
 };
 int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall &c, void *stream);
+
+// ---- launch rules the solver files share (host)
+// Is `stream` being captured into a HIP graph?  (Per-call workspaces and attribute calls are refused or skipped then.)
+inline bool stream_capturing(void *stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+// The spread of a wavefront-solver launch over a batch of B without a dispatch order: workgroup (or ticket) w takes aircraft
+// (w * stride) % B -- a prime that does not divide B (B has at most a few of these factors); 0: the identity (B <= 16, F16_MPC_SPREAD=0).
+inline unsigned mpc_spread_stride(long B) {
+  static const bool spread = [] { const char *e = getenv("F16_MPC_SPREAD"); return !(e && e[0] == '0'); }();
+  if (!spread || B <= 16) return 0;
+  for (unsigned p : {2053u, 2063u, 2069u, 2081u, 2083u, 2087u, 2089u, 2099u})
+    if (B % p != 0) return p;
+  return 0;
+}
 
 // f16_mpc_big.hip: one 512-lane workgroup per aircraft, 33 <= N <= 150 (operands in the HBM workspace `bigws`)
 size_t mpc_big_ws_doubles(int N);

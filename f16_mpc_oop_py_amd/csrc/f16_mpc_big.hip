@@ -982,12 +982,7 @@ int mpc_big_opt_in() {
 static int big_launch(f16_ctx *ctx, const MpcArgs &a, void *stream, int sw_lo, int sw_hi, double *sw_base, double *sw_ucmd,
                       double *sw_info, int32_t *sw_status, unsigned int *sw_next, int32_t *sw_iters = nullptr,
                       const int32_t *sw_order = nullptr) {
-  (void)ctx;
-  {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = stream && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    if (!capturing) { if (int rc = mpc_big_opt_in()) return rc; }      // (a captured plan solve: done by f16_mpc_plan_create)
-  }
+  if (!stream_capturing(stream)) { if (int rc = mpc_big_opt_in()) return rc; }      // (a captured plan solve: done by f16_mpc_plan_create)
   const bool sweep = sw_hi > 0;
   if (sweep && (sw_lo < 1 || sw_hi < sw_lo || sw_hi > BIG_MAXN || !sw_base || !sw_ucmd || !sw_next)) return set_error(F16_EINVAL, "horizon sweep: bad arguments");
   big::SweepArgs sw{};
@@ -997,9 +992,7 @@ static int big_launch(f16_ctx *ctx, const MpcArgs &a, void *stream, int sw_lo, i
   const long total = sweep ? (long)(sw_hi - sw_lo + 1) * a.B : a.B;
   long grid = total < 65536 ? total : 65536;
   if (sweep) {                                            // resident workgroups only (two per CU at most: LDS)
-    int cus = 256, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = ctx->cus > 0 ? ctx->cus : 256;
     if (grid > 2L * cus) grid = 2L * cus;
   }
   hipLaunchKernelGGL(big::k_mpc_big, dim3((unsigned)grid), dim3(big::BLK), lds, (hipStream_t)stream, a, sw);

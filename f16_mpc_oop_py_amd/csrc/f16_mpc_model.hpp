@@ -2,7 +2,8 @@
 // the zero-order hold (c2d_wave), the DARE by structure-preserving doubling on the fp64 matrix cores (dare_sda_wave) and the model
 // part of the condensed MPC QP (Q, Qbar, G_k, packed P).  Shared by f16_control.hip (k_c2d, k_lqr, k_rollout_lqr_relin, k_mpc) and
 // f16_mpc_wave.hip (the closed MPC loop that re-derives its model at every step); the library is not built with relocatable
-// device code, so what two translation units run has to live in a header.
+// device code, so what two translation units run has to live in a header.  The stage in front of these -- the linearisation that
+// produces the (A, B, C) they take -- is f16_linearise.hpp, shared in the same way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -43,6 +43,7 @@
 #include "f16_mpc_state.hpp"
 #include "f16_osqp_rules.hpp"
 #include "f16_plant.hpp"
+#include "f16_linearise.hpp"
 #include "f16_smallmat.hpp"
 #include "f16_wave_tables.inc"
 
@@ -1618,9 +1619,8 @@ __device__ __noinline__ int pair_prepare(PairIO *io) {
   if (uniform_flag((stw & ST_ENVELOPE) != 0)) code = PAIR_FROZEN;
   else {
     bool fin = true;
-    const int MX[9] = {3, 4, 7, 8, 9, 10, 11, 17, 16};
 #pragma unroll
-    for (int i = 0; i < 9; ++i) fin = fin && isfinite(x[MX[i]]);
+    for (int i = 0; i < 9; ++i) fin = fin && isfinite(x[mpc_x_index(i)]);
     fin = fin && isfinite(x[13]) && isfinite(x[14]) && isfinite(x[15]);
     double dm[3];
 #pragma unroll
@@ -1635,7 +1635,7 @@ __device__ __noinline__ int pair_prepare(PairIO *io) {
       if (l < 9) {
         double v = x[0];
 #pragma unroll
-        for (int i = 0; i < 18; ++i) v = MX[l] == i ? x[i] : v;
+        for (int i = 0; i < 18; ++i) v = mpc_x_index(l) == i ? x[i] : v;
         s_w[RU_X9 + l] = v;
         s_w[RU_XREF + l] = (l >= 5 && l < 8) ? (l == 5 ? dm[0] : (l == 6 ? dm[1] : dm[2])) : v;          // env.py:380-383
       }
@@ -1721,7 +1721,7 @@ __device__ __noinline__ void pair_finish(const PairIO *io, int code) {
 // (x.values with u.values[1:4] in place of the actuator states, env.py:175-177), and everything of the QP that depends on the model
 // only, written into the aircraft's own blocks of the plan's workspace (A | Q | Qbar, G, packed P) -- where pair_prepare and
 // solve_aircraft pick it up exactly as they pick up a frozen plan's.  The pieces are the ones k_rollout_lqr_relin and k_mpc<true> run
-// (f16_plant.hpp: xdot_na_exact; f16_mpc_model.hpp: c2d_wave, dare_sda_wave, mpc_model_*), so f16_mpc_batch_w on the stored model
+// (f16_linearise.hpp: linearise_na_wave; f16_mpc_model.hpp: c2d_wave, dare_sda_wave, mpc_model_*), so f16_mpc_batch_w on the stored model
 // builds the same QP bit for bit.  Scratch: the solver's LDS block, idle between two solves:
 constexpr int RM_F = 0, RM_A = RM_F + 13 * 9 + 1, RM_B = RM_A + 82, RM_C = RM_B + 28, RM_AD = RM_C + 82, RM_BD = RM_AD + 82, RM_Q = RM_BD + 28,
               RM_QB = RM_Q + 82, RM_X = RM_QB + 82, RM_JIT = RM_X + 82, RM_CD = RM_JIT + 54, RM_SCR = RM_CD + 10,
@@ -1773,30 +1773,9 @@ __device__ __noinline__ int pair_model(PairIO *io, const ModelIO *mo) {
          *Qb = s_w + RM_QB, *X = s_w + RM_X, *jit = s_w + RM_JIT, *cd = s_w + RM_CD, *scr = s_w + RM_SCR, *G = s_w + RM_G;
   const double eps = mo->eps;
   wave_lds_sync();
-  // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps).  Lane l < 12: column
-  // l (mpc_x_idx = [3,4,7,8,9,10,11,17,16], inputs -> [13,14,15]); lane 12: the base point.  As k_rollout_lqr_relin.
-  if (l < 13) {
-    const int idx = l == 0 ? 3 : l == 1 ? 4 : l == 2 ? 7 : l == 3 ? 8 : l == 4 ? 9 : l == 5 ? 10 : l == 6 ? 11
-                  : l == 7 ? 17 : l == 8 ? 16 : l < 12 ? 13 + (l - 9) : -1;
-    double sv[18], f[9];
-#pragma unroll
-    for (int k = 0; k < 18; ++k) sv[k] = x[k];
-    sv[13] = u3[0]; sv[14] = u3[1]; sv[15] = u3[2];      // env.py:175-177
-    double base = 0.0, pert = 0.0;
-#pragma unroll
-    for (int k = 0; k < 18; ++k)
-      if (k == idx) { base = sv[k]; pert = sv[k] + eps; sv[k] = pert; }
-    int sl = 0;      // (the grid bits of the perturbed points are not the aircraft's: build_ssr does not keep them)
-    xdot_na_exact(io->tab, io->lofi, sv, f, io->xcg, io->fi, io->flags, &sl);
-#pragma unroll
-    for (int r = 0; r < 9; ++r) F[l * 9 + r] = f[r];
-    if (l < 9) cd[l] = (pert - base) / eps;
-  }
-  __syncthreads();
-  for (int e = l; e < 108; e += 64) {
-    if (e < 81) { const int r = e / 9, c = e - r * 9; A[e] = (F[c * 9 + r] - F[12 * 9 + r]) / eps; }
-    else { const int e2 = e - 81, r = e2 / 3, c = e2 - r * 3; Bm[e2] = (F[(9 + c) * 9 + r] - F[12 * 9 + r]) / eps; }
-  }
+  // env.py:294-342 (f16_linearise_batch): forward differences at (x, u[1:4]), eps; C = diag((x + eps - x) / eps): f16_linearise.hpp,
+  // the one definition k_rollout_lqr_relin calls too
+  linearise_na_wave(io->tab, io->lofi, x, u3[0], u3[1], u3[2], eps, io->xcg, io->fi, io->flags, F, A, Bm, cd, l);
   for (int e = l; e < 81; e += 64) { const int i = e / 9, j = e - i * 9; Cm[e] = i == j ? cd[i] : 0.0; }
   __syncthreads();
   c2d_wave<9, 3>(A, Bm, io->dt, Ad, Bd, scr);                                           // f16_c2d_batch
@@ -1872,27 +1851,17 @@ bool mpc_wave_enabled(const MpcArgs &a) {
 }
 
 int mpc_wave_solve_launch(f16_ctx *ctx, const MpcArgs &a, void *stream, const double *soft6) {
-  (void)ctx;
   if (a.N < 1 || a.N > WAVE_MAXN || !a.gramws) return set_error(F16_EINVAL, "wavefront MPC solver needs 1 <= N <= 30 and a workspace");
   if (a.B > 0x7fffffffL) return set_error(F16_EINVAL, "batch too large for one launch");
   MpcArgs w = a;
-  static const bool spread = [] { const char *e = getenv("F16_MPC_SPREAD"); return !(e && e[0] == '0'); }();
-  w.wave_stride = 0;
-  if (!a.order && spread && a.B > 16) {
-    static const unsigned primes[] = {2053, 2063, 2069, 2081, 2083, 2087, 2089, 2099};      // (B has at most a few of these factors)
-    for (unsigned p : primes)
-      if (a.B % p != 0) { w.wave_stride = p; break; }
-  }
+  w.wave_stride = a.order ? 0 : mpc_spread_stride(a.B);
   // one workgroup per SIMD and a work queue of our own (see k_mpc_wave); the counter is the spare slot behind the scaling block of
   // aircraft 0's workspace.  F16_MPC_WAVE_QUEUE=0: one workgroup per aircraft, distributed by the hardware.
   static const bool queue = [] { const char *e = getenv("F16_MPC_WAVE_QUEUE"); return !(e && e[0] == '0'); }();
   unsigned grid = (unsigned)a.B;
   w.wave_queue = nullptr;
   if (queue) {
-    static const int cus = [] {                              // (one GPU model per process: asked once)
-      int dev = 0, n = 0;
-      return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) ? n : 0;
-    }();
+    const int cus = ctx->cus;
     if (cus > 0 && a.B > 4L * cus) {
       w.wave_queue = reinterpret_cast<unsigned *>(a.gramws + wave::GW_SCAL + wave::GW_QUEUE);
       int rc = hip_check(hipMemsetAsync(w.wave_queue, 0, sizeof(unsigned), (hipStream_t)stream), "f16_mpc_batch work-queue counter");
@@ -1924,18 +1893,9 @@ int mpc_wave_rollout_launch(f16_ctx *ctx, const MpcArgs &a, const RolloutMpcCall
   r.tab = ctx->d_tab; r.lofi = ctx->d_lofi;
   r.T = c.T; r.every = c.every; r.hold = c.hold; r.dem_hold = c.dem_hold > 0 ? c.dem_hold : 0x7fffffff; r.dtp = c.dt; r.xcg = c.xcg; r.fi = c.fi; r.flags = c.flags;
   r.total = (unsigned)((unsigned long long)a.B * (unsigned long long)c.T);
-  r.stride = 0;
-  static const bool spread = [] { const char *e = getenv("F16_MPC_SPREAD"); return !(e && e[0] == '0'); }();
-  if (spread && a.B > 16) {
-    static const unsigned primes[] = {2053, 2063, 2069, 2081, 2083, 2087, 2089, 2099};
-    for (unsigned p : primes)
-      if (a.B % p != 0) { r.stride = p; break; }
-  }
+  r.stride = mpc_spread_stride(a.B);
   if (int rc = hip_check(hipMemsetAsync(c.sync, 0, 8 + (size_t)a.B * sizeof(int32_t), (hipStream_t)stream), "f16_rollout_mpc counters")) return rc;
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) ? n : 0;
-  }();
+  const int cus = ctx->cus;
   // one wavefront-workgroup per SIMD (all resident: 40 KB of LDS each, four per CU); never more than aircraft -- the surplus could
   // only wait
   const long slots = cus > 0 ? 4L * cus : 1024;

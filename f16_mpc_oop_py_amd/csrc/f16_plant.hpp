@@ -1275,4 +1275,14 @@ static __device__ __noinline__ void xdot_na_exact(const double *tab, const doubl
   *stio |= st;
 }
 
+// Cooperative copy of the table image into LDS (16 B per lane per load), ended by a barrier.  BLOCK: the workgroup size where the
+// kernel knows it (a constant stride); 0: as the launch has it (a read of the dispatch packet).
+template <int BLOCK = 0> F16_DEV void stage_tables(double *lds, const double *__restrict__ g) {
+  const double2 *src = reinterpret_cast<const double2 *>(g);
+  double2 *dst = reinterpret_cast<double2 *>(lds);
+  if constexpr (BLOCK > 0) { for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += BLOCK) dst[i] = src[i]; }
+  else { for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += blockDim.x) dst[i] = src[i]; }
+  __syncthreads();
+}
+
 }  // namespace f16

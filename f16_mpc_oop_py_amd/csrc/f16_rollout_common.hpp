@@ -1,6 +1,6 @@
 // f16_rollout_common.hpp -- what the rollout kernels of f16_dynamics.hip and of f16_wind.hip share, stated once: the argument blocks
-// of the constant-input and scheduled rollouts, the look-ahead of a schedule's rows (RowAhead), the LQR action, the staging of the
-// table image, and on the host the launch geometry and the argument rules.
+// of the constant-input and scheduled rollouts, the look-ahead of a schedule's rows (RowAhead), the LQR action, and on the host the
+// launch geometry and the argument rules.  (The staging of the table image, stage_tables, is f16_plant.hpp's: every kernel file uses it.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -94,14 +94,6 @@ struct RowAhead {
 // not an LQR output (test_env_mk2.py:76-79 overwrites u.values[1:] only).  kr = K[i][4..6] of the lane's row.
 F16_DEV double lqr_action(double kr0, double kr1, double kr2, double e0, double e1, double e2, double u0) {
   return -(kr0 * e0 + kr1 * e1 + kr2 * e2) + u0;
-}
-
-// Cooperative copy of the table image into LDS (16 B per lane per load).
-__device__ __forceinline__ void stage_tables(double *lds, const double *__restrict__ g) {
-  const double2 *src = reinterpret_cast<const double2 *>(g);
-  double2 *dst = reinterpret_cast<double2 *>(lds);
-  for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
 }
 
 // ---- launch geometry and argument rules (host)

@@ -288,16 +288,6 @@ __device__ __forceinline__ void nm_run(const F &f, const int s, const bool skip,
   }
 }
 
-// the table image of the hifi plant in LDS, once per workgroup
-__device__ __forceinline__ void stage_tables(double *tab, const double *image, int fi) {
-  if (fi == 1) {
-    const double2 *src = reinterpret_cast<const double2 *>(image);
-    double2 *dst = reinterpret_cast<double2 *>(tab);
-    for (int i = threadIdx.x; i < TABLE_IMAGE_DOUBLES / 2; i += 256) dst[i] = src[i];
-    __syncthreads();
-  }
-}
-
 struct LevelCost {
   const double *tab, *lofi;
   double h, V, xcg;
@@ -310,7 +300,7 @@ struct LevelCost {
 
 __global__ __launch_bounds__(256) void k_trim(TrimArgs a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
-  stage_tables(tab, a.tab, a.fi);
+  if (a.fi == 1) stage_tables<256>(tab, a.tab);      // the table image of the hifi plant in LDS, once per workgroup
   const int s = threadIdx.x & 15;                                 // candidate slot of this lane
   // one row per condition, four conditions per wavefront; wavefronts stride over the batch independently (no barrier below)
   for (long b = (long)blockIdx.x * 16 + (threadIdx.x >> 4); b < ((a.B + 3) & ~3L); b += (long)gridDim.x * 16) {
@@ -405,7 +395,7 @@ struct ManCost {
 
 __global__ __launch_bounds__(256) void k_trim_man(TrimManArgs a) {
   __shared__ __attribute__((aligned(16))) double tab[TABLE_IMAGE_DOUBLES];
-  stage_tables(tab, a.tab, a.fi);
+  if (a.fi == 1) stage_tables<256>(tab, a.tab);      // the table image of the hifi plant in LDS, once per workgroup
   const int s = threadIdx.x & 15;
   const double pi = 3.141592653589793;
   const double x0_ref[6] = {5000, -0.09, 8.49, -0.01, 0.01, 0.0};   // the level trim's start, beta = 0

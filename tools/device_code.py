@@ -6,7 +6,7 @@ instruction stream of every device function (assembly: labels renumbered, commen
     python tools/device_code.py f16_dynamics.hip f16_wind.hip ... [--parent REV] [--allow-new]
 
 names every device function of these files that is missing, new (an error unless --allow-new), or differs from REV's in instructions
-or resource figures, and exits non-zero if there is one.  REV defaults to HEAD while csrc/ or include/ differ from it, else HEAD~1."""
+or resource figures -- with the figures of each such function before -> after -- and exits non-zero if there is one.  REV defaults to HEAD while csrc/ or include/ differ from it, else HEAD~1."""
 import argparse
 import functools
 import os
@@ -109,6 +109,15 @@ def differences(parent, name):
     diffs += [f"{name}: {f}: new" for f in asm_after if f not in asm_before]
     diffs += [f"{name}: {f}: instructions differ" for f in asm_before if f in asm_after and asm_before[f] != asm_after[f]]
     diffs += [f"{name}: {n}: resource figures differ" for n, k in before.items() if n in after and figures(k) != figures(after[n])]
+    # the figures of every function named above that the compiler reports on, before -> after, with its instruction counts
+    for n, k in before.items():
+        sym = k["mangled"]
+        if n in after and (figures(k) != figures(after[n]) or asm_before.get(sym) != asm_after.get(sym)):
+            diffs.append(f"{name}: {n}: figures: instructions {len(asm_before.get(sym, []))} -> {len(asm_after.get(sym, []))}; "
+                         + "; ".join(f"{f.split(' [')[0]} {k[f]} -> {after[n][f]}" for f in FIELDS))
+    kernels = {k["mangled"] for k in before.values()}
+    diffs += [f"{name}: {f}: figures: instructions {len(asm_before[f])} -> {len(asm_after[f])} (a device function: the compiler reports no figures of its own)"
+              for f in asm_before if f in asm_after and asm_before[f] != asm_after[f] and f not in kernels]
     return len(asm_before), len(asm_after), diffs
 
 
@@ -129,7 +138,7 @@ def main():
                   f"instructions differ {count('instructions differ')}, resource figures differ {count('figures differ')}", flush=True)
             for d in diffs:
                 print("  " + d)
-            bad += [d for d in diffs if not (args.allow_new and d.endswith(": new"))]
+            bad += [d for d in diffs if not (args.allow_new and d.endswith(": new")) and ": figures: " not in d]
     sys.exit(f"{len(bad)} differences from {rev}" if bad else 0)
 
 

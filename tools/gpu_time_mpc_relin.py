@@ -104,7 +104,7 @@ def main():
     if args.child:
         return child(args.child, args.steps, args.repeats)
     out = dict(tool="gpu_time_mpc_relin", steps=args.steps, repeats=args.repeats, xcg=0.35, hzn=N, demands=DEM, settings="OSQP defaults",
-               sizes={})
+               so=os.path.basename(os.environ.get("F16HIP_SO", "libf16hip.so")), sizes={})
     for B in (int(s) for s in args.sizes.split(",")):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", str(B), "--steps", str(args.steps), "--repeats", str(args.repeats)]
         try:
